@@ -2,6 +2,7 @@
 """bench.py -- throughput of the pitch-corrector / vocoder hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode pitch|voc|both] [--streams S] [--block N] [--exchange]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one processBlock() over the whole stream batch: S streams x N samples per GPU (default the
 BASELINE.json configs[1] workload: 256 mono streams, pitch corrector only, 1024-sample frames,
@@ -13,6 +14,13 @@ starts.  One process per GPU.  `--gpus N` with N > 1 and no launcher (WORLD_SIZE
 process spawn N rank processes itself (before anything here touches a GPU) and wait for them; under
 `python -m torch.distributed.run ...` the ranks are the launcher's.  Every rank owns its own S streams
 (weak scaling, streams are independent: no data-path collective in `value`), rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, the long stretch of value_long (untimed: it brings the chip to its sustained
+clocks), WAKE_STEPS + W warm-up steps, exactly K timed steps, the result line
+(`value`, `ms_per_step`, the `roofline` of the timed region's own sampled events).  `--dump-outputs DIR` writes what the last timed
+step handed back, DIR/y.npy (float32 [blocks per step][S][2][N]; above 64 MB a fixed seeded sample of the
+streams): the inputs are seeded, so two builds can be compared output for output.  Everything below but `roofline` and `rccl`
+is measured only with `--full` (the exchange also with --exchange).
 
 Besides the contract fields the line carries
   roofline     -- dominant kernel, ALGORITHMIC bytes (3072 B per pitch frame, 5120 B with the
@@ -36,7 +44,9 @@ Besides the contract fields the line carries
   configs4     -- BASELINE configs[4]'s per-GPU share: 48 kHz, 2048-pt frames hop 512, orders 48/48/30, 512 streams, both
                   processes (its frames are 512-sample hops)
   value_long   -- the headline workload again for about --long-seconds (6 s: a 20-step driver run times 1.3 ms; this is the stable
-                  figure, and the stretch in which an outside observer's rocm-smi samples see the GPU busy)
+                  figure, and the stretch in which an outside observer's rocm-smi samples see the GPU busy).  It and the
+                  figures timed before the headline (the other IIR mode, 8 blocks per call) run on a second processor of the
+                  same configuration, so that the headline's processor takes the same blocks in every run
 The per-kernel durations (`kernel_us`, `roofline.avg_kernel_us`) are HIP events around every 8th launch of THE timed region;
 `value_long` runs without any event record, and `roofline.step_us_without_events` is its time per step (one launch per step: an
 upper bound of the kernel's duration that carries no event overhead).
@@ -62,6 +72,10 @@ PROFILE_EVERY = 8       # kernel durations are sampled live inside the timed reg
 VALU_LANE_OPS_PEAK = 256 * 4 * 16 * 2.4e9
 HBM_PEAK_GBS = 8000.0                                                  # MI355X_MICROARCH.md
 UNIQUE_BLOCKS = 16                                                      # synthetic input ring, cycled
+# untimed steps of the headline processor before its W warm-up ones: a fresh processor's first blocks run slow (a 20-step region
+# five blocks after prepare measured 4 % under one 2000 blocks after it, both behind the long stretch), and a fixed count keeps the
+# processor's state -- and the output of the last timed step -- the same from run to run
+WAKE_STEPS = 2000
 COUNTERS_JSON = os.path.join(ROOT, "profiles", "r06_counters.json")
 
 
@@ -253,6 +267,21 @@ def parity_vs_oracle(make, S_, N_, fs_, prepare, params, mono_, first_stream, ii
     return out
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(d, y):
+    """--dump-outputs: what the headline's last timed step handed back, y [blocks per step][S][2][N] float32, as d/y.npy.  Above
+    DUMP_CAP_BYTES a fixed seeded sample of the streams (the same for every run of the same arguments), in stream order."""
+    import numpy as np
+    a = y.cpu().numpy()
+    if a.nbytes > DUMP_CAP_BYTES:
+        keep = max(1, DUMP_CAP_BYTES * a.shape[1] // a.nbytes)
+        a = a[:, np.sort(np.random.default_rng(0).choice(a.shape[1], keep, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "y.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 # fp64 vector instructions one wavefront executes per frame in vp_k_stft_fused<false, false> (its loop body is straight-line: one pass
 # per frame), counted in the disassembly of the built library by tools/kernel_resources.py fp64_op_counts();
 # tests/test_kernel_resources.py fails when the build and these figures part.
@@ -428,7 +457,8 @@ def main():
                     help="arithmetic of the two synthesis IIRs: 'fast' (VP_IIR_FAST, tolerance-tested) is the measured "
                          "configuration; 'exact' (bit-identical to the oracle) is timed beside it as value_exact_mode")
     ap.add_argument("--single-mode", action="store_true",
-                    help="do not time the other IIR mode, the STFT kernel or the secondary configurations (for profiler runs: one kernel population)")
+                    help="with --full: do not time the other IIR mode, the STFT kernel or the secondary configurations (for profiler runs: one "
+                         "kernel population)")
     ap.add_argument("--yin", default="xcorr", choices=["direct", "xcorr", "fft"],
                     help="evaluation of the YIN difference function: 'xcorr' (default) is certified to take the same "
                          "decisions as 'direct' (the reference's arithmetic) and falls back to it otherwise: same output bits")
@@ -445,7 +475,7 @@ def main():
                          "2048/1536, vocoder 2048/512), LPC orders 48/48/30, host block 2048 (a documentation figure: use with --mode both --no-cpu)")
     ap.add_argument("--exchange", action="store_true",
                     help="also time SURVEY 8(e)'s exchange: rank 0 holds the whole batch; per step scatter -> processBlock -> gather "
-                         "(double-buffered, RCCL point-to-point).  On by default when N > 1.")
+                         "(double-buffered, RCCL point-to-point).  On by default with --full when N > 1.")
     ap.add_argument("--voc-path", default="auto", choices=["auto", "workgroup", "batched"],
                     help="vocoder implementation (vp_set_vocoder_path): one workgroup per stream, or the lane-per-window pipeline "
                          "(auto: the pipeline above 256 streams)")
@@ -456,17 +486,23 @@ def main():
                     help="lpcVoice (the plugin's default is 40; BASELINE configs[2] names 24)")
     ap.add_argument("--voc-window", default=None, choices=["512/128", "1024/256"],
                     help="vocoder window/hop: the reference's own 512/128 (default) or the metric's 1024/256 (SURVEY section 8, cfg 3)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--stft-only", action="store_true",
                     help="time the standalone fused STFT kernel alone and print its figure (one kernel population: for the rocprofv3 passes)")
     ap.add_argument("--stft-precision", default="f64", choices=["f64", "f32"], help="with --stft-only: which build of the kernel")
-    ap.add_argument("--no-parity", action="store_true", help="skip the per-leg comparison with the CPU oracle")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the per-leg comparison with the CPU oracle")
     ap.add_argument("--parity-streams", type=int, default=8, help="streams of each leg's batch that are run through the CPU oracle")
     ap.add_argument("--parity-blocks", type=int, default=12, help="blocks per stream of that comparison")
     ap.add_argument("--long-seconds", type=float, default=6.0,
                     help="value_long: the headline workload again for about this long (so that an outside observer -- the driver's "
                          "rocm-smi samples -- sees the GPU busy)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline also measure and check everything else: the other IIR mode, 8 blocks per call, value_long, "
+                         "the +-12-semitone shift, the other BASELINE configs, the STFT kernel, the CPU baseline, parity with the CPU oracle, "
+                         "the exchange when N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step (rank 0) as DIR/y.npy, float32")
     args = ap.parse_args()
 
     # (VP_BENCH_SPAWN=1: take the spawning route even for one rank -- how the route is tested on a one-GPU box)
@@ -494,7 +530,7 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but the launcher started {world} rank(s); reporting n_gpus = {world}", file=sys.stderr)
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
-    do_exchange = (args.exchange or world > 1) and not args.single_mode and args.blocks_per_step == 1
+    do_exchange = (args.exchange or (world > 1 and args.full)) and not args.single_mode and args.blocks_per_step == 1
     use_dist = world > 1 or do_exchange or os.environ.get("VP_BENCH_FORCE_DIST") == "1"   # the latter: exercise the RCCL path on one GPU
     rccl = None
     if use_dist:
@@ -540,14 +576,23 @@ def main():
         q.set_overlap({"auto": "auto", "on": True, "off": False}[args.overlap])
         return q
 
+    secondary = args.full and not args.single_mode       # the figures beside the headline (plain run: the headline alone)
+    check_parity = args.full and not args.no_parity
+    warm_long = args.blocks_per_step == 1 and not args.single_mode       # the long stretch before the headline (value_long)
     p = make_processor(mode, S)
+    # the long stretch and --full's other figures before the headline run on a second processor of the same configuration: the
+    # headline's processor takes the same blocks in every run (WAKE_STEPS, W warm-up steps, the phase alignment, K timed steps), so
+    # its last output does not depend on how many steps the time-bounded stretch took
+    pre = make_processor(mode, S) if (secondary or warm_long) else None
 
-    def set_shift(semi):
+    def set_shift(q, semi):
         for s_ in range(S):
-            p.setPitchShift(semi if s_ % 2 == 0 else -semi, on=True, stream=s_)
+            q.setPitchShift(semi if s_ % 2 == 0 else -semi, on=True, stream=s_)
 
     if args.shift is not None and mode != "voc":
-        set_shift(args.shift)
+        for q_ in (p, pre):
+            if q_ is not None:
+                set_shift(q_, args.shift)
 
     # synthetic inputs in HBM: [U][S][3][N], stream ids unique across ranks
     U = UNIQUE_BLOCKS
@@ -563,21 +608,26 @@ def main():
     mono = mode == "pitch" and not args.three_channel
     xm = x[:, :, 0, :].contiguous() if mono else None                          # [U][S][N]
 
-    blocks_done = [0]                                  # host blocks the headline processor has taken since prepare
+    def make_step(q):
+        """One headline step of processor q; step.blocks_done counts the host blocks q has taken since prepare."""
+        def step(i):
+            step.blocks_done += BPS
+            if BPS == 1:
+                if mono:
+                    q.process_mono_device(xm[i % U], y[0], stream.cuda_stream)
+                else:
+                    q.process_device(x[i % U], y[0], stream.cuda_stream)
+            else:
+                b0 = (i * BPS) % U
+                if mono:
+                    q.process_blocks_mono_device(xm[b0:b0 + BPS], y, stream.cuda_stream)
+                else:
+                    q.process_blocks_device(x[b0:b0 + BPS], y, stream.cuda_stream)
+        step.q, step.blocks_done = q, 0
+        return step
 
-    def step(i):
-        blocks_done[0] += BPS
-        if BPS == 1:
-            if mono:
-                p.process_mono_device(xm[i % U], y[0], stream.cuda_stream)
-            else:
-                p.process_device(x[i % U], y[0], stream.cuda_stream)
-        else:
-            b0 = (i * BPS) % U
-            if mono:
-                p.process_blocks_mono_device(xm[b0:b0 + BPS], y, stream.cuda_stream)
-            else:
-                p.process_blocks_device(x[b0:b0 + BPS], y, stream.cuda_stream)
+    step = make_step(p)
+    pre_step = make_step(pre) if pre is not None else None
 
     def region(fn, steps, warmup):
         """W untimed calls of fn, then exactly K timed ones between barrier + synchronize on both sides"""
@@ -610,67 +660,80 @@ def main():
     mix_period = start_mix(geom["F"], geom["H"], N, 1)[0] if mode != "voc" else 1
     align_info = {"period_blocks": mix_period, "extra_untimed_steps": 0}
 
-    def align_phase():
+    def align_phase(st):
         n = 0
-        while mix_period > 1 and mix_period <= 64 and BPS == 1 and blocks_done[0] % mix_period != 0:
-            step(blocks_done[0])
+        while mix_period > 1 and mix_period <= 64 and BPS == 1 and st.blocks_done % mix_period != 0:
+            st(st.blocks_done)
             n += 1
         return n
 
-    def timed(mode_iir, steps, warmup):
-        p.set_iir_mode(mode_iir)
+    def timed(st, mode_iir, steps, warmup):
+        q = st.q
+        q.set_iir_mode(mode_iir)
         for i in range(warmup):
-            step(i)
-        align_info["extra_untimed_steps"] = align_phase()
+            st(i)
+        align_info["extra_untimed_steps"] = align_phase(st)
         torch.cuda.synchronize(dev)
-        p.profile_read(reset=True)
-        p.profile_enable(PROFILE_EVERY)       # HIP events around every PROFILE_EVERY-th launch of the timed region
-        dt_ = region(lambda i: step(warmup + i), steps, 0)
-        p.profile_enable(False)
-        return dt_, p.profile_read(reset=True)
+        q.profile_read(reset=True)
+        q.profile_enable(PROFILE_EVERY)       # HIP events around every PROFILE_EVERY-th launch of the timed region
+        dt_ = region(lambda i: st(warmup + i), steps, 0)
+        q.profile_enable(False)
+        return dt_, q.profile_read(reset=True)
 
     # secondary figure first (shorter), then THE timed region: W warmup steps, exactly K timed steps
     other = "exact" if args.iir == "fast" else "fast"
     k2 = max(10, args.steps // 4)
     dt_other = float("nan")
-    if not args.single_mode:
-        dt_other, _ = timed(other, k2, max(2, args.warmup // 4))
+    if secondary:
+        dt_other, _ = timed(pre_step, other, k2, max(2, args.warmup // 4))
     # a second secondary figure: the same blocks handed over eight at a time (vp_process_blocks_device: one launch per eight
     # blocks in pitch mode, state stays on chip in between; one launch of the lane-per-window pipeline with eight times the
     # windows in vocoder mode); reported beside `value`, never as it
     MB, k3 = 8, max(4, args.steps // 16)
     dt_mb = float("nan")
-    if not args.single_mode and BPS == 1 and mode in ("pitch", "voc") and U % MB == 0:
+    if secondary and BPS == 1 and mode in ("pitch", "voc") and U % MB == 0:
         ymb = torch.empty((MB, S, 2, N), dtype=torch.float32, device=dev)
-        p.set_iir_mode(args.iir)
+        pre.set_iir_mode(args.iir)
 
         def step_mb(i):
-            blocks_done[0] += MB
+            pre_step.blocks_done += MB
             b0 = (i * MB) % U
             if mono:
-                p.process_blocks_mono_device(xm[b0:b0 + MB], ymb, stream.cuda_stream)
+                pre.process_blocks_mono_device(xm[b0:b0 + MB], ymb, stream.cuda_stream)
             else:
-                p.process_blocks_device(x[b0:b0 + MB], ymb, stream.cuda_stream)
+                pre.process_blocks_device(x[b0:b0 + MB], ymb, stream.cuda_stream)
 
         dt_mb = region(step_mb, k3, 2)
     # the headline workload over a long stretch without any event record, BEFORE the timed region: the stable figure beside a
-    # 20-step driver run, the stretch an outside observer (rocm-smi samples) sees the GPU busy in, and what brings the chip to the
-    # clocks it holds under sustained load before the K timed steps are taken
+    # 20-step driver run (reported with --full), the stretch an outside observer (rocm-smi samples) sees the GPU busy in, and what
+    # brings the chip to the clocks it holds under sustained load before the K timed steps are taken (a plain run too: without it
+    # its 20-step `value` measured 1.3 % under the figure taken behind it)
     frames_per_step_gpu = S * N * BPS // HOP
     value_long = None
-    if not args.single_mode and BPS == 1:
-        p.set_iir_mode(args.iir)
-        region(step, 50, 8)
+    if warm_long:
+        pre.set_iir_mode(args.iir)
+        region(pre_step, 50, 8)
         torch.cuda.synchronize(dev)
         t_probe = time.perf_counter()
-        region(step, 200, 0)
+        region(pre_step, 200, 0)
         (per_step,) = max_over_ranks((time.perf_counter() - t_probe) / 200)
-        kl = max(2000, args.steps, int(args.long_seconds / max(per_step, 1e-6)))
-        dtl = region(step, kl, 8)
+        kl = max(2000, args.steps if args.full else 0, int(args.long_seconds / max(per_step, 1e-6)))   # (plain: bounded in time)
+        dtl = region(pre_step, kl, 8)
         (dtl,) = max_over_ranks(dtl)
-        value_long = {"value": frames_per_step_gpu * kl * n_gpus / dtl, "steps": kl, "ms_per_step": dtl / kl * 1e3}
+        if args.full:
+            value_long = {"value": frames_per_step_gpu * kl * n_gpus / dtl, "steps": kl, "ms_per_step": dtl / kl * 1e3}
+    if pre is not None:
+        torch.cuda.synchronize(dev)
+        pre.close()
+        pre = pre_step = None
+    if warm_long:
+        p.set_iir_mode(args.iir)
+        for i in range(WAKE_STEPS):
+            step(i)
 
-    dt, prof = timed(args.iir, args.steps, args.warmup)
+    dt, prof = timed(step, args.iir, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y)
 
     chk = y.double().abs().sum().view(1)
     if use_dist:
@@ -680,9 +743,9 @@ def main():
     # a third secondary figure, AFTER the headline region: BASELINE configs[1]'s "+-12-semitone pitch shift" (fixed
     # interval, +12 on even and -12 on odd streams; extension without a reference counterpart, parity GPU <-> oracle)
     dt_shift = float("nan")
-    if not args.single_mode and args.shift is None and mode != "voc" and BPS == 1:
-        set_shift(12.0)
-        dt_shift, _ = timed(args.iir, k2, max(4, args.warmup // 2))
+    if secondary and args.shift is None and mode != "voc" and BPS == 1:
+        set_shift(p, 12.0)
+        dt_shift, _ = timed(step, args.iir, k2, max(4, args.warmup // 2))
         (dt_shift,) = max_over_ranks(dt_shift)
         for s_ in range(S):
             p.setPitchShift(0.0, on=False, stream=s_)
@@ -690,12 +753,12 @@ def main():
     # The accuracy half of the metric for the headline workload (and for the secondary modes timed above), on rank 0, outside the
     # timed regions: sampled streams of a fresh processor of the same configuration against the CPU oracle.
     parity = parity_other = parity_shift = None
-    if rank == 0 and not args.no_parity and BPS == 1:
+    if rank == 0 and check_parity and BPS == 1:
         def mk_hl():
             return make_processor(mode, S)
         pk = dict(dev=dev, streams=args.parity_streams, blocks=min(args.parity_blocks, U))
         parity = parity_vs_oracle(mk_hl, S, N, FS, hl_prepare, hl_params, mono, rank * S, args.iir, shift=args.shift, **pk)
-        if not args.single_mode:
+        if secondary:
             parity_other = parity_vs_oracle(mk_hl, S, N, FS, hl_prepare, hl_params, mono, rank * S, other, shift=args.shift, **pk)
             if dt_shift == dt_shift:
                 parity_shift = parity_vs_oracle(mk_hl, S, N, FS, hl_prepare, hl_params, mono, rank * S, args.iir, shift=12.0, **pk)
@@ -779,7 +842,7 @@ def main():
             (dte_,) = max_over_ranks(dte_)
             out_[f"value_{other}_mode"] = (S_ * N_ // hop_) * ke * n_gpus / dte_
             q.set_iir_mode(args.iir)
-        if rank == 0 and not args.no_parity:           # the accuracy half of the metric, in the mode and on the builds just timed
+        if rank == 0 and check_parity:                 # the accuracy half of the metric, in the mode and on the builds just timed
             out_["parity"] = parity_vs_oracle(mk, S_, N_, fs_, prepare, params, mono_, rank * S_, args.iir, dev=dev,
                                               streams=args.parity_streams, blocks=args.parity_blocks)
         if do_exchange and with_exchange:
@@ -797,7 +860,7 @@ def main():
 
     cfg2 = cfg3 = cfg4 = fs48 = lpc24 = None
     k4 = max(120, args.steps // 2)                     # (a leg is tens of milliseconds: long enough for a stable figure whatever --steps is)
-    if not args.single_mode and not args.cfg5 and BPS == 1:
+    if secondary and not args.cfg5 and BPS == 1:
         if not (mode == "voc" and args.lpc_voice == 24):
             cfg2 = {"window_512_128": leg("configs[2]: 256 streams, vocoder, lpcVoice 24, the reference's 512/128 window", "voc", 256, 44100.0, 1024, 256,
                                           None, {"lpcVoice": 24}, k4),
@@ -883,9 +946,9 @@ def main():
             out["fs48k"] = fs48
         if lpc24:
             out["configs1_lpcPitch24"] = lpc24
-        if not args.single_mode:
+        if secondary:
             out["stft_kernel"] = stft_figure(dev, S)
-        if n_gpus == 1 and not args.no_cpu:
+        if n_gpus == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(mode, N, args.cpu_seconds)
 
         # The certificate in brief, INSIDE the objects every consumer of the line keeps (`config`, `roofline`): per leg the accuracy half

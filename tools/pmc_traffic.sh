@@ -5,10 +5,10 @@ tag=${1:-r01}
 out=gpurun_out/pmc_$tag
 mkdir -p $out
 cd /tmp; export TMPDIR=/tmp; cd - >/dev/null
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/mono_fetch -- python3 bench.py --steps 40 --warmup 4 --no-cpu --single-mode > /dev/null 2> $out/mono_fetch.err
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/mono_write -- python3 bench.py --steps 40 --warmup 4 --no-cpu --single-mode > /dev/null 2> $out/mono_write.err
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/3ch_fetch -- python3 bench.py --steps 40 --warmup 4 --no-cpu --single-mode --three-channel > /dev/null 2> $out/3ch_fetch.err
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/3ch_write -- python3 bench.py --steps 40 --warmup 4 --no-cpu --single-mode --three-channel > /dev/null 2> $out/3ch_write.err
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/mono_fetch -- python3 bench.py --full --steps 40 --warmup 4 --no-cpu --single-mode > /dev/null 2> $out/mono_fetch.err
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/mono_write -- python3 bench.py --full --steps 40 --warmup 4 --no-cpu --single-mode > /dev/null 2> $out/mono_write.err
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/3ch_fetch -- python3 bench.py --full --steps 40 --warmup 4 --no-cpu --single-mode --three-channel > /dev/null 2> $out/3ch_fetch.err
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/3ch_write -- python3 bench.py --full --steps 40 --warmup 4 --no-cpu --single-mode --three-channel > /dev/null 2> $out/3ch_write.err
 python3 - <<PY
 import csv, glob, statistics
 for name in ["mono_fetch", "mono_write", "3ch_fetch", "3ch_write"]:
