@@ -64,6 +64,11 @@ struct vp_handle {
     hipEvent_t evFork = nullptr, evJoin = nullptr;
     double *acc2 = nullptr;
     int overlap = VP_OVERLAP_AUTO, acc2Live = 0;
+    // accLive: blocks for which the output accumulator (d.outAcc) may still hold a vocoder window's tail beyond the pitch corrector's
+    // reach -- up to N + W - 1 samples past the block whose windows added it.  The multi-block pitch kernel (process_ws_blocks) keeps
+    // only the launch's first slice of N + C entries from HBM and starts every later block's slice from zeros, so it waits for both
+    // counters to run out (a call after a vocoder block goes block by block until then)
+    int accLive = 0;
     int waveSpec = 1;                           // vp_set_wave_specialised: vp_k_pitch_ws* where they apply (pitch_ws_ok)
     int timeParallel = 0;                       // vp_set_time_parallel: stored and returned, without effect (the analysis front end it selected was removed in round 6)
     std::vector<void *> allocs;
@@ -699,7 +704,7 @@ extern "C" int vp_prepare_explicit(vp_handle *h, double fs, int N, int S, int F,
     RC(dev_alloc(h, &d.synthRing, (size_t)S * 2 * g.inSize));
     RC(dev_alloc(h, &d.outAcc, (size_t)S * g.outSize));
     RC(dev_alloc(h, &h->acc2, (size_t)S * g.outSize));
-    h->acc2Live = 0;
+    h->acc2Live = 0; h->accLive = 0;
     RC(dev_alloc(h, &d.gate, (size_t)S * 2));
     RC(dev_alloc(h, &d.pitch, (size_t)S));
     RC(dev_alloc(h, &d.eFrame, (size_t)S * g.eLen));
@@ -1081,7 +1086,10 @@ static int process_device(vp_handle *h, const float *d_in, float *d_out, hipStre
             }
         }
     }
+    for (auto &co : h->cohorts)
+        if (co.vocOn) h->accLive = (g.outSize + g.N - 1) / g.N + 1;         // (+1: this block's own decrement below)
     h->acc2Live = std::max(0, h->acc2Live - nBlocks);
+    h->accLive = std::max(0, h->accLive - nBlocks);
     for (int b = 0; b < nBlocks; b++) {                                      // MyBuffer.cpp:129-132
         h->outCounter = (h->outCounter + g.N) % g.outSize;
         h->inCounter = (h->inCounter + g.N) % g.inSize;
@@ -1203,6 +1211,7 @@ static int process_voc_blocks(vp_handle *h, const float *d_in, float *d_out, int
     co.vStart = vs;
     h->synthNonZero = g.inSize;
     h->acc2Live = std::max(0, h->acc2Live - nb);
+    h->accLive = (g.outSize + g.N - 1) / g.N;                                // (the call's last block's windows)
     for (int b = 0; b < nb; b++) {                                           // MyBuffer.cpp:129-132
         h->outCounter = (h->outCounter + g.N) % g.outSize;
         h->inCounter = (h->inCounter + g.N) % g.inSize;
@@ -1325,6 +1334,7 @@ static int process_both_blocks(vp_handle *h, const float *d_in, float *d_out, in
     }
     h->synthNonZero = g.inSize;
     h->acc2Live = std::max(0, h->acc2Live - nb);
+    h->accLive = (g.outSize + g.N - 1) / g.N;                                // (the call's last block's windows)
     for (int b = 0; b < nb; b++) {                                           // MyBuffer.cpp:129-132
         h->outCounter = (h->outCounter + g.N) % g.outSize;
         h->inCounter = (h->inCounter + g.N) % g.inSize;
@@ -1403,6 +1413,7 @@ static int process_ws_blocks(vp_handle *h, const float *d_in, float *d_out, int 
     co.nChunk = nChunk;
     h->inCounter = inC; h->outCounter = outC; h->currCounter = curC;
     h->acc2Live = std::max(0, h->acc2Live - nb);
+    h->accLive = std::max(0, h->accLive - nb);
     *done = true;
     return VP_OK;
 }
@@ -1422,7 +1433,7 @@ static int process_blocks_device(vp_handle *h, const float *d_in, float *d_out, 
     // of vp_k_pitch_ws_mb (round 6, process_ws_blocks), else a launch of the single-block kernel per block (44.8
     // against 53.6 us per block for the one-launch phase kernel at 256 streams, round 5)
     const bool wsBlocks = pitchOnly && pitch_ws_ok(h, fast, 1, (h->g.N + h->g.C - 1) / h->g.C);
-    if (wsBlocks && n_blocks > 1 && h->acc2Live == 0) {
+    if (wsBlocks && n_blocks > 1 && h->acc2Live == 0 && h->accLive == 0) {
         // groups of up to WS_MB_MAX blocks per launch of the wave-specialised kernel; what the plan does not take goes block by block below
         const size_t nIn_ = (size_t)h->g.S * (mono ? 1 : 3) * h->g.N, nOut_ = (size_t)h->g.S * 2 * h->g.N;
         while (n_blocks > 1) {

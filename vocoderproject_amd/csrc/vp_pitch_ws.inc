@@ -1058,14 +1058,22 @@ __device__ __forceinline__ void ws_mb_boundary(VpGeom &g, VpCall &c, VpDev &d, c
     }
     ws_lds_barrier();
     // ---- the gate of the next block (see the prologue): the ring's sum of squares updated, decided outside the rounding band -- which
-    // widens with every incremental update --, else by the reference's sequential sum over the ring (which then also resets the drift)
+    // widens with every incremental update --, else by the reference's sequential sum over the ring (which then also resets the drift).
+    // The bound: every rounding since the last exact sum (the prologue's tree sum or a fallback's sequential one) is at most u times an
+    // operand, and every operand is a partial sum of squares of the ring (<= T), of the new samples or of the leaving ones; both of the
+    // latter are <= T_before + T_after.  So with M = the largest T since that exact sum, the drift is <= 2 M u (2 N + 64) per update,
+    // on top of the exact sum's own (2 inSize + 64) M u against the reference's order.  M, not the current T: after a loud passage has
+    // left the ring T is orders of magnitude smaller than the rounding its sums left behind.  M lives in gateRed[16] (in LDS: a register
+    // more spilled around the block loop); thread 0 raises it while the others may still read it -- fmax with the raised value gives
+    // the same Tm.
     {
         double T = gateT;
 #pragma unroll
         for (int w = 0; w < 16; w++) T += gateRed[w];
-        const double Tm = fmax(T, gateT);
-        const double band = Tm * vp_f64_here(2 * g.inSize + 64 + (blk + 1) * (2 * N + 64)) * 1.1102230246251565e-16 * 1.5;
+        const double Tm = fmax(gateRed[16], T);
+        const double band = Tm * vp_f64_here(2 * g.inSize + 64 + 2 * (blk + 1) * (2 * N + 64)) * 1.1102230246251565e-16 * 1.5;
         gateT = T;
+        if (tid == 0) gateRed[16] = Tm;
         if (T - g.gateThrSum > band) gateOpen = 1;
         else if (g.gateThrSum - T > band) gateOpen = 0;
         else {
@@ -1082,7 +1090,7 @@ __device__ __forceinline__ void ws_mb_boundary(VpGeom &g, VpCall &c, VpDev &d, c
             gateOpen = ctl->ishareP[0];
             gateT = gateRed[15];
             __syncthreads();
-            if (tid == 0) { ctl->ishareP[0] = 0; gateRed[15] = 0.0; }
+            if (tid == 0) { ctl->ishareP[0] = 0; gateRed[15] = 0.0; gateRed[16] = gateT; }   // (an exact sum again: the drift starts from it)
         }
         if (tid == 0) d.gate[s * 2 + 0] = gateOpen;
     }

@@ -62,7 +62,11 @@ __device__ __forceinline__ void pitch_ws_body(const VpGeom &g, const VpCall &c, 
     const int pS0 = c.pStart;
     const int span = g.toKeep + g.F + (nSteps - 1) * g.C;
 
+#ifdef WS_MB
+    __shared__ double gateRed[17];                                            // ([16]: see ws_mb_boundary)
+#else
     __shared__ double gateRed[16];
+#endif
     // Everything the block needs from HBM is REQUESTED first -- every loop below only loads into registers, a fixed number of
     // (predicated) trips each, so the requests leave back to back -- and consumed afterwards: loop after loop of load -> convert ->
     // store paid one memory round trip per loop, eleven of them (6 us of prologue).
@@ -294,6 +298,7 @@ __device__ __forceinline__ void pitch_ws_body(const VpGeom &g, const VpCall &c, 
         for (int w = 0; w < 16; w++) T += gateRed[w];
 #ifdef WS_MB
         gateT = T;
+        if (tid == 0) gateRed[16] = T;                                        // the largest T since the last exact sum (ws_mb_boundary)
 #endif
         const double band = T * vp_f64_here(2 * g.inSize + 64) * 1.1102230246251565e-16 * 1.5;
         if (T - g.gateThrSum > band) gateOpen = 1;
