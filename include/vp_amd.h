@@ -328,6 +328,41 @@ int vp_stft_set_runs(vp_stft *p, int runs_per_stream);
 int vp_stft_set_precision(vp_stft *p, int precision);
 int vp_stft_get_precision(const vp_stft *p);
 
+/* Streaming phase vocoder: vp_stft_pitch_shift's pitch shifter driven block by block, with per-stream state (no reference counterpart;
+ * BASELINE configs[1] "256 mono streams, +-12-semitone phase-vocoder pitch shift, 1024-pt FFT hop 256").  One handle holds S independent
+ * streams, frame length F = 1024, hop = 64, 128, 256 or 512 (vp_stft_supported(1024, hop); VP_ERR_GEOMETRY otherwise), block size N >= 1
+ * fixed at create.
+ *  - Per stream, frame f covers input samples [f hop, f hop + F) of everything the stream received since create or its last reset (the
+ *    one-shot's frame grid).  A frame is computed in the call in which its last input sample arrives, with the interval in force for
+ *    that call.
+ *  - Latency L = F - gcd(N, hop) (vp_pv_get_latency): the smallest value at which every output sample is finished -- covered by all the
+ *    frames that will ever cover it -- when it is emitted.  N = 1024 or 4096 at hop 256: 768; N = 64: 960; N = 100: 1020.
+ *  - Output sample t of a stream is sample t - L of the one-shot result; the first L output samples are 0.  With a constant interval the
+ *    concatenated outputs of any number of calls, less the first L samples, are BIT-IDENTICAL to vp_stft_pitch_shift run on the
+ *    concatenated input with that interval, over every sample emitted; how the blocks are grouped into calls (one or n blocks per call,
+ *    host or device entry point) does not change a bit.
+ *  - vp_pv_set_semitones / vp_pv_reset take effect at the next process call issued after them; a call already enqueued does not see
+ *    them.  The changes travel in that call's kernel arguments (ordered on its hip_stream, no host memory read later, no allocation).
+ *    |semitones| <= 12, default 0; stream -1 = every stream.
+ *  - After vp_pv_reset(stream) that stream behaves like a freshly created one with the same interval: its frame grid restarts at the
+ *    next call, its pending overlap-add tail is dropped.  The other streams are untouched.
+ * Device memory is allocated at create only (state: ~16 KB per stream; the host call's staging); vp_pv_debug_alloc_count() stays
+ * constant across process calls.  Arguments are checked before the device is touched: VP_ERR_INVALID_ARG (null pointer, non-positive
+ * size, stream out of range, |semitones| > 12), VP_ERR_GEOMETRY (frame_len != 1024, unsupported hop), VP_ERR_NO_DEVICE (no GPU). */
+typedef struct vp_pv vp_pv;
+int vp_pv_create(int device, int n_streams, int block_size, int frame_len, int hop, vp_pv **out);
+int vp_pv_destroy(vp_pv *p);
+int vp_pv_get_latency(const vp_pv *p);                                  /* F - gcd(N, hop) */
+int vp_pv_set_semitones(vp_pv *p, int stream, double semitones);        /* stream -1 = all; |s| <= 12; default 0 */
+int vp_pv_get_semitones(const vp_pv *p, int stream, double *semitones); /* what the next call uses */
+int vp_pv_reset(vp_pv *p, int stream);                                  /* stream -1 = all */
+/* host float [S][N] -> [S][N]; synchronous */
+int vp_pv_process_block(vp_pv *p, const float *in, float *out);
+/* device float [n_blocks][S][N] -> [n_blocks][S][N] (block b's slab is what vp_pv_process_block would take), enqueued on hip_stream
+ * (a hipStream_t, NULL = default stream) without synchronising, like vp_process_blocks_device */
+int vp_pv_process_blocks_device(vp_pv *p, const float *d_in, float *d_out, int n_blocks, void *hip_stream);
+long vp_pv_debug_alloc_count(const vp_pv *p);                           /* constant across process calls */
+
 const char *vp_error_string(int code);
 const char *vp_last_error(const vp_handle *h);
 int vp_abi_version(void);

@@ -320,4 +320,47 @@ private:
     int nStreams_ = 0, N_ = 0;
 };
 
+// ------------------------------------------------------------------------------------------------
+// vp::StreamingPitchShifter -- the streaming phase vocoder (vp_pv_*, vp_amd.h): S streams, blocks of N samples, state kept across calls.
+// Output sample t of a stream is sample t - latency() of the one-shot vp_stft_pitch_shift on everything the stream received.
+//
+//     vp::StreamingPitchShifter ps(/*device*/ 0, /*streams*/ 256, /*block*/ 1024);   // hop 256
+//     ps.setSemitones(7.0);                             // every stream; ps.setSemitones(-5.0, 3) for stream 3 alone
+//     ps.processBlock(in, out);                         // float [256][1024] -> [256][1024], host memory, synchronous
+class StreamingPitchShifter {
+public:
+    StreamingPitchShifter(int device, int nStreams, int blockSize, int hop = 256, int frameLen = 1024)
+    {
+        check(vp_pv_create(device, nStreams, blockSize, frameLen, hop, &p_), "vp_pv_create");
+    }
+    ~StreamingPitchShifter() { if (p_) vp_pv_destroy(p_); }
+    StreamingPitchShifter(const StreamingPitchShifter &) = delete;
+    StreamingPitchShifter &operator=(const StreamingPitchShifter &) = delete;
+
+    int latency() const { return vp_pv_get_latency(p_); }
+    // takes effect at the next process call; stream = -1: all streams
+    void setSemitones(double semitones, int stream = -1) { check(vp_pv_set_semitones(p_, stream, semitones), "setSemitones"); }
+    double semitones(int stream) const
+    {
+        double v = 0;
+        check(vp_pv_get_semitones(p_, stream, &v), "semitones");
+        return v;
+    }
+    void reset(int stream = -1) { check(vp_pv_reset(p_, stream), "reset"); }
+    void processBlock(const float *in, float *out) { check(vp_pv_process_block(p_, in, out), "processBlock"); }
+    // device float [nBlocks][S][N], enqueued on hipStream without synchronising
+    void processBlocksDevice(const float *dIn, float *dOut, int nBlocks, void *hipStream = nullptr)
+    {
+        check(vp_pv_process_blocks_device(p_, dIn, dOut, nBlocks, hipStream), "processBlocksDevice");
+    }
+    vp_pv *handle() const { return p_; }
+
+private:
+    static void check(int rc, const std::string &what)
+    {
+        if (rc != VP_OK) throw Error(rc, what + ": " + vp_error_string(rc));
+    }
+    vp_pv *p_ = nullptr;
+};
+
 }  // namespace vp

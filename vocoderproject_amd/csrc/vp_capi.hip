@@ -1751,6 +1751,9 @@ struct vp_stft {
     int f32 = 0;                      // vp_stft_set_precision
 };
 
+static float stft_host_tables(int frame_len, int hop, std::vector<double> &w, std::vector<double> &t1, std::vector<double> &t2,
+                              std::vector<double> &ts, std::vector<double> &tt);
+
 static void stft_free(vp_stft *p)
 {
     (void)hipFree(p->win); (void)hipFree(p->tw1); (void)hipFree(p->tw2); (void)hipFree(p->tws); (void)hipFree(p->twTop);
@@ -1774,19 +1777,29 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     if (!p->pvOk) (void)hipGetLastError();
     p->device = device; p->F = frame_len; p->hop = hop; p->S = n_streams; p->T = n_samples;
     p->nFrames = (n_samples - frame_len) / hop + 1;
-    const double PI = 3.141592653589793238;
-    std::vector<double> w(frame_len);
-    double sumsq = 0;                                             // sum over one hop grid of w^2 (constant for periodic Hann)
-    for (int i = 0; i < frame_len; i++) w[i] = std::sqrt(0.5 - 0.5 * std::cos(2.0 * PI * i / frame_len));
-    for (int i = 0; i < frame_len; i += hop) sumsq += w[i] * w[i];
-    p->scale = (float)(1.0 / sumsq);
+    std::vector<double> w, t1, t2, ts, tt;
+    p->scale = stft_host_tables(frame_len, hop, w, t1, t2, ts, tt);
     auto up = [](double **d, const std::vector<double> &v) {
         return hipMalloc(d, v.size() * 8) == hipSuccess && hipMemcpy(*d, v.data(), v.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
     };
+    if (!(up(&p->win, w) && up(&p->tw1, t1) && up(&p->tw2, t2) && up(&p->tws, ts) && (frame_len != 2048 || up(&p->twTop, tt)))) { stft_free(p); delete p; return VP_ERR_OOM; }
+    *out = p;
+    return VP_OK;
+}
+
+// the window and the transform's tables (host libm); returns the overlap-add normalisation
+static float stft_host_tables(int frame_len, int hop, std::vector<double> &w, std::vector<double> &t1, std::vector<double> &t2,
+                              std::vector<double> &ts, std::vector<double> &tt)
+{
+    const double PI = 3.141592653589793238;
+    w.assign(frame_len, 0.0);
+    double sumsq = 0;                                             // sum over one hop grid of w^2 (constant for periodic Hann)
+    for (int i = 0; i < frame_len; i++) w[i] = std::sqrt(0.5 - 0.5 * std::cos(2.0 * PI * i / frame_len));
+    for (int i = 0; i < frame_len; i += hop) sumsq += w[i] * w[i];
     // per-lane twiddles of the wavefront transform (vp_fft.inc fft512), of the real-input split (NP = F / 256 bin pairs per lane:
     // W_F^(64 q + lane)) and, for 2048-point frames, of the radix-2 step on top of two 512-point transforms (W_1024^(64 q + lane)), host libm
     const int NP = frame_len / 256;
-    std::vector<double> t1(64 * 8 * 2), t2(64 * 8 * 2), ts(64 * NP * 2), tt(64 * 8 * 2);
+    t1.assign(64 * 8 * 2, 0.0); t2.assign(64 * 8 * 2, 0.0); ts.assign(64 * NP * 2, 0.0); tt.assign(64 * 8 * 2, 0.0);
     for (int lane = 0; lane < 64; lane++) {
         for (int r = 0; r < 8; r++) {
             const double a1 = -2.0 * PI * (double)(r * (lane >> 3)) / 64.0, a2 = -2.0 * PI * (double)(r * lane) / 512.0;
@@ -1800,9 +1813,7 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
             ts[(lane * NP + q) * 2] = std::cos(a); ts[(lane * NP + q) * 2 + 1] = std::sin(a);
         }
     }
-    if (!(up(&p->win, w) && up(&p->tw1, t1) && up(&p->tw2, t2) && up(&p->tws, ts) && (frame_len != 2048 || up(&p->twTop, tt)))) { stft_free(p); delete p; return VP_ERR_OOM; }
-    *out = p;
-    return VP_OK;
+    return (float)(1.0 / sumsq);
 }
 
 extern "C" int vp_stft_destroy(vp_stft *p)
@@ -1876,4 +1887,159 @@ extern "C" int vp_stft_pitch_shift(vp_stft *p, const float *d_in, float *d_out, 
     if (!p->pvOk) return VP_ERR_HIP;                           // (its dynamic-LDS ceiling could not be raised on this device: vp_stft_create)
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, std::pow(2.0, semitones / 12.0));
+}
+
+// ---- streaming phase vocoder (no reference counterpart): vp_k_pv_stream of vp_stft.hip, the one-shot stage block by block -----------
+struct vp_pv {
+    int device = 0, S = 0, N = 0, F = 0, hop = 0, L = 0;
+    double *win = nullptr, *tw1 = nullptr, *tw2 = nullptr, *tws = nullptr;
+    double c = 0;
+    unsigned char *state = nullptr;             // [S][VP_PV_REC_BYTES] (vp_stft.h)
+    float *stageIn = nullptr, *stageOut = nullptr;   // [S][N]: the host-pointer call's staging
+    hipStream_t ownStream = nullptr;
+    long nAllocs = 0;
+    std::vector<double> semi;                   // [S] the interval the next call uses
+    // changes made since the last process call, as the updates it carries: the all-stream ones first, then the per-stream ones (a
+    // per-stream change is always newer than a pending all-stream one: an all-stream change clears them)
+    double allRatio = 0; bool allReset = false;
+    std::vector<double> ratioPend;              // [S] 0: none
+    std::vector<char> resetPend;                // [S]
+    std::vector<VpPvUpdate> upd;                // staging of the updates (capacity S + 1, reserved at create)
+};
+
+static void pv_free(vp_pv *p)
+{
+    (void)hipFree(p->win); (void)hipFree(p->tw1); (void)hipFree(p->tw2); (void)hipFree(p->tws);
+    (void)hipFree(p->state); (void)hipFree(p->stageIn); (void)hipFree(p->stageOut);
+    if (p->ownStream) (void)hipStreamDestroy(p->ownStream);
+}
+
+extern "C" int vp_pv_create(int device, int n_streams, int block_size, int frame_len, int hop, vp_pv **out)
+{
+    if (!out || n_streams <= 0 || block_size <= 0 || frame_len <= 0 || hop <= 0) return VP_ERR_INVALID_ARG;
+    if ((long long)n_streams * block_size > (1LL << 28) || (long long)block_size > (1 << 24)) return VP_ERR_INVALID_ARG;
+    if (frame_len != 1024 || !vp_stft_supported(frame_len, hop)) return VP_ERR_GEOMETRY;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VP_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    if (vp_pv_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
+    vp_pv *p = new vp_pv();
+    p->device = device; p->S = n_streams; p->N = block_size; p->F = frame_len; p->hop = hop;
+    int g = block_size, b = hop;
+    while (b) { const int t = g % b; g = b; b = t; }
+    p->L = frame_len - g;
+    std::vector<double> w, t1, t2, ts, tt;
+    const float scale = stft_host_tables(frame_len, hop, w, t1, t2, ts, tt);
+    p->c = (double)scale / (double)(frame_len / 2);                      // (as stft_fused)
+    p->semi.assign(n_streams, 0.0);
+    p->ratioPend.assign(n_streams, 0.0);
+    p->resetPend.assign(n_streams, 0);
+    p->upd.reserve(n_streams + 1);
+    auto al = [p](void **d, size_t bytes) { if (hipMalloc(d, bytes) != hipSuccess) return false; p->nAllocs++; return true; };
+    auto up = [&](double **d, const std::vector<double> &v) {
+        return al((void **)d, v.size() * 8) && hipMemcpy(*d, v.data(), v.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    // every stream starts with zero phases, history and carry, ratio 1
+    std::vector<unsigned char> rec((size_t)n_streams * VP_PV_REC_BYTES, 0);
+    for (int s = 0; s < n_streams; s++) { const double one = 1.0; memcpy(&rec[(size_t)s * VP_PV_REC_BYTES + VP_PV_RATIO * 8], &one, 8); }
+    const size_t blk = (size_t)n_streams * block_size * sizeof(float);
+    const bool ok = up(&p->win, w) && up(&p->tw1, t1) && up(&p->tw2, t2) && up(&p->tws, ts)
+        && al((void **)&p->state, rec.size()) && hipMemcpy(p->state, rec.data(), rec.size(), hipMemcpyHostToDevice) == hipSuccess
+        && al((void **)&p->stageIn, blk) && al((void **)&p->stageOut, blk)
+        && hipStreamCreateWithFlags(&p->ownStream, hipStreamNonBlocking) == hipSuccess;
+    if (!ok) { pv_free(p); delete p; (void)hipGetLastError(); return VP_ERR_OOM; }
+    *out = p;
+    return VP_OK;
+}
+
+extern "C" int vp_pv_destroy(vp_pv *p)
+{
+    if (!p) return VP_ERR_INVALID_ARG;
+    (void)hipSetDevice(p->device);
+    (void)hipDeviceSynchronize();
+    pv_free(p);
+    delete p;
+    return VP_OK;
+}
+
+extern "C" int vp_pv_get_latency(const vp_pv *p) { return p ? p->L : VP_ERR_INVALID_ARG; }
+extern "C" long vp_pv_debug_alloc_count(const vp_pv *p) { return p ? p->nAllocs : VP_ERR_INVALID_ARG; }
+
+extern "C" int vp_pv_set_semitones(vp_pv *p, int stream, double semitones)
+{
+    if (!p || stream < -1 || stream >= p->S || !(semitones >= -12.0 && semitones <= 12.0)) return VP_ERR_INVALID_ARG;
+    const double ratio = std::pow(2.0, semitones / 12.0);                // (as vp_stft_pitch_shift: the same bits)
+    if (stream < 0) {
+        p->allRatio = ratio;
+        std::fill(p->ratioPend.begin(), p->ratioPend.end(), 0.0);
+        std::fill(p->semi.begin(), p->semi.end(), semitones);
+    } else {
+        p->ratioPend[stream] = ratio;
+        p->semi[stream] = semitones;
+    }
+    return VP_OK;
+}
+
+extern "C" int vp_pv_get_semitones(const vp_pv *p, int stream, double *semitones)
+{
+    if (!p || !semitones || stream < 0 || stream >= p->S) return VP_ERR_INVALID_ARG;
+    *semitones = p->semi[stream];
+    return VP_OK;
+}
+
+extern "C" int vp_pv_reset(vp_pv *p, int stream)
+{
+    if (!p || stream < -1 || stream >= p->S) return VP_ERR_INVALID_ARG;
+    if (stream < 0) {
+        p->allReset = true;
+        std::fill(p->resetPend.begin(), p->resetPend.end(), 0);
+    } else p->resetPend[stream] = 1;
+    return VP_OK;
+}
+
+// the pending changes travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update launches in front of it): ordered on
+// the caller's stream, no host memory the device reads later, no allocation
+static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipStream_t st)
+{
+    p->upd.clear();
+    if (p->allRatio > 0.0 || p->allReset) p->upd.push_back(VpPvUpdate{-1, p->allReset ? 1 : 0, p->allRatio});
+    for (int s = 0; s < p->S; s++)
+        if (p->ratioPend[s] > 0.0 || p->resetPend[s]) p->upd.push_back(VpPvUpdate{s, p->resetPend[s] ? 1 : 0, p->ratioPend[s]});
+    VpPvArgs a;
+    memset(&a, 0, sizeof a);
+    a.state = p->state; a.win = p->win; a.tw1 = p->tw1; a.tw2 = p->tw2; a.tws = p->tws; a.c = p->c;
+    a.S = p->S; a.N = p->N; a.hop = p->hop; a.O = p->F / p->hop; a.L = p->L;
+    size_t i = 0;
+    while (p->upd.size() - i > VP_PV_MAX_UPDATES) {
+        a.nBlocks = 0; a.nUpd = VP_PV_MAX_UPDATES;
+        for (int k = 0; k < VP_PV_MAX_UPDATES; k++) a.upd[k] = p->upd[i + k];
+        if (vp_pv_launch(a, st) != hipSuccess) return VP_ERR_HIP;
+        i += VP_PV_MAX_UPDATES;
+    }
+    a.in = d_in; a.out = d_out; a.nBlocks = n_blocks; a.nUpd = (int)(p->upd.size() - i);
+    for (int k = 0; k < a.nUpd; k++) a.upd[k] = p->upd[i + k];
+    if (vp_pv_launch(a, st) != hipSuccess) return VP_ERR_HIP;
+    p->allRatio = 0.0; p->allReset = false;
+    std::fill(p->ratioPend.begin(), p->ratioPend.end(), 0.0);
+    std::fill(p->resetPend.begin(), p->resetPend.end(), 0);
+    return VP_OK;
+}
+
+extern "C" int vp_pv_process_blocks_device(vp_pv *p, const float *d_in, float *d_out, int n_blocks, void *hip_stream)
+{
+    if (!p || !d_in || !d_out || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream);
+}
+
+extern "C" int vp_pv_process_block(vp_pv *p, const float *in, float *out)
+{
+    if (!p || !in || !out) return VP_ERR_INVALID_ARG;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    const size_t bytes = (size_t)p->S * p->N * sizeof(float);
+    if (hipMemcpyAsync(p->stageIn, in, bytes, hipMemcpyHostToDevice, p->ownStream) != hipSuccess) return VP_ERR_HIP;
+    const int rc = pv_run(p, p->stageIn, p->stageOut, 1, p->ownStream);
+    if (rc) return rc;
+    if (hipMemcpyAsync(out, p->stageOut, bytes, hipMemcpyDeviceToHost, p->ownStream) != hipSuccess) return VP_ERR_HIP;
+    return hipStreamSynchronize(p->ownStream) == hipSuccess ? VP_OK : VP_ERR_HIP;
 }

@@ -31,3 +31,37 @@ hipError_t vp_stft_launch(const VpStftArgs &a, int nStreams, int nRuns, hipStrea
 int vp_stft_supported(int F, int hop);
 // once per handle, on the handle's device (current device): the dynamic-LDS ceiling of the builds that need more than 64 KB
 hipError_t vp_stft_prepare_device();
+
+// ---- streaming phase vocoder (vp_pv_*): one workgroup per stream and call, state in HBM between calls -----------------------------
+#define VP_PV_MAX_UPDATES 16            // interval changes / resets carried in a process call's arguments
+#define VP_PV_RING 4096                 // overlap-add ring in LDS (floats): the carry plus one round's frames at hop <= 512
+// one stream's state, VP_PV_REC_BYTES each: previous-frame phases [513] | synthesis accumulator [513] | ratio | samples received (int64)
+// (doubles) | input history [F] | overlap-add carry [F] (floats)
+#define VP_PV_NB 513
+#define VP_PV_RATIO (2 * VP_PV_NB)
+#define VP_PV_COUNT (2 * VP_PV_NB + 1)
+#define VP_PV_HIST_BYTES ((2 * VP_PV_NB + 2) * 8)
+#define VP_PV_CARRY_BYTES (VP_PV_HIST_BYTES + 1024 * 4)
+#define VP_PV_REC_BYTES (VP_PV_CARRY_BYTES + 1024 * 4)
+
+struct VpPvUpdate {
+    int stream;                         // -1: every stream
+    int reset;                          // 1: the stream's signal state restarts (its interval stays)
+    double ratio;                       // > 0: the new pitch ratio; 0: unchanged
+};
+
+struct VpPvArgs {
+    const float *in;                    // [nBlocks][S][N]
+    float *out;                         // [nBlocks][S][N]
+    unsigned char *state;               // [S][VP_PV_REC_BYTES]
+    const double *win, *tw1, *tw2, *tws;   // the one-shot's tables (VpStftArgs)
+    double c;                           // the one-shot's normalisation
+    int S, N, nBlocks, hop, O, L;       // streams, block, blocks in this call, hop, F / hop, latency F - gcd(N, hop)
+    int nUpd;
+    VpPvUpdate upd[VP_PV_MAX_UPDATES];
+};
+
+size_t vp_pv_lds_bytes();
+// the streaming kernel (grid = S workgroups); nBlocks = 0 launches the small kernel that only applies the updates
+hipError_t vp_pv_launch(const VpPvArgs &a, hipStream_t st);
+hipError_t vp_pv_prepare_device();

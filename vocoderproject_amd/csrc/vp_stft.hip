@@ -661,3 +661,283 @@ hipError_t vp_stft_launch(const VpStftArgs &a, int nStreams, int nRuns, hipStrea
         hipLaunchKernelGGL((vp_k_stft_fused<false, false>), grid, block, lds, st, a);
     return hipGetLastError();
 }
+
+// ---- streaming phase vocoder (vp_pv_*, include/vp_amd.h) ---------------------------------------------------------------------------
+// vp_k_stft_fused<true, false> block by block: one workgroup per stream and call, the stream's state in HBM between calls (VpPvArgs).
+// Frame f of the stream covers samples [f hop, f hop + F) of everything it received since create / reset and is computed in the call in
+// which its last sample arrives; wavefront w takes the frames 4 r + w by their global index, so the rounds of four frames are the
+// one-shot's, cut where the calls cut them.  The stage below is the one-shot's, statement for statement (same operations on the same
+// operands: the outputs agree bit for bit), except for what a round cut by a call needs:
+//   * the first live frame of the call reads its "previous frame" phases from slot 0 (the state), whatever its wavefront;
+//   * the accumulator of a round sums from the first live frame; a round that the call ends early leaves its partial sum UNWRAPPED (the
+//     next call continues the same left-to-right sum) and only a round's frame 4 r + 3 wraps it;
+//   * the overlap-add works on a ring of one-shot samples (VP_PV_RING floats): frames add in frame order onto what earlier frames and
+//     calls left (every sample starts from 0.f, as in stft_overlap_add), and a sample leaves the ring, to output time t + L, once the
+//     frames that cover it are all in and t + L falls inside the call.  Ring word q belongs to thread q mod 256 throughout: no barrier
+//     between a round's additions and its stores.
+// History (samples of frames not yet complete, < F), carry (< F unfinished or unemitted samples), phases, accumulator, ratio and the
+// sample counter are read into LDS at entry and written back at exit.
+// LDS: exchange buffers / output slots, ring, history, then the one-shot's phase-vocoder arrays (124 KB: one workgroup per CU)
+__host__ __device__ constexpr size_t pv_stream_lds_bytes()
+{
+    return (size_t)NWV * 8192 + (VP_PV_RING + 1024) * sizeof(float) + ((NWV + 1) * VP_PV_NB + NWV * VP_PV_NB * 2 + NWV * VP_PV_NB + VP_PV_NB) * sizeof(double);
+}
+
+__global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream(VpPvArgs A)
+{
+    extern __shared__ double smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int s = blockIdx.x;
+    constexpr int N = 512, F = 1024, nb = N + 1, RM = VP_PV_RING - 1;
+    const int hop = A.hop, O = A.O, L = A.L, NB = A.N, S = A.S;
+    lds_d2 *xb = (lds_d2 *)smem + wv * 512;
+    lds_f32 *slots = (lds_f32 *)smem;                                          // wavefront w's output frame at w * 2048
+    lds_f32 *ring = (lds_f32 *)smem + NWV * 2048;                              // [VP_PV_RING]
+    lds_f32 *hist = ring + VP_PV_RING;                                         // [F]
+    PvLds pv;
+    {
+        lds_f64 *p = (lds_f64 *)(hist + F);
+        pv.ana = (lds_d2 *)p + (size_t)wv * nb; p += NWV * nb * 2;
+        pv.phPrev = p; p += (NWV + 1) * nb;
+        pv.inc = p; p += NWV * nb;
+        pv.sum = p;
+    }
+#ifdef VP_POISON_LDS
+    for (int i = tid; i < (int)(pv_stream_lds_bytes() / 8); i += 64 * NWV) ((lds_f64 *)smem)[i] = __builtin_nan("0x5a5a");
+    __syncthreads();
+#endif
+    unsigned char *rec = A.state + (size_t)s * VP_PV_REC_BYTES;
+    double *recD = (double *)rec;
+    float *recHist = (float *)(rec + VP_PV_HIST_BYTES), *recCarry = (float *)(rec + VP_PV_CARRY_BYTES);
+
+    // the call's interval changes and resets, in the order they were made (arguments: scalar, uniform)
+    double ratio = recD[VP_PV_RATIO];
+    long long n = ((const long long *)recD)[VP_PV_COUNT];                     // samples received before this call
+    bool rst = false;
+    for (int i = 0; i < A.nUpd; i++) {
+        if (A.upd[i].stream != s && A.upd[i].stream != -1) continue;
+        if (A.upd[i].ratio > 0.0) ratio = A.upd[i].ratio;
+        if (A.upd[i].reset) rst = true;
+    }
+    if (rst) n = 0;
+
+    const int M = A.nBlocks * NB;                                              // samples this call
+    const long long R = n + M;
+    const long long fa = n >= F ? (n - F) / hop + 1 : 0;                       // frames complete before the call
+    const long long fb = R >= F ? (R - F) / hop + 1 : 0;                       // ... and after it
+    const int nf = (int)(fb - fa);                                             // frames of this call
+    const int H = (int)(n - fa * hop);                                         // history: samples [fa hop, n) (< F), relative index 0 .. H - 1
+    const int er = H - L;                                                      // relative index of the next sample to emit (output time n)
+    const int fr0 = -(int)(fa & 3);                                            // relative frame of wavefront 0 in the first round
+
+    // state -> LDS (a reset stream starts from zeros)
+    for (int i = tid; i < H; i += 64 * NWV) hist[i] = recHist[i];
+    for (int i = tid; i < nb; i += 64 * NWV) { pv.phPrev[i] = rst ? 0.0 : recD[i]; pv.sum[i] = rst ? 0.0 : recD[nb + i]; }
+    for (int q = tid; q < VP_PV_RING; q += 64 * NWV) {                         // carry[i] = one-shot sample er + i
+        const int i = (q - er) & RM;
+        ring[q] = (i < F && !rst) ? recCarry[i] : 0.f;
+    }
+
+    FftLane Lf;
+    fft_lane_init(Lf, lane, A.tw1, A.tw2);
+    d2 wa[8];
+    d2 ws[4];
+#pragma unroll
+    for (int r = 0; r < 8; r++) wa[r] = ((const d2 *)A.win)[lane + 64 * r];
+#pragma unroll
+    for (int q = 0; q < 4; q++) ws[q] = ((const d2 *)A.tws)[lane * 4 + q];
+    const bool lane0 = lane == 0;
+    __syncthreads();
+
+    const float *xs = A.in + (size_t)s * NB;
+    float *ys = A.out + (size_t)s * NB;
+    // sample at relative index rel (>= 0): the history below H, this call's blocks above
+    auto sample = [&](int rel) -> float {
+        if (rel < H) return hist[rel];
+        const unsigned c = (unsigned)(rel - H), b = c / (unsigned)NB;
+        return xs[(size_t)b * S * NB + (c - b * NB)];
+    };
+    // output time n + c, c in [0, M)
+    auto emit = [&](int c, float v) {
+        const unsigned b = (unsigned)c / (unsigned)NB;
+        ys[(size_t)b * S * NB + ((unsigned)c - b * NB)] = v;
+    };
+    const int nRounds = nf > 0 ? (nf - fr0 + NWV - 1) / NWV : 0;
+    int cb = er;                                                               // next relative index to emit (uniform)
+    f2 xv[8];
+    auto request = [&](int k_) {
+        const int fr_ = fr0 + NWV * k_ + wv;
+        if (k_ < nRounds && fr_ >= 0 && fr_ < nf) {
+#pragma unroll
+            for (int r = 0; r < 8; r++) { const int rel = fr_ * hop + 2 * (lane + 64 * r); xv[r] = f2{sample(rel), sample(rel + 1)}; }
+        }
+    };
+    request(0);
+    for (int k = 0; k < nRounds; k++) {
+        const int frW0 = fr0 + NWV * k;                                        // relative frame of wavefront 0 in this round
+        const int fr = frW0 + wv;
+        const bool live = fr >= 0 && fr < nf;                                  // (wavefront-uniform)
+        const int wFirst = max(0, -frW0), wLast = min(NWV - 1, nf - 1 - frW0);
+        C8 z;
+        RPairs X;
+        if (live) {
+#pragma unroll
+            for (int r = 0; r < 8; r++) { z.re[r] = (double)xv[r].x * wa[r].x; z.im[r] = (double)xv[r].y * wa[r].y; }
+        }
+        request(k + 1);
+        if (live) {
+            fft512_rx(z, xb, Lf);
+            rfft_split(z, xb, lane, (const d2 *)ws, X);
+        }
+        {
+            const double invO = 1.0 / (double)O;
+            const double invRatio = 1.0 / ratio;
+            const int prevSlot = wv == wFirst ? 0 : wv;                        // the call's first frame continues from the state
+            double ph[9];
+            int kb[9];
+            double mg[9];
+            if (live) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    kb[2 * q] = 64 * q + lane; kb[2 * q + 1] = N - kb[2 * q];
+                    mg[2 * q] = sqrt(X.kr[q] * X.kr[q] + X.ki[q] * X.ki[q]); ph[2 * q] = pv_phase_turns(X.ki[q], X.kr[q]);
+                    mg[2 * q + 1] = sqrt(X.mr[q] * X.mr[q] + X.mi[q] * X.mi[q]); ph[2 * q + 1] = pv_phase_turns(X.mi[q], X.mr[q]);
+                }
+                kb[8] = N / 2; mg[8] = sqrt(X.hr * X.hr + X.hi * X.hi); ph[8] = pv_phase_turns(X.hi, X.hr);
+#pragma unroll
+                for (int e = 0; e < 9; e++) if (e < 8 || lane0) pv.phPrev[(wv + 1) * nb + kb[e]] = ph[e];
+            }
+            __syncthreads();
+            if (live) {
+#pragma unroll
+                for (int e = 0; e < 9; e++) {
+                    if (e == 8 && !lane0) continue;
+                    const int k_ = kb[e];
+                    double d = ph[e] - pv.phPrev[prevSlot * nb + k_] - (double)k_ * invO;
+                    d -= rint(d);
+                    pv.ana[k_] = d2{mg[e], (double)k_ + d * (double)O};
+                }
+                wave_sync();
+#pragma unroll
+                for (int e = 0; e < 9; e++) {
+                    if (e == 8 && !lane0) continue;
+                    const int kk = kb[e];
+                    const int kc = (int)((double)kk * invRatio);
+                    double sm = 0.0, sf = 0.0;
+                    d2 cand[5];
+#pragma unroll
+                    for (int c_ = 0; c_ < 5; c_++) cand[c_] = pv.ana[min(max(kc - 2 + c_, 0), N)];
+#pragma unroll
+                    for (int c_ = 0; c_ < 5; c_++) {
+                        const int k_ = kc - 2 + c_;
+                        if (k_ >= 0 && k_ <= N && (int)floor((double)k_ * ratio + 0.5) == kk) { sm += cand[c_].x; sf = cand[c_].y * ratio; }
+                    }
+                    mg[e] = sm;
+                    pv.inc[wv * nb + kk] = sf * invO;
+                }
+            }
+            __syncthreads();
+            if (live) {
+#pragma unroll
+                for (int e = 0; e < 9; e++) {
+                    if (e == 8 && !lane0) continue;
+                    const int kk = kb[e];
+                    double sp = pv.sum[kk];
+                    for (int w = wFirst; w <= wv; w++) sp += pv.inc[w * nb + kk];
+                    ph[e] = sp;
+                    double sn, cs;
+                    pv_sincos_turns(sp, sn, cs);
+                    const double re = mg[e] * cs, im = mg[e] * sn;
+                    if (e == 8) { X.hr = re; X.hi = im; }
+                    else if (e & 1) { X.mr[e >> 1] = re; X.mi[e >> 1] = im; }
+                    else { X.kr[e >> 1] = re; X.ki[e >> 1] = im; }
+                }
+                if (lane0) { X.ki[0] = 0.0; X.mi[0] = 0.0; }
+            }
+            __syncthreads();
+            // the round's last live frame leaves the phases and the accumulator: wrapped at a round's end, the partial sum otherwise
+            if (live && wv == wLast) {
+#pragma unroll
+                for (int e = 0; e < 9; e++) {
+                    if (e == 8 && !lane0) continue;
+                    pv.phPrev[kb[e]] = pv.phPrev[(wv + 1) * nb + kb[e]];
+                    pv.sum[kb[e]] = wv == NWV - 1 ? ph[e] - rint(ph[e]) : ph[e];
+                }
+            }
+        }
+        lds_f2 *slot = (lds_f2 *)(slots + wv * 2048);
+        if (live) {
+            rfft_merge_conj(z, xb, lane, (const d2 *)ws, X, A.c);
+            fft512_rx(z, xb, Lf);
+            wave_sync();
+#pragma unroll
+            for (int r = 0; r < 8; r++) slot[lane + 64 * r] = f2{(float)(z.re[r] * wa[r].x), (float)(-(z.im[r] * wa[r].y))};
+        }
+        __syncthreads();
+        // overlap-add of the round's frames [frA, frB] in frame order, then the samples they finish that fall inside the call
+        const int frA = frW0 + wFirst, frB = frW0 + wLast;
+        const int lo = frA * hop, hi = frB * hop + F;
+        for (int j = lo + ((tid - lo) & (64 * NWV - 1)); j < hi; j += 64 * NWV) {
+            float v = ring[j & RM];
+            for (int w = wFirst; w <= wLast; w++) {
+                const int o = j - (frW0 + w) * hop;
+                if (o >= 0 && o < F) v += slots[w * 2048 + o];
+            }
+            ring[j & RM] = v;
+        }
+        const int emitEnd = min((frB + 1) * hop, er + M);
+        for (int j = cb + ((tid - cb) & (64 * NWV - 1)); j < emitEnd; j += 64 * NWV) { emit(j - er, ring[j & RM]); ring[j & RM] = 0.f; }
+        cb = max(cb, emitEnd);
+        __syncthreads();
+    }
+    // the rest of the call's output: finished in earlier calls or rounds (or before the stream's first sample: zeros)
+    for (int j = cb + ((tid - cb) & (64 * NWV - 1)); j < er + M; j += 64 * NWV) { emit(j - er, ring[j & RM]); ring[j & RM] = 0.f; }
+
+    // LDS -> state.  History: samples [fb hop, R); carry: one-shot samples from the next one to emit (relative er + M) on
+    const int Hn = H + M - nf * hop;
+    for (int i = tid; i < Hn; i += 64 * NWV) recHist[i] = sample(nf * hop + i);
+    const int ern = er + M;
+    for (int q = tid; q < VP_PV_RING; q += 64 * NWV) {
+        const int i = (q - ern) & RM;
+        if (i < F) recCarry[i] = ring[q];
+    }
+    __syncthreads();                                                           // (slot 0 / sum of the last round)
+    for (int i = tid; i < nb; i += 64 * NWV) { recD[i] = pv.phPrev[i]; recD[nb + i] = pv.sum[i]; }
+    if (tid == 0) { recD[VP_PV_RATIO] = ratio; ((long long *)recD)[VP_PV_COUNT] = R; }
+}
+
+// the updates alone (a call with more than VP_PV_MAX_UPDATES of them pending enqueues this first, on the same stream)
+__global__ __launch_bounds__(256) void vp_k_pv_update(VpPvArgs A)
+{
+    const int s = blockIdx.x;
+    unsigned char *rec = A.state + (size_t)s * VP_PV_REC_BYTES;
+    double *recD = (double *)rec;
+    bool rst = false;
+    double ratio = 0.0;
+    for (int i = 0; i < A.nUpd; i++) {
+        if (A.upd[i].stream != s && A.upd[i].stream != -1) continue;
+        if (A.upd[i].ratio > 0.0) ratio = A.upd[i].ratio;
+        if (A.upd[i].reset) rst = true;
+    }
+    if (rst) {
+        float *recCarry = (float *)(rec + VP_PV_CARRY_BYTES);
+        for (int i = threadIdx.x; i < VP_PV_NB; i += 256) { recD[i] = 0.0; recD[VP_PV_NB + i] = 0.0; }
+        for (int i = threadIdx.x; i < 1024; i += 256) recCarry[i] = 0.f;
+        if (threadIdx.x == 0) ((long long *)recD)[VP_PV_COUNT] = 0;
+    }
+    if (threadIdx.x == 0 && ratio > 0.0) recD[VP_PV_RATIO] = ratio;
+}
+
+size_t vp_pv_lds_bytes() { return pv_stream_lds_bytes(); }
+
+hipError_t vp_pv_prepare_device()
+{
+    return hipFuncSetAttribute((const void *)vp_k_pv_stream, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+}
+
+hipError_t vp_pv_launch(const VpPvArgs &a, hipStream_t st)
+{
+    if (a.nBlocks == 0) hipLaunchKernelGGL(vp_k_pv_update, dim3(a.S), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(vp_k_pv_stream, dim3(a.S), dim3(64 * NWV), vp_pv_lds_bytes(), st, a);
+    return hipGetLastError();
+}

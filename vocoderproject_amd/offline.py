@@ -12,6 +12,7 @@ There is no CPU path here either: without a GPU the processor raises.
 
     python -m vocoderproject_amd.offline pitch  take1.wav take2.wav --out-dir tuned/ [--key 12] [--shift +3]
     python -m vocoderproject_amd.offline vocode voice.wav --carrier synth.wav --out-dir out/
+    python -m vocoderproject_amd.offline pvshift a.wav b.wav --shift 7 --out-dir out/     (streaming phase vocoder)
 """
 import argparse
 import os
@@ -166,11 +167,41 @@ def vocode(voices, carriers, fs, order_lpc=40, order_synth=5, **kw):
     return render(voices, carriers, fs, pitch=False, vocoder=True, params=params, **kw)
 
 
+def pv_shift(voices, shift, N=1024, hop=256, device=0, processor=None):
+    """A batch of recordings through the streaming phase vocoder (PhaseVocoderStream: one stream per recording), block by block,
+    its latency taken off the front.  shift: one interval in semitones or one per recording.  Returns float32 [2][len] per
+    recording (the shifted signal on both channels: the layout the pitch flow writes).  `processor` (tests): an object with the
+    PhaseVocoderStream interface (set_semitones, latency, process) to use instead of a new one."""
+    S = len(voices)
+    if S == 0:
+        raise ValueError("no recordings")
+    p = processor
+    if p is None:
+        from . import PhaseVocoderStream
+        p = PhaseVocoderStream(S, int(N), hop=int(hop), device=device)
+    per = list(shift) if isinstance(shift, (list, tuple)) else [shift] * S
+    if len(per) != S:
+        raise ValueError("shift: one value per recording expected")
+    for s, v in enumerate(per):
+        p.set_semitones(float(v), stream=s)
+    lat = int(p.latency)
+    lens = [int(np.asarray(v).shape[-1]) for v in voices]
+    T = -(-(max(lens) + lat) // N) * N
+    x = np.zeros((S, T), np.float32)
+    for s, v in enumerate(voices):
+        v = np.asarray(v, np.float32)
+        if v.ndim != 1:
+            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
+        x[s, :lens[s]] = v
+    y = np.concatenate([p.process(np.ascontiguousarray(x[:, b:b + N])) for b in range(0, T, N)], axis=1)
+    return [np.ascontiguousarray(np.stack([y[s, lat:lat + lens[s]]] * 2)) for s in range(S)]
+
+
 # ---- command line ---------------------------------------------------------------------------------------------------------
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m vocoderproject_amd.offline", description=__doc__.split("\n\n")[0])
-    ap.add_argument("flow", choices=["pitch", "vocode", "both"])
+    ap.add_argument("flow", choices=["pitch", "vocode", "both", "pvshift"])
     ap.add_argument("inputs", nargs="+", help="voice recordings (WAV; channel 0 is used, like the notebook)")
     ap.add_argument("--carrier", action="append", default=None,
                     help="side-chain recording(s) for vocode/both: one for all voices or one per voice")
@@ -180,6 +211,7 @@ def main(argv=None):
     ap.add_argument("--lpc-voice", type=int, default=40)
     ap.add_argument("--lpc-synth", type=int, default=5)
     ap.add_argument("--block", type=int, default=1024)
+    ap.add_argument("--hop", type=int, default=256, help="pvshift: hop of the 1024-point frames (64, 128, 256 or 512)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--fast", action="store_true", help="VP_IIR_FAST + certified cross-correlation YIN")
     a = ap.parse_args(argv)
@@ -189,6 +221,11 @@ def main(argv=None):
     if any(r[0] != fs for r in recs):
         raise SystemExit("all recordings of a batch must share one sample rate (one prepareToPlay)")
     voices = [r[1][0] for r in recs]
+    if a.flow == "pvshift":
+        if a.shift is None:
+            raise SystemExit("pvshift needs --shift")
+        outs = pv_shift(voices, a.shift, N=a.block, hop=a.hop, device=a.device)
+        return _write_outputs(a, fs, outs)
     carriers = None
     if a.flow != "pitch":
         if not a.carrier:
@@ -204,6 +241,10 @@ def main(argv=None):
     params = dict(keyPitch=a.key, lpcVoice=a.lpc_voice, lpcSynth=a.lpc_synth)
     outs = render(voices, carriers, fs, pitch=a.flow != "vocode", vocoder=a.flow != "pitch", params=params, shift=a.shift,
                   N=a.block, device=a.device, iir_mode="fast" if a.fast else "exact", yin_mode="xcorr" if a.fast else "direct")
+    return _write_outputs(a, fs, outs)
+
+
+def _write_outputs(a, fs, outs):
     os.makedirs(a.out_dir, exist_ok=True)
     for f, y in zip(a.inputs, outs):
         out = os.path.join(a.out_dir, os.path.splitext(os.path.basename(f))[0] + f"_{a.flow}.wav")

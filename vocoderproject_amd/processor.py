@@ -130,6 +130,17 @@ def load_library():
     L.vp_stft_set_runs.argtypes = [vp, C.c_int]
     L.vp_stft_set_precision.argtypes = [vp, C.c_int]
     L.vp_stft_get_precision.argtypes = [vp]
+    if hasattr(L, "vp_pv_create"):                     # (the streaming phase vocoder; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_pv_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.vp_pv_destroy.argtypes = [vp]
+        L.vp_pv_get_latency.argtypes = [vp]
+        L.vp_pv_set_semitones.argtypes = [vp, C.c_int, C.c_double]
+        L.vp_pv_get_semitones.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
+        L.vp_pv_reset.argtypes = [vp, C.c_int]
+        L.vp_pv_process_block.argtypes = [vp, fp, fp]
+        L.vp_pv_process_blocks_device.argtypes = [vp, fp, fp, C.c_int, C.c_void_p]
+        L.vp_pv_debug_alloc_count.argtypes = [vp]
+        L.vp_pv_debug_alloc_count.restype = C.c_long
     L.vp_error_string.argtypes = [C.c_int]
     L.vp_error_string.restype = C.c_char_p
     L.vp_last_error.argtypes = [vp]
@@ -471,6 +482,102 @@ class StftRoundTrip:
     def close(self):
         if getattr(self, "h", None):
             self.L.vp_stft_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PhaseVocoderStream:
+    """Streaming phase-vocoder pitch shifter: `n_streams` independent streams, blocks of `block_size` samples, state kept across
+    calls (include/vp_amd.h vp_pv_*).  Output sample t of a stream is sample t - latency of what StftRoundTrip.pitch_shift gives on
+    everything the stream has received, bit for bit; the first `latency` samples are 0."""
+
+    def __init__(self, n_streams, block_size, hop=256, frame_len=1024, device=0):
+        try:
+            import torch  # noqa: F401  (run() and process_device() use torch: load its HIP runtime before the library loads one)
+        except ImportError:
+            pass
+        self.L = load_library()
+        h = C.c_void_p()
+        rc = self.L.vp_pv_create(int(device), int(n_streams), int(block_size), int(frame_len), int(hop), C.byref(h))
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+        self.h, self.S, self.N, self.hop, self.F, self.device = h, int(n_streams), int(block_size), int(hop), int(frame_len), device
+
+    def _chk(self, rc):
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+
+    @property
+    def latency(self):
+        """F - gcd(N, hop) samples."""
+        return self.L.vp_pv_get_latency(self.h)
+
+    def set_semitones(self, v, stream=-1):
+        """Interval in [-12, 12] for one stream or (-1) all; takes effect at the next process call."""
+        self._chk(self.L.vp_pv_set_semitones(self.h, int(stream), float(v)))
+
+    def semitones(self, stream):
+        v = C.c_double()
+        self._chk(self.L.vp_pv_get_semitones(self.h, int(stream), C.byref(v)))
+        return v.value
+
+    def reset(self, stream=-1):
+        """The stream (-1: all) starts again like a fresh one at the next process call; its interval stays."""
+        self._chk(self.L.vp_pv_reset(self.h, int(stream)))
+
+    def process(self, x):
+        """One block from host memory: float32 [S][N] -> [S][N] (synchronous)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        assert x.shape == (self.S, self.N), x.shape
+        y = np.empty_like(x)
+        self._chk(self.L.vp_pv_process_block(self.h, x.ctypes.data, y.ctypes.data))
+        return y
+
+    def process_device(self, d_in, d_out, n_blocks=1, stream=None):
+        """n_blocks blocks on the device: torch float32 [n_blocks][S][N] (or [S][N] for one block), enqueued on `stream`
+        (default: the current torch stream) without synchronising."""
+        import torch
+        shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
+        assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == shape and d_out.is_contiguous()
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        self._chk(self.L.vp_pv_process_blocks_device(self.h, d_in.data_ptr(), d_out.data_ptr(), int(n_blocks), C.c_void_p(stream)))
+
+    def run(self, x, blocks_per_call=8):
+        """Whole signals float [S][T] -> output aligned with the input, [S][T]: the input padded with `latency` zeros (and up to
+        whole blocks), streamed through the device entry point `blocks_per_call` blocks at a time, the first `latency` samples
+        dropped.  Continues from the handle's state (reset() first for a fresh start)."""
+        import torch
+        x = np.asarray(x, dtype=np.float32)
+        assert x.ndim == 2 and x.shape[0] == self.S, x.shape
+        T, Lat, N = x.shape[1], self.latency, self.N
+        nb = -(-(T + Lat) // N)
+        xp = np.zeros((self.S, nb * N), np.float32)
+        xp[:, :T] = x
+        dev = torch.device("cuda", self.device)
+        d_in = torch.from_numpy(np.ascontiguousarray(xp.reshape(self.S, nb, N).transpose(1, 0, 2))).to(dev)
+        d_out = torch.empty_like(d_in)
+        b = 0
+        while b < nb:
+            k = min(int(blocks_per_call), nb - b)
+            self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k)
+            b += k
+        torch.cuda.synchronize(dev)
+        y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, nb * N)
+        return np.ascontiguousarray(y[:, Lat:Lat + T])
+
+    def debug_alloc_count(self):
+        return self.L.vp_pv_debug_alloc_count(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vp_pv_destroy(self.h)
             self.h = None
 
     def __del__(self):
