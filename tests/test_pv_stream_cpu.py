@@ -116,8 +116,8 @@ def test_latency_formula():
     assert P.latency(100, 128) == 1020 and P.latency(1024, 128) == 896 and P.latency(512, 512) == 512
 
 
-@pytest.mark.parametrize("hop", [128, 256])
-@pytest.mark.parametrize("N", [64, 100, 256, 1000, 1024, 4096])
+@pytest.mark.parametrize("hop", [64, 128, 256, 512])
+@pytest.mark.parametrize("N", [17, 64, 100, 256, 1000, 1024, 4096])
 def test_restatement_equals_one_shot_delayed_by_latency(N, hop):
     rng = np.random.default_rng(N + hop)
     T = N * max(6, -(-7000 // N))
@@ -134,8 +134,8 @@ def test_restatement_equals_one_shot_delayed_by_latency(N, hop):
     assert np.array_equal(y, y1)
 
 
-@pytest.mark.parametrize("hop", [128, 256])
-@pytest.mark.parametrize("N", [64, 100, 256, 1000, 1024, 4096])
+@pytest.mark.parametrize("hop", [64, 128, 256, 512])
+@pytest.mark.parametrize("N", [17, 64, 100, 256, 1000, 1024, 4096])
 def test_latency_is_minimal(N, hop):
     """With L every emitted sample is finished when it leaves; with L - 1 some emitted sample is not, within hop / gcd(N, hop)
     blocks (+ the blocks before the first frame)."""
