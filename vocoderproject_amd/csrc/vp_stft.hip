@@ -52,16 +52,45 @@ __host__ __device__ static inline size_t stft_lds_base(int F, int hop, int f32 =
     return (((size_t)NWV * (f32 ? 4096 : 8192) + (size_t)(F - hop) * sizeof(float)) + 15) & ~(size_t)15;
 }
 size_t vp_stft_lds_bytes(int F, int hop, int f32) { return stft_lds_base(F, hop, f32); }
-static size_t stft_pv_lds_bytes(int F)
-{
-    const size_t nb = (size_t)F / 2 + 1;
-    // previous-frame phases [NWV + 1][nb], analysis (magnitude, frequency) [NWV][nb][2], phase increments [NWV][nb], accumulator [nb]
-    return ((NWV + 1) * nb + NWV * nb * 2 + NWV * nb + nb) * sizeof(double);
-}
 
 int vp_stft_supported(int F, int hop)
 {
     return (F == 1024 || F == 2048) && hop > 0 && F % hop == 0 && F / hop >= 2 && F / hop <= 16;
+}
+
+// the rounds of a workgroup's run: it stores the hops of [rFirst, r1) and recomputes [r0, rFirst) in front of them for the carry
+struct StftRun { int rFirst, r0, r1; };
+__device__ __forceinline__ StftRun stft_run(const VpStftArgs &A, int run)
+{
+    const int rFirst = run * A.roundsPerRun;
+    return StftRun{rFirst, max(0, rFirst - (run > 0 ? A.haloRounds : 0)), min(rFirst + A.roundsPerRun, A.nRounds)};
+}
+
+// the samples of the 1024-point frame at x: one float2 per lane and register.  (Whether the run has the frame is the caller's test: with
+// the test in here the single-precision kernel carries sixteen more moves.)
+__device__ __forceinline__ void stft_load_frame(f2 (&xv)[8], const float *x, int aligned, int lane)
+{
+    if (aligned) {
+#pragma unroll
+        for (int r = 0; r < 8; r++) xv[r] = *(const f2 *)(x + 2 * (lane + 64 * r));
+    } else {
+#pragma unroll
+        for (int r = 0; r < 8; r++) xv[r] = f2{x[2 * (lane + 64 * r)], x[2 * (lane + 64 * r) + 1]};
+    }
+}
+
+// magnitude dump of one frame: |X[k]|, k <= N = 128 Q, natural order (lane 0, q = 0: X[N] sits in the mirror slot)
+template <int Q, class T>
+__device__ __forceinline__ void stft_mag_dump(float *m, const RPairsT<T, Q> &X, int lane)
+{
+    constexpr int N = 128 * Q;
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+        const int k = 64 * q + lane;
+        m[k] = (float)sqrt(X.kr[q] * X.kr[q] + X.ki[q] * X.ki[q]);             // (sqrt: the float or the double overload, by T)
+        m[N - k] = (float)sqrt(X.mr[q] * X.mr[q] + X.mi[q] * X.mi[q]);
+    }
+    if (lane == 0) m[N / 2] = (float)sqrt(X.hr * X.hr + X.hi * X.hi);
 }
 
 // Overlap-add of one round, by the whole workgroup (behind the barrier that follows the wavefronts' slot writes): relative hop u of the
@@ -134,13 +163,25 @@ __device__ __forceinline__ void pv_sincos_turns(double t, double &sn, double &cs
     cs = (iq == 0) ? cr : (iq == 1) ? -sr : (iq == 2) ? -cr : sr;
 }
 
-// the wavefront's phase-vocoder work arrays (PV builds only)
+// the workgroup's phase-vocoder work arrays (1024-point frames: VP_PV_NB bins), carved for wavefront wv
 struct PvLds {
-    lds_f64 *phPrev;           // [NWV + 1][nb]  slot w + 1: frame of wavefront w this round; slot 0: the previous round's last frame
     lds_d2 *ana;               // [NWV][nb]      (magnitude, true frequency in bins) of this wavefront's frame
+    lds_f64 *phPrev;           // [NWV + 1][nb]  slot w + 1: frame of wavefront w this round; slot 0: the frame before the round's first live one
     lds_f64 *inc;              // [NWV][nb]      synthesis phase increment of each wavefront's frame
-    lds_f64 *sum;              // [nb]           synthesis phase accumulator after the previous round
+    lds_f64 *sum;              // [nb]           synthesis phase accumulator in front of the round's first live frame
 };
+__host__ __device__ constexpr size_t pv_lds_bytes() { return (size_t)(NWV * 2 + (NWV + 1) + NWV + 1) * VP_PV_NB * sizeof(double); }
+// p: 16-byte aligned (the 16-byte type comes first: nb is odd)
+__device__ __forceinline__ PvLds pv_lds_carve(lds_f64 *p, int wv)
+{
+    constexpr int nb = VP_PV_NB;
+    PvLds pv;
+    pv.ana = (lds_d2 *)p + (size_t)wv * nb; p += NWV * nb * 2;
+    pv.phPrev = p; p += (NWV + 1) * nb;
+    pv.inc = p; p += NWV * nb;
+    pv.sum = p;
+    return pv;
+}
 
 // PV: phase-vocoder stage between the transforms; MAG: magnitude dump (builds of their own: the timed round trip carries neither)
 template <bool PV, bool MAG>
@@ -155,14 +196,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_fused(VpStftArgs A)
     lds_f32 *slots = (lds_f32 *)smem;                                          // ... whose first F floats double as its output slot (slot w at w * 2048)
     lds_f32 *carry = (lds_f32 *)smem + NWV * 2048;                             // [(O - 1) hop]
     PvLds pv;
-    if (PV) {
-        const int nb = N + 1;
-        lds_f64 *p = (lds_f64 *)smem + (stft_lds_base(F, hop) / 8);
-        pv.ana = (lds_d2 *)p + (size_t)wv * nb; p += NWV * nb * 2;           // (the 16-byte type first: the base is 16-byte aligned, nb is odd)
-        pv.phPrev = p; p += (NWV + 1) * nb;
-        pv.inc = p; p += NWV * nb;
-        pv.sum = p;
-    }
+    if (PV) pv = pv_lds_carve((lds_f64 *)smem + stft_lds_base(F, hop) / 8, wv);
 
     // per-lane constants, once per wavefront: window values of the lane's 16 samples, transform constants, split twiddles
     FftLane L;
@@ -177,32 +211,20 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_fused(VpStftArgs A)
 
     for (int i = tid; i < F - hop; i += 64 * NWV) carry[i] = 0.f;
     if (PV) {
-        const int nb = N + 1;
-        for (int i = tid; i < nb; i += 64 * NWV) { pv.phPrev[i] = 0.0; pv.sum[i] = 0.0; }
+        for (int i = tid; i < VP_PV_NB; i += 64 * NWV) { pv.phPrev[i] = 0.0; pv.sum[i] = 0.0; }
     }
     __syncthreads();
 
-    const int rFirst = run * A.roundsPerRun;                                   // first round whose hops this workgroup stores
-    const int r0 = max(0, rFirst - (run > 0 ? A.haloRounds : 0));
-    const int r1 = min(rFirst + A.roundsPerRun, A.nRounds);
+    const StftRun R = stft_run(A, run);
     const float *xs = A.in + (size_t)s * T;
     // the frame's samples are requested a round ahead (see vp_k_stft_fused32)
     f2 xv[8];
     auto request = [&](int rd_) {
         const int f_ = rd_ * NWV + wv;
-        if (rd_ < r1 && f_ < A.nFrames) {
-            const float *x = xs + (size_t)f_ * hop;
-            if (A.aligned) {
-#pragma unroll
-                for (int r = 0; r < 8; r++) xv[r] = *(const f2 *)(x + 2 * (lane + 64 * r));
-            } else {
-#pragma unroll
-                for (int r = 0; r < 8; r++) xv[r] = f2{x[2 * (lane + 64 * r)], x[2 * (lane + 64 * r) + 1]};
-            }
-        }
+        if (rd_ < R.r1 && f_ < A.nFrames) stft_load_frame(xv, xs + (size_t)f_ * hop, A.aligned, lane);
     };
-    request(r0);
-    for (int rd = r0; rd < r1; rd++) {
+    request(R.r0);
+    for (int rd = R.r0; rd < R.r1; rd++) {
         const int f = rd * NWV + wv;
         const bool live = f < A.nFrames;                                       // (wavefront-uniform)
         C8 z;
@@ -215,16 +237,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_fused(VpStftArgs A)
         if (live) {
             fft512_rx(z, xb, L);
             rfft_split(z, xb, lane, (const d2 *)ws, X);
-            if (MAG) {                                                         // |X[k]|, k <= N, natural order
-                float *m = A.mag + ((size_t)s * A.nFrames + f) * (N + 1);
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int k = 64 * q + lane;
-                    m[k] = (float)sqrt(X.kr[q] * X.kr[q] + X.ki[q] * X.ki[q]);
-                    m[N - k] = (float)sqrt(X.mr[q] * X.mr[q] + X.mi[q] * X.mi[q]);      // (lane 0, q = 0: X[N] sits in the mirror slot)
-                }
-                if (lane0) m[N / 2] = (float)sqrt(X.hr * X.hr + X.hi * X.hi);
-            }
+            if (MAG) stft_mag_dump<4>(A.mag + ((size_t)s * A.nFrames + f) * (N + 1), X, lane);
         }
         if (PV) {
             // ---- phase-vocoder stage, phases in TURNS.  Bins of this lane: k = 64 q + lane and N - k (q < 4); lane 0 also holds 0, N and N / 2.
@@ -320,7 +333,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_fused(VpStftArgs A)
             for (int r = 0; r < 8; r++) slot[lane + 64 * r] = f2{0.f, 0.f};
         }
         __syncthreads();
-        stft_overlap_add(A, slots, carry, s, rd, rd >= rFirst, tid);
+        stft_overlap_add(A, slots, carry, s, rd, rd >= R.rFirst, tid);
         __syncthreads();
     }
 }
@@ -355,13 +368,11 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_fused2k(VpStftArgs A)
     for (int i = tid; i < F - hop; i += 64 * NWV) carry[i] = 0.f;
     __syncthreads();
 
-    const int rFirst = run * A.roundsPerRun;
-    const int r0 = max(0, rFirst - (run > 0 ? A.haloRounds : 0));
-    const int r1 = min(rFirst + A.roundsPerRun, A.nRounds);
+    const StftRun R = stft_run(A, run);
     const float *xs = A.in + (size_t)s * T;
     typedef float f4 __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) f4 lds_f4;
-    for (int rd = r0; rd < r1; rd++) {
+    for (int rd = R.r0; rd < R.r1; rd++) {
         const int f = rd * NWV + wv;
         const bool live = f < A.nFrames;
         lds_f4 *slot = (lds_f4 *)(slots + wv * 2048);
@@ -389,16 +400,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_fused2k(VpStftArgs A)
             }
             RPairsN<8> X;
             rfft_split_n<8>(e.re, e.im, hr, hi, xb, lane, (const d2 *)ws, X);
-            if (MAG) {                                                         // |X[k]|, k <= N, natural order
-                float *mg = A.mag + ((size_t)s * A.nFrames + f) * (N + 1);
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const int k = 64 * q + lane;
-                    mg[k] = (float)sqrt(X.kr[q] * X.kr[q] + X.ki[q] * X.ki[q]);
-                    mg[N - k] = (float)sqrt(X.mr[q] * X.mr[q] + X.mi[q] * X.mi[q]);
-                }
-                if (lane == 0) mg[N / 2] = (float)sqrt(X.hr * X.hr + X.hi * X.hi);
-            }
+            if (MAG) stft_mag_dump<8>(A.mag + ((size_t)s * A.nFrames + f) * (N + 1), X, lane);
             rfft_merge_conj_n<8>(e.re, e.im, hr, hi, xb, lane, (const d2 *)ws, X, A.c);
 #pragma unroll
             for (int q = 0; q < 8; q++) {                                      // radix-2 on top, decimation in frequency: e = lo + hi, o = (lo - hi) W^k'
@@ -420,7 +422,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_fused2k(VpStftArgs A)
             for (int r = 0; r < 8; r++) slot[lane + 64 * r] = f4{0.f, 0.f, 0.f, 0.f};
         }
         __syncthreads();
-        stft_overlap_add(A, slots, carry, s, rd, rd >= rFirst, tid);
+        stft_overlap_add(A, slots, carry, s, rd, rd >= R.rFirst, tid);
         __syncthreads();
     }
 }
@@ -461,28 +463,17 @@ __global__ __launch_bounds__(64 * NWV, 4) void vp_k_stft_fused32(VpStftArgs A)
     for (int i = tid; i < F - hop; i += 64 * NWV) carry[i] = 0.f;
     __syncthreads();
 
-    const int rFirst = run * A.roundsPerRun;
-    const int r0 = max(0, rFirst - (run > 0 ? A.haloRounds : 0));
-    const int r1 = min(rFirst + A.roundsPerRun, A.nRounds);
+    const StftRun R = stft_run(A, run);
     const float *xs = A.in + (size_t)s * T;
     // the frame's samples are requested a round ahead (16 registers this build can afford; +3 to +8 % on one box: 570 -> 590 M frames/s at
     // 256 streams x 65 536 samples, 675 -> 730 M at 4096 x 32 768)
     f2 xv[8];
     auto request = [&](int rd_) {
         const int f_ = rd_ * NWV + wv;
-        if (rd_ < r1 && f_ < A.nFrames) {
-            const float *x = xs + (size_t)f_ * hop;
-            if (A.aligned) {
-#pragma unroll
-                for (int r = 0; r < 8; r++) xv[r] = *(const f2 *)(x + 2 * (lane + 64 * r));
-            } else {
-#pragma unroll
-                for (int r = 0; r < 8; r++) xv[r] = f2{x[2 * (lane + 64 * r)], x[2 * (lane + 64 * r) + 1]};
-            }
-        }
+        if (rd_ < R.r1 && f_ < A.nFrames) stft_load_frame(xv, xs + (size_t)f_ * hop, A.aligned, lane);
     };
-    request(r0);
-    for (int rd = r0; rd < r1; rd++) {
+    request(R.r0);
+    for (int rd = R.r0; rd < R.r1; rd++) {
         const int f = rd * NWV + wv;
         const bool live = f < A.nFrames;
         C8f z;
@@ -495,16 +486,7 @@ __global__ __launch_bounds__(64 * NWV, 4) void vp_k_stft_fused32(VpStftArgs A)
             fft512f(z, xb, L, tw1, (const f2 *)tw2);
             RPairsT<float, 4> X;
             rfft_split_n<4>(z.re, z.im, z.re + 4, z.im + 4, xb, lane, (const f2 *)ws, X);
-            if (MAG) {
-                float *m = A.mag + ((size_t)s * A.nFrames + f) * (N + 1);
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int k = 64 * q + lane;
-                    m[k] = sqrtf(X.kr[q] * X.kr[q] + X.ki[q] * X.ki[q]);
-                    m[N - k] = sqrtf(X.mr[q] * X.mr[q] + X.mi[q] * X.mi[q]);
-                }
-                if (lane == 0) m[N / 2] = sqrtf(X.hr * X.hr + X.hi * X.hi);
-            }
+            if (MAG) stft_mag_dump<4>(A.mag + ((size_t)s * A.nFrames + f) * (N + 1), X, lane);
             rfft_merge_conj_n<4>(z.re, z.im, z.re + 4, z.im + 4, xb, lane, (const f2 *)ws, X, c);
             fft512f(z, xb, L, tw1, (const f2 *)tw2);
             wave_sync();
@@ -515,7 +497,7 @@ __global__ __launch_bounds__(64 * NWV, 4) void vp_k_stft_fused32(VpStftArgs A)
             for (int r = 0; r < 8; r++) xb[lane + 64 * r] = f2{0.f, 0.f};
         }
         __syncthreads();
-        stft_overlap_add<1024>(A, slots, carry, s, rd, rd >= rFirst, tid);
+        stft_overlap_add<1024>(A, slots, carry, s, rd, rd >= R.rFirst, tid);
         __syncthreads();
     }
 }
@@ -562,11 +544,9 @@ __global__ __launch_bounds__(64 * NWV, 3) void vp_k_stft_fused2k32(VpStftArgs A)
     for (int i = tid; i < F - hop; i += 64 * NWV) carry[i] = 0.f;
     __syncthreads();
 
-    const int rFirst = run * A.roundsPerRun;
-    const int r0 = max(0, rFirst - (run > 0 ? A.haloRounds : 0));
-    const int r1 = min(rFirst + A.roundsPerRun, A.nRounds);
+    const StftRun R = stft_run(A, run);
     const float *xs = A.in + (size_t)s * T;
-    for (int rd = r0; rd < r1; rd++) {
+    for (int rd = R.r0; rd < R.r1; rd++) {
         const int f = rd * NWV + wv;
         const bool live = f < A.nFrames;
         lds_f4 *slot = (lds_f4 *)(slots + wv * 2048);
@@ -594,16 +574,7 @@ __global__ __launch_bounds__(64 * NWV, 3) void vp_k_stft_fused2k32(VpStftArgs A)
             }
             RPairsT<float, 8> X;
             rfft_split_n<8>(e.re, e.im, hr, hi, xb, lane, (const f2 *)ws, X);
-            if (MAG) {
-                float *mg = A.mag + ((size_t)s * A.nFrames + f) * (N + 1);
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const int k = 64 * q + lane;
-                    mg[k] = sqrtf(X.kr[q] * X.kr[q] + X.ki[q] * X.ki[q]);
-                    mg[N - k] = sqrtf(X.mr[q] * X.mr[q] + X.mi[q] * X.mi[q]);
-                }
-                if (lane == 0) mg[N / 2] = sqrtf(X.hr * X.hr + X.hi * X.hi);
-            }
+            if (MAG) stft_mag_dump<8>(A.mag + ((size_t)s * A.nFrames + f) * (N + 1), X, lane);
             rfft_merge_conj_n<8>(e.re, e.im, hr, hi, xb, lane, (const f2 *)ws, X, c);
 #pragma unroll
             for (int q = 0; q < 8; q++) {
@@ -624,7 +595,7 @@ __global__ __launch_bounds__(64 * NWV, 3) void vp_k_stft_fused2k32(VpStftArgs A)
             for (int r = 0; r < 8; r++) slot[lane + 64 * r] = f4{0.f, 0.f, 0.f, 0.f};
         }
         __syncthreads();
-        stft_overlap_add(A, slots, carry, s, rd, rd >= rFirst, tid);
+        stft_overlap_add(A, slots, carry, s, rd, rd >= R.rFirst, tid);
         __syncthreads();
     }
 }
@@ -654,7 +625,7 @@ hipError_t vp_stft_launch(const VpStftArgs &a, int nStreams, int nRuns, hipStrea
         if (a.mag) hipLaunchKernelGGL((vp_k_stft_fused2k<true>), grid, block, lds2, st, a);
         else hipLaunchKernelGGL((vp_k_stft_fused2k<false>), grid, block, lds2, st, a);
     } else if (a.pv)
-        hipLaunchKernelGGL((vp_k_stft_fused<true, false>), grid, block, lds + stft_pv_lds_bytes(a.F), st, a);
+        hipLaunchKernelGGL((vp_k_stft_fused<true, false>), grid, block, lds + pv_lds_bytes(), st, a);
     else if (a.mag)
         hipLaunchKernelGGL((vp_k_stft_fused<false, true>), grid, block, lds, st, a);
     else
@@ -667,7 +638,8 @@ hipError_t vp_stft_launch(const VpStftArgs &a, int nStreams, int nRuns, hipStrea
 // Frame f of the stream covers samples [f hop, f hop + F) of everything it received since create / reset and is computed in the call in
 // which its last sample arrives; wavefront w takes the frames 4 r + w by their global index, so the rounds of four frames are the
 // one-shot's, cut where the calls cut them.  The stage below is the one-shot's, statement for statement (same operations on the same
-// operands: the outputs agree bit for bit), except for what a round cut by a call needs:
+// operands: the outputs agree bit for bit; ONE force-inlined function for both kernels compiles to another instruction mix and cost the
+// one-shot 2 %: docs/HISTORY.md), except for what a round cut by a call needs:
 //   * the first live frame of the call reads its "previous frame" phases from slot 0 (the state), whatever its wavefront;
 //   * the accumulator of a round sums from the first live frame; a round that the call ends early leaves its partial sum UNWRAPPED (the
 //     next call continues the same left-to-right sum) and only a round's frame 4 r + 3 wraps it;
@@ -678,9 +650,19 @@ hipError_t vp_stft_launch(const VpStftArgs &a, int nStreams, int nRuns, hipStrea
 // History (samples of frames not yet complete, < F), carry (< F unfinished or unemitted samples), phases, accumulator, ratio and the
 // sample counter are read into LDS at entry and written back at exit.
 // LDS: exchange buffers / output slots, ring, history, then the one-shot's phase-vocoder arrays (124 KB: one workgroup per CU)
-__host__ __device__ constexpr size_t pv_stream_lds_bytes()
+__host__ __device__ constexpr size_t pv_stream_lds_bytes() { return (size_t)NWV * 8192 + (VP_PV_RING + 1024) * sizeof(float) + pv_lds_bytes(); }
+
+// the call's interval changes and resets that concern stream s, in the order they were made (arguments: scalar, uniform): the last new
+// ratio replaces `ratio`; returns whether the stream was reset
+__device__ __forceinline__ bool pv_scan_updates(const VpPvArgs &A, int s, double &ratio)
 {
-    return (size_t)NWV * 8192 + (VP_PV_RING + 1024) * sizeof(float) + ((NWV + 1) * VP_PV_NB + NWV * VP_PV_NB * 2 + NWV * VP_PV_NB + VP_PV_NB) * sizeof(double);
+    bool rst = false;
+    for (int i = 0; i < A.nUpd; i++) {
+        if (A.upd[i].stream != s && A.upd[i].stream != -1) continue;
+        if (A.upd[i].ratio > 0.0) ratio = A.upd[i].ratio;
+        if (A.upd[i].reset) rst = true;
+    }
+    return rst;
 }
 
 __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream(VpPvArgs A)
@@ -694,14 +676,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream(VpPvArgs A)
     lds_f32 *slots = (lds_f32 *)smem;                                          // wavefront w's output frame at w * 2048
     lds_f32 *ring = (lds_f32 *)smem + NWV * 2048;                              // [VP_PV_RING]
     lds_f32 *hist = ring + VP_PV_RING;                                         // [F]
-    PvLds pv;
-    {
-        lds_f64 *p = (lds_f64 *)(hist + F);
-        pv.ana = (lds_d2 *)p + (size_t)wv * nb; p += NWV * nb * 2;
-        pv.phPrev = p; p += (NWV + 1) * nb;
-        pv.inc = p; p += NWV * nb;
-        pv.sum = p;
-    }
+    const PvLds pv = pv_lds_carve((lds_f64 *)(hist + F), wv);
 #ifdef VP_POISON_LDS
     for (int i = tid; i < (int)(pv_stream_lds_bytes() / 8); i += 64 * NWV) ((lds_f64 *)smem)[i] = __builtin_nan("0x5a5a");
     __syncthreads();
@@ -710,15 +685,9 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream(VpPvArgs A)
     double *recD = (double *)rec;
     float *recHist = (float *)(rec + VP_PV_HIST_BYTES), *recCarry = (float *)(rec + VP_PV_CARRY_BYTES);
 
-    // the call's interval changes and resets, in the order they were made (arguments: scalar, uniform)
     double ratio = recD[VP_PV_RATIO];
     long long n = ((const long long *)recD)[VP_PV_COUNT];                     // samples received before this call
-    bool rst = false;
-    for (int i = 0; i < A.nUpd; i++) {
-        if (A.upd[i].stream != s && A.upd[i].stream != -1) continue;
-        if (A.upd[i].ratio > 0.0) ratio = A.upd[i].ratio;
-        if (A.upd[i].reset) rst = true;
-    }
+    const bool rst = pv_scan_updates(A, s, ratio);
     if (rst) n = 0;
 
     const int M = A.nBlocks * NB;                                              // samples this call
@@ -912,13 +881,8 @@ __global__ __launch_bounds__(256) void vp_k_pv_update(VpPvArgs A)
     const int s = blockIdx.x;
     unsigned char *rec = A.state + (size_t)s * VP_PV_REC_BYTES;
     double *recD = (double *)rec;
-    bool rst = false;
     double ratio = 0.0;
-    for (int i = 0; i < A.nUpd; i++) {
-        if (A.upd[i].stream != s && A.upd[i].stream != -1) continue;
-        if (A.upd[i].ratio > 0.0) ratio = A.upd[i].ratio;
-        if (A.upd[i].reset) rst = true;
-    }
+    const bool rst = pv_scan_updates(A, s, ratio);
     if (rst) {
         float *recCarry = (float *)(rec + VP_PV_CARRY_BYTES);
         for (int i = threadIdx.x; i < VP_PV_NB; i += 256) { recD[i] = 0.0; recD[VP_PV_NB + i] = 0.0; }
