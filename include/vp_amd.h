@@ -168,6 +168,30 @@ int vp_process_blocks_device(vp_handle *h, const float *d_in, float *d_out, int 
  * download, in groups of as many blocks as vp_reserve_blocks sized the staging buffers for (none reserved: block by block through
  * the single-block staging buffers of prepare); synchronises before returning. */
 int vp_process_blocks(vp_handle *h, const float *in, float *out, int n_blocks);
+/* Channel-pointer forms: processBlock() on what AudioBuffer<float> holds, one pointer per channel (getReadPointer / getWritePointer,
+ * MyBuffer.cpp:74-105), the channels of a stream neither contiguous nor all present.
+ *   in:  n_streams * n_in  pointers; row (s, ch) = in[s * n_in + ch], N floats each.   n_in  = 1 (voice only) or 3.
+ *   out: n_streams * n_out pointers; row (s, ch) = out[s * n_out + ch], N floats each. n_out = 2 (L, R) or 3.
+ *  - A null input pointer reads as silence (MyBuffer.cpp:93-102, here for every channel and per stream); a null output pointer means
+ *    that channel is not wanted.  With n_out = 3, channel 2 (where not null) receives zeros (MyBuffer.cpp:115 buffer.clear()).
+ *  - Output rows may alias input rows (JUCE's in-place buffer): every input row is consumed before any output row is written.  Output
+ *    rows must not overlap each other (not checked).  Rows need float alignment only.
+ *  - Host form (vp_process_block_channels): table and rows in host memory, synchronous like vp_process_block.  n_in = 1, or n_in = 3 with
+ *    every side-chain pointer null, takes the mono path (vp_process_block_mono).
+ *  - Device forms: the tables are DEVICE arrays of device pointers (the convention of batched BLAS), the rows device memory; the work is
+ *    enqueued on hip_stream without synchronising, like vp_process_block_device.  Build the tables once and reuse them.  n_in = 1 takes
+ *    the mono path; null side-chain entries in an n_in = 3 table are zero-filled on the three-channel path (same results).
+ *  - vp_process_blocks_channels_device: every row holds n_blocks * N contiguous samples -- a stream's recording as it lies in memory.
+ *    The result is what vp_process_blocks_device gives on the equivalent [n_blocks][n_streams][3][N] slab, its grouping of the blocks
+ *    under vp_reserve_blocks included.  A call within the reservation costs one pack and one unpack kernel around that plan; a larger
+ *    one is carried out in groups of the reserved size (whole multiples of 16 blocks above 16; the consumed-before-written rule then
+ *    holds per group), and without a reservation block by block through the single-block staging.
+ * The results are bit-identical to the packed entry points on the packed data: the same plans run on the same values.  No allocation in
+ * any of the three (the packed staging is sized in prepare and in vp_reserve_blocks).  VP_ERR_INVALID_ARG (null handle or table, n_in
+ * not 1 or 3, n_out not 2 or 3, n_blocks < 1) and VP_ERR_NOT_PREPARED are reported before the device is touched. */
+int vp_process_block_channels(vp_handle *h, const float *const *in, int n_in, float *const *out, int n_out);
+int vp_process_block_channels_device(vp_handle *h, const float *const *d_in, int n_in, float *const *d_out, int n_out, void *hip_stream);
+int vp_process_blocks_channels_device(vp_handle *h, const float *const *d_in, int n_in, float *const *d_out, int n_out, int n_blocks, void *hip_stream);
 /* Allocation for the multi-block entry points, outside the process calls: scratch of the lane-per-window pipeline for the windows of
  * min(n_blocks, 16) blocks, the combined plan's ring snapshots / per-block gates / linear accumulator, and host staging for
  * n_blocks blocks.  After prepare (a new prepare drops the reservation); grows only; synchronises the device.  VP_ERR_OOM.

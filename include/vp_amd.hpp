@@ -115,6 +115,21 @@ public:
     // processBlock(AudioBuffer<float>&, MidiBuffer&) (:203): io [streams][3][N] in place, host memory
     void processBlock(float *io) { check(vp_process_block_inplace(h_, io), "processBlock"); }
     void processBlock(const float *in, float *out) { check(vp_process_block(h_, in, out), "processBlock"); }
+    // what AudioBuffer<float> holds: one pointer per channel (getReadPointer / getWritePointer), row (s, ch) = in[s * nIn + ch];
+    // nIn 1 or 3, nOut 2 or 3; a null input is silence (MyBuffer.cpp:93-102), a null output is not written, out may alias in
+    void processBlock(const float *const *in, int nIn, float *const *out, int nOut)
+    {
+        check(vp_process_block_channels(h_, in, nIn, out, nOut), "processBlock");
+    }
+    // the same with DEVICE tables of device rows, asynchronous on `hipStream`; rows of nBlocks * N samples in the second form
+    void processBlockChannelsDevice(const float *const *dIn, int nIn, float *const *dOut, int nOut, void *hipStream = nullptr)
+    {
+        check(vp_process_block_channels_device(h_, dIn, nIn, dOut, nOut, hipStream), "processBlockChannelsDevice");
+    }
+    void processBlocksChannelsDevice(const float *const *dIn, int nIn, float *const *dOut, int nOut, int nBlocks, void *hipStream = nullptr)
+    {
+        check(vp_process_blocks_channels_device(h_, dIn, nIn, dOut, nOut, nBlocks, hipStream), "processBlocksChannelsDevice");
+    }
     // device-resident, asynchronous on `hipStream`
     void processBlockDevice(const float *dIn, float *dOut, void *hipStream = nullptr)
     {
@@ -228,6 +243,11 @@ public:
     void processBlockMono(const float *voice, float *out)                         // voice [streams][N] -> out [streams][2][N]
     {
         run([&](int g, Shard &sh) { const int lo = shardRange(g).first; sh.proc.processBlockMono(voice + (size_t)lo * N_, out + (size_t)lo * 2 * N_); });
+    }
+    // channel pointers for the whole batch, host memory: a shard's tables are the caller's, offset to its first stream (no copy)
+    void processBlock(const float *const *in, int nIn, float *const *out, int nOut)
+    {
+        run([&](int g, Shard &sh) { const int lo = shardRange(g).first; sh.proc.processBlock(in + (size_t)lo * nIn, nIn, out + (size_t)lo * nOut, nOut); });
     }
     int getLatencySamples() const { return shards_[0]->proc.getLatencySamples(); }
 

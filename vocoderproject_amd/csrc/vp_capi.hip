@@ -22,6 +22,7 @@
 #include "vp_kernels.h"
 #include "vp_voc2.h"
 #include "vp_stft.h"
+#include "vp_channels.h"
 
 struct vp_handle {
     int device = 0;
@@ -76,6 +77,10 @@ struct vp_handle {
     int synthNonZero = 0;                       // samples of the synth rings not known to be zero (mono entry points)
     float *stageInB = nullptr, *stageOutB = nullptr; int stageBlocks = 0;   // vp_process_blocks: [B][S][3|2][N], sized by vp_reserve_blocks
     int reservedBlocks = 0;                     // vp_reserve_blocks: blocks per call the multi-block scratch is sized for
+    // vp_process_block_channels (host rows): pinned packing buffers [S][3][N] / [S][2][N], sized in prepare.  The device channel forms
+    // pack into stageIn / stageOut (stageInB / stageOutB for several blocks) on the caller's stream: like the handle's device state,
+    // they belong to whichever call is in flight (one caller thread per handle, calls ordered by the caller)
+    float *chHostIn = nullptr, *chHostOut = nullptr;
     long nAllocs = 0;                           // device allocations made for this handle since vp_create (vp_debug_alloc_count)
     hipStream_t ownStream = nullptr;
     int vocWaves = 8;
@@ -388,6 +393,9 @@ static void free_all(vp_handle *h)
     if (h->stageInB) (void)hipFree(h->stageInB);
     if (h->stageOutB) (void)hipFree(h->stageOutB);
     h->stageInB = h->stageOutB = nullptr; h->stageBlocks = 0; h->reservedBlocks = 0;
+    if (h->chHostIn) (void)hipHostFree(h->chHostIn);
+    if (h->chHostOut) (void)hipHostFree(h->chHostOut);
+    h->chHostIn = h->chHostOut = nullptr;
     h->prepared = false;
 }
 
@@ -767,6 +775,14 @@ extern "C" int vp_prepare_explicit(vp_handle *h, double fs, int N, int S, int F,
     }
     RC(dev_alloc(h, &h->stageIn, (size_t)S * 3 * N, false));
     RC(dev_alloc(h, &h->stageOut, (size_t)S * 3 * N, false));
+    // packing buffers of the host channel form (vp_process_block_channels): pinned, so that no process call allocates or pins
+    if (hipHostMalloc((void **)&h->chHostIn, (size_t)S * 3 * N * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void **)&h->chHostOut, (size_t)S * 2 * N * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        free_all(h);
+        h->lastError = "out of pinned host memory for the channel staging buffers";
+        return VP_ERR_OOM;
+    }
     {   // PitchProcess::prepare initial members (:76-85): everything 0 except beta = 1
         std::vector<VpPitchState> init(S);
         memset(init.data(), 0, init.size() * sizeof(VpPitchState));
@@ -1593,6 +1609,92 @@ extern "C" int vp_process_block_inplace(vp_handle *h, float *io)
     HIPCHK(h, hipMemcpyAsync(io, h->stageOut, n * sizeof(float), hipMemcpyDeviceToHost, h->ownStream));
     HIPCHK(h, hipStreamSynchronize(h->ownStream));
     return check_fault(h);                                                    // (behind the synchronisation: this call's own launches included)
+}
+
+
+// ---- channel-pointer entry points: what AudioBuffer<float> hands processBlock() (PluginProcessor.cpp:203) is one pointer per channel,
+// not a slab; MyBuffer::fillInputBuffers reads them one by one and takes null side-chain pointers as silence (MyBuffer.cpp:74-105).
+// A channel call packs the rows (vp_k_gather_channels, or memcpy for host rows), runs the plan of the packed entry point on the slab
+// -- process_device / process_blocks_device, unchanged, with their checks -- and unpacks (vp_k_scatter_channels).
+static int channels_args(const vp_handle *h, const void *in, int n_in, const void *out, int n_out, int n_blocks)
+{
+    if (!h || !in || !out || (n_in != 1 && n_in != 3) || (n_out != 2 && n_out != 3) || n_blocks < 1) return VP_ERR_INVALID_ARG;
+    if (!h->prepared) return VP_ERR_NOT_PREPARED;
+    return VP_OK;
+}
+
+extern "C" int vp_process_block_channels(vp_handle *h, const float *const *in, int n_in, float *const *out, int n_out)
+{
+    if (int rc = channels_args(h, in, n_in, out, n_out, 1)) return rc;
+    if (hipSetDevice(h->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    const int S = h->g.S, N = h->g.N;
+    // no side chain on any stream (host pointers: visible here): the mono path, a third of the upload (MyBuffer.cpp:93-102)
+    bool mono = true;
+    for (int s = 0; s < S && mono && n_in == 3; s++) mono = !in[s * 3 + 1] && !in[s * 3 + 2];
+    const int nc = mono ? 1 : 3;
+    for (int s = 0; s < S; s++)                                               // every input row is consumed before any output row is written
+        for (int ch = 0; ch < nc; ch++) {
+            float *dst = h->chHostIn + ((size_t)s * nc + ch) * N;
+            const float *src = in[s * n_in + ch];
+            if (src) memcpy(dst, src, (size_t)N * sizeof(float)); else memset(dst, 0, (size_t)N * sizeof(float));
+        }
+    const size_t nIn = (size_t)S * nc * N, nOut = (size_t)S * 2 * N;
+    HIPCHK(h, hipMemcpyAsync(h->stageIn, h->chHostIn, nIn * sizeof(float), hipMemcpyHostToDevice, h->ownStream));
+    int rc = process_device(h, h->stageIn, h->stageOut, h->ownStream, 0, 1, mono);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->chHostOut, h->stageOut, nOut * sizeof(float), hipMemcpyDeviceToHost, h->ownStream));
+    HIPCHK(h, hipStreamSynchronize(h->ownStream));
+    if ((rc = check_fault(h)) != VP_OK) return rc;                            // (behind the synchronisation: this call's own launches included)
+    for (int s = 0; s < S; s++)
+        for (int ch = 0; ch < n_out; ch++) {
+            float *dst = out[s * n_out + ch];
+            if (!dst) continue;                                               // channel not wanted
+            if (ch < 2) memcpy(dst, h->chHostOut + ((size_t)s * 2 + ch) * N, (size_t)N * sizeof(float));
+            else memset(dst, 0, (size_t)N * sizeof(float));                   // MyBuffer.cpp:115 buffer.clear()
+        }
+    return VP_OK;
+}
+
+// the device forms: blocks [b0, b0 + nb) of every row through `sIn` / `sOut`, one gather and one scatter around the packed call
+static int channels_group(vp_handle *h, const float *const *d_in, int n_in, float *const *d_out, int n_out, int b0, int nb, float *sIn, float *sOut,
+                          bool blocksForm, hipStream_t st)
+{
+    const int S = h->g.S, N = h->g.N;
+    const bool mono = n_in == 1;
+    hipError_t e = vp_channels_gather(d_in, sIn, n_in, S, N, nb, (size_t)b0 * N, st);
+    if (e != hipSuccess) return fail_hip(h, e, "vp_k_gather_channels launch");
+    const int rc = blocksForm ? process_blocks_device(h, sIn, sOut, nb, (void *)st, mono) : process_device(h, sIn, sOut, st, 0, 1, mono);
+    if (rc) return rc;
+    e = vp_channels_scatter(sOut, d_out, n_out, S, N, nb, (size_t)b0 * N, st);
+    if (e != hipSuccess) { h->poisoned = true; return fail_hip(h, e, "vp_k_scatter_channels launch"); }   // (the block ran, its output is lost)
+    return VP_OK;
+}
+
+extern "C" int vp_process_block_channels_device(vp_handle *h, const float *const *d_in, int n_in, float *const *d_out, int n_out, void *hip_stream)
+{
+    if (int rc = channels_args(h, d_in, n_in, d_out, n_out, 1)) return rc;
+    if (hipSetDevice(h->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return channels_group(h, d_in, n_in, d_out, n_out, 0, 1, h->stageIn, h->stageOut, false, (hipStream_t)hip_stream);
+}
+
+extern "C" int vp_process_blocks_channels_device(vp_handle *h, const float *const *d_in, int n_in, float *const *d_out, int n_out, int n_blocks,
+                                                 void *hip_stream)
+{
+    if (int rc = channels_args(h, d_in, n_in, d_out, n_out, n_blocks)) return rc;
+    if (hipSetDevice(h->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    // groups of as many blocks as the staging of vp_reserve_blocks holds -- one group, i.e. one gather and one scatter, for a call within
+    // the reservation --, cut where vp_process_blocks_device cuts its own groups (whole multiples of V2_MB_MAX), so that the plans see
+    // the groups they would see on the slab; nothing reserved: block by block through the single-block staging, a sample offset into
+    // the rows.  No allocation here.
+    int group = std::min(h->stageBlocks, 65535);                              // (a grid's y extent)
+    if (group > V2_MB_MAX) group -= group % V2_MB_MAX;
+    float *sIn = group ? h->stageInB : h->stageIn, *sOut = group ? h->stageOutB : h->stageOut;
+    group = std::max(group, 1);
+    for (int b = 0; b < n_blocks; b += group) {
+        const int rc = channels_group(h, d_in, n_in, d_out, n_out, b, std::min(n_blocks - b, group), sIn, sOut, true, (hipStream_t)hip_stream);
+        if (rc) return rc;
+    }
+    return VP_OK;
 }
 
 extern "C" int vp_get_latency(const vp_handle *h) { return (h && h->prepared) ? h->g.latency : VP_ERR_NOT_PREPARED; }

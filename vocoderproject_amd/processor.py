@@ -86,6 +86,10 @@ def load_library():
         L.vp_process_block_mono.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vp_process_block_mono_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vp_process_blocks_mono_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "vp_process_block_channels"):        # (absent only from older libraries loaded through VP_AMD_LIB)
+        L.vp_process_block_channels.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.vp_process_block_channels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.vp_process_blocks_channels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "vp_process_blocks"):
         L.vp_process_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     if hasattr(L, "vp_set_pitch_shift"):
@@ -359,6 +363,57 @@ class BatchVocoderProcessor:
         self.reserve_blocks(x.shape[0])
         self._chk(self.L.vp_process_blocks(self.h, x.ctypes.data, out.ctypes.data, int(x.shape[0])))
         return out
+
+    # ---- channel pointers (what AudioBuffer<float> holds: one row per channel, not a slab) -------------------
+    def process_channels(self, ins, outs):
+        """vp_process_block_channels: `ins` a sequence of S * n_in rows (n_in 1 or 3; row (s, ch) = ins[s * n_in + ch]), `outs` of
+        S * n_out rows (n_out 2 or 3): float32 numpy arrays of N samples each, or None -- silence on the input side (MyBuffer.cpp:93-102),
+        "not wanted" on the output side.  Output rows are written in place and may be the input rows; row 2 of a stream receives zeros."""
+        S, N = self.n_streams, self.N
+        n_in, n_out = len(ins) // max(S, 1), len(outs) // max(S, 1)
+        assert len(ins) == S * n_in and len(outs) == S * n_out, (len(ins), len(outs), S)
+
+        def table(rows, writable):
+            t = (C.c_void_p * len(rows))()
+            for i, r in enumerate(rows):
+                if r is None:
+                    continue
+                assert isinstance(r, np.ndarray) and r.dtype == np.float32 and r.ndim == 1 and r.shape[0] == N and r.strides[0] == 4, i
+                assert not writable or r.flags.writeable, i
+                t[i] = r.ctypes.data
+            return t
+        self._chk(self.L.vp_process_block_channels(self.h, table(ins, False), n_in, table(outs, True), n_out))
+
+    @staticmethod
+    def channel_table(rows):
+        """A device table for process_channels_device: `rows` a sequence of 1-D float32 CUDA tensors (each a row of samples, any
+        alignment a float has) or None -> int64 CUDA tensor of their data_ptr()s (0 for None).  The table keeps the rows alive
+        (`table.rows`); build it once and reuse it."""
+        import torch
+        dev = next((r.device for r in rows if r is not None), torch.device("cuda"))
+        for r in rows:
+            assert r is None or (r.is_cuda and r.dtype == torch.float32 and r.dim() == 1 and r.stride(0) == 1 and r.device == dev)
+        t = torch.tensor([0 if r is None else r.data_ptr() for r in rows], dtype=torch.int64).to(dev)
+        t.rows = list(rows)
+        t.min_len = min((r.numel() for r in rows if r is not None), default=1 << 62)    # (checked against n_blocks * N per call: one comparison, not a loop)
+        return t
+
+    def process_channels_device(self, in_table, n_in, out_table, n_out, n_blocks=1, stream=None):
+        """vp_process_block_channels_device (n_blocks = 1) / vp_process_blocks_channels_device (rows of n_blocks * N samples): device
+        tables from channel_table(), S * n_in and S * n_out entries; enqueued on `stream` (default: the current torch stream) without
+        synchronising.  Bit-identical to process_device / process_blocks_device on the packed data."""
+        import torch
+        for t, n in ((in_table, n_in), (out_table, n_out)):
+            assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == self.n_streams * n, (t.shape, n)
+        for t in (in_table, out_table):
+            assert getattr(t, "min_len", int(n_blocks) * self.N) >= int(n_blocks) * self.N, "a row is shorter than n_blocks * N samples"
+        if stream is None:
+            stream = torch.cuda.current_stream(in_table.device).cuda_stream
+        if int(n_blocks) == 1:
+            self._chk(self.L.vp_process_block_channels_device(self.h, in_table.data_ptr(), int(n_in), out_table.data_ptr(), int(n_out), C.c_void_p(stream)))
+        else:
+            self._chk(self.L.vp_process_blocks_channels_device(self.h, in_table.data_ptr(), int(n_in), out_table.data_ptr(), int(n_out), int(n_blocks),
+                                                               C.c_void_p(stream)))
 
     def run(self, x):
         """x: float32 numpy [S][3][T], T a multiple of N -> float32 [S][2][T] (block by block)."""
