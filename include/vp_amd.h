@@ -325,7 +325,8 @@ int vp_debug_read_stream_ticks(vp_handle *h, unsigned long long *out, int n, int
  * per lane of a wavefront; VP_ERR_GEOMETRY otherwise), hop a divisor of it with 2 <= frame_len / hop <= 16.  NO reference counterpart (the
  * reference contains no FFT): these are the STFT-shaped kernels BASELINE.json's north_star lists, reported
  * on their own by bench.py and checked against numpy.fft / a build-authored NumPy restatement (tests/stft_reference.py: parity
- * unpinned by nature).
+ * unpinned by nature).  vp_stft_roundtrip is the plain round trip (double or single precision), vp_stft_pitch_shift the same with the
+ * phase-vocoder pitch shift between the transforms; both serve both frame lengths.
  * d_in/d_out: device float32 [n_streams][n_samples]; d_mag (optional): [n_streams][frames][frame_len/2+1]. */
 typedef struct vp_stft vp_stft;
 int vp_stft_create(int device, int n_streams, int n_samples, int frame_len, int hop, vp_stft **out);
@@ -335,8 +336,12 @@ int vp_stft_roundtrip(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
 /* The north_star's "per-bin phase unwrap/accumulate" stage between the two transforms: the classic phase-vocoder pitch shift by
  * `semitones` in [-12, 12] (per frame and bin: magnitude and phase; phase advance against the previous frame minus the bin's
  * nominal advance, wrapped to (-pi, pi] -> true frequency; bins move to floor(k ratio + 0.5), magnitudes that land together
- * add; the synthesis phase accumulates the scaled advance).  Each call starts from a zero phase state.  1024-point frames only
- * (VP_ERR_GEOMETRY otherwise).  No reference counterpart; checked against tests/stft_reference.py. */
+ * add; the synthesis phase accumulates the scaled advance).  Each call starts from a zero phase state.  1024- and 2048-point
+ * frames, at every hop vp_stft_create admits (kernels vp_k_stft_fused<true, false> and vp_k_stft_pv2k).  The definition that holds for
+ * both is tests/stft_reference.py's stft_roundtrip(x, frame_len, hop, ratio = 2^(semitones / 12)): sqrt-Hann window, 1 / sum w^2
+ * normalisation, the synthesis phase summed left to right within rounds of four frames and wrapped at a round's last frame, bins 0 and
+ * frame_len / 2 real, samples no frame covers 0.  Double precision whatever vp_stft_set_precision says.  VP_ERR_INVALID_ARG for null
+ * pointers or |semitones| > 12, VP_ERR_HIP when the device refused the kernels' LDS size at create.  No reference counterpart. */
 int vp_stft_pitch_shift(vp_stft *p, const float *d_in, float *d_out, double semitones, void *hip_stream);
 int vp_stft_is_fused(const vp_stft *p);                      /* 1 (every handle runs the fused kernel; kept for older callers) */
 /* Diagnostic: cut every stream into this many runs of frames (one workgroup each) instead of choosing from the batch size

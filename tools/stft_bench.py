@@ -34,6 +34,8 @@ if __name__ == "__main__":
     run(256, 65536, hop=128)
     run(256, 65536, F=2048, hop=512)          # BASELINE configs[4]'s "2048-pt FFT hop 512"
     run(1024, 65536, F=2048, hop=512)
+    run(256, 65536, F=2048, hop=512, semitones=7.0)          # ... with the phase-vocoder stage (vp_k_stft_pv2k)
+    run(1024, 65536, F=2048, hop=512, semitones=7.0)
     # single precision (vp_stft_set_precision: vp_k_stft_fused32)
     for S, T in ((256, 16384), (256, 65536), (1024, 65536), (4096, 32768), (64, 262144)):
         run(S, T, precision="f32")

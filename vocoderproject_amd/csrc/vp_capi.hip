@@ -1843,12 +1843,12 @@ extern "C" int vp_set_yin_mode(vp_handle *h, int mode)
 extern "C" int vp_get_yin_mode(const vp_handle *h) { return h ? h->yinMode : VP_ERR_INVALID_ARG; }
 
 // ---- standalone STFT round trip (no reference counterpart): the fused kernel of vp_stft.hip -------------------------------------
-// (one frame per wavefront, register FFT, overlap-add in LDS; 1024-point frames, optionally with the phase-vocoder stage, and 2048-point frames)
+// (one frame per wavefront, register FFT, overlap-add in LDS; 1024- and 2048-point frames, each optionally with the phase-vocoder stage)
 struct vp_stft {
     int device, F, hop, S, T, nFrames;
     double *win = nullptr, *tw1 = nullptr, *tw2 = nullptr, *tws = nullptr, *twTop = nullptr;
     float scale;
-    bool pvOk = false;                // the phase-vocoder build's dynamic-LDS ceiling could be raised on this device (vp_stft_pitch_shift needs it)
+    bool pvOk = false;                // the phase-vocoder builds' dynamic-LDS ceiling could be raised on this device (vp_stft_pitch_shift needs it)
     int runsPerStream = 0;            // 0: chosen from the batch so that the grid fills the chip; > 0: vp_stft_set_runs (tests)
     int f32 = 0;                      // vp_stft_set_precision
 };
@@ -1981,11 +1981,10 @@ extern "C" int vp_stft_roundtrip(vp_stft *p, const float *d_in, float *d_out, fl
     return stft_fused(p, d_in, d_out, d_mag, (hipStream_t)hip_stream, false, 1.0);
 }
 
-// the same round trip with the phase-vocoder pitch shift between the transforms (fused kernel only)
+// the same round trip with the phase-vocoder pitch shift between the transforms (1024- and 2048-point frames: vp_stft_launch picks the build)
 extern "C" int vp_stft_pitch_shift(vp_stft *p, const float *d_in, float *d_out, double semitones, void *hip_stream)
 {
     if (!p || !d_in || !d_out || !(semitones >= -12.0 && semitones <= 12.0)) return VP_ERR_INVALID_ARG;
-    if (p->F != 1024) return VP_ERR_GEOMETRY;                  // the phase-vocoder stage is built for 1024-point frames
     if (!p->pvOk) return VP_ERR_HIP;                           // (its dynamic-LDS ceiling could not be raised on this device: vp_stft_create)
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, std::pow(2.0, semitones / 12.0));

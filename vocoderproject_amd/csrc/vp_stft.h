@@ -26,6 +26,8 @@ struct VpStftArgs {
 };
 
 size_t vp_stft_lds_bytes(int F, int hop, int f32 = 0);
+// dynamic LDS of the 2048-point phase-vocoder build (vp_k_stft_pv2k) at this hop: slots, carry and the stage's arrays
+size_t vp_stft_pv2k_lds_bytes(int hop);
 // enqueues the fused kernel (grid = runs x streams); returns hipGetLastError()
 hipError_t vp_stft_launch(const VpStftArgs &a, int nStreams, int nRuns, hipStream_t st);
 int vp_stft_supported(int F, int hop);

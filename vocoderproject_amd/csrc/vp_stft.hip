@@ -427,6 +427,203 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_fused2k(VpStftArgs A)
     }
 }
 
+// ---- 2048-point frames WITH the phase-vocoder stage ------------------------------------------------------------------------------------
+// vp_k_stft_fused2k's transforms, split and merge around vp_k_stft_fused<true, false>'s stage: the same definition (tests/stft_reference.py
+// with F = 2048), the same operations in the same order per bin, seventeen bins per lane (k = 64 q + lane and 1024 - k, q < 8; lane 0 also
+// bin 512).  The 1024 build's layout scaled to 1025 bins needs 197 KB of LDS at hop 128 and more than 512 registers; what differs here:
+//   * no `inc` array.  The lane <-> bin map is the same in every wavefront, so the round's left-to-right sum sum + inc_0 + inc_1 + ... is
+//     handed from wavefront to wavefront IN PLACE through `sum`: wavefront w adds its increment in its turn (a barrier between turns), keeps
+//     the partial sum as its own synthesis phase, and the round's last live wavefront leaves the sum wrapped.  The additions and their
+//     order are the 1024 build's.
+//   * no LDS copies of the 512-point transform's twiddle tables: they, the top step's and the split's twiddles and the window come from
+//     the global tables where they are used (L1 / L2-resident: 16 + 8 + 8 + 16 KB; the loads do not depend on the data and are issued
+//     ahead of it).  Resident in registers the transform's twiddles are 64 more of them.
+//   * nothing of the stage is carried in registers across a barrier except the gathered magnitude and increment: magnitudes and phases go
+//     to the LDS arrays that hold them anyway (ana.x, phPrev) as they are computed, the bin pairs X are dead from there to the synthesis.
+// LDS at hop 128: slots 32 768 + carry 7 680 + ana 65 600 + phPrev 41 000 + sum 8 200 = 155 248 B of the 163 328 B ceiling: one workgroup
+// per CU, one wavefront per SIMD, hence up to 512 registers per lane.
+#define VP_PV2K_NB 1025
+__host__ __device__ constexpr size_t pv2k_lds_bytes() { return (size_t)(NWV * 2 + (NWV + 1) + 1) * VP_PV2K_NB * sizeof(double); }
+size_t vp_stft_pv2k_lds_bytes(int hop) { return stft_lds_base(2048, hop) + pv2k_lds_bytes(); }
+
+// bin e of the lane's seventeen: even e the pair's k = 64 (e / 2) + lane, odd e its mirror N - k, e = 16 bin N / 2 (lane 0 only)
+__device__ __forceinline__ int pv2k_bin(int e, int lane) { return e == 16 ? 512 : (e & 1) ? 1024 - (64 * (e >> 1) + lane) : 64 * (e >> 1) + lane; }
+
+__global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv2k(VpStftArgs A)
+{
+    extern __shared__ double smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int s = blockIdx.y, run = blockIdx.x;
+    constexpr int N = 1024, nb = VP_PV2K_NB;                                   // complex points = F / 2; bins
+    const int F = A.F, hop = A.hop, O = A.O, T = A.T;
+    lds_d2 *xb = (lds_d2 *)smem + wv * 512;
+    lds_f32 *slots = (lds_f32 *)smem;                                          // slot w: the whole exchange buffer (2048 floats)
+    lds_f32 *carry = (lds_f32 *)smem + NWV * 2048;
+    // the stage's arrays (the 16-byte type first: nb is odd)
+    lds_d2 *ana = (lds_d2 *)smem + stft_lds_base(F, hop) / 16 + (size_t)wv * nb;   // [NWV][nb] (magnitude, true frequency in bins) of this wavefront's frame
+    lds_f64 *an = (lds_f64 *)ana;
+    lds_f64 *phPrev = (lds_f64 *)((lds_d2 *)smem + stft_lds_base(F, hop) / 16 + (size_t)NWV * nb);   // [NWV + 1][nb] as in PvLds
+    lds_f64 *sum = phPrev + (NWV + 1) * nb;                                    // [nb] the accumulator: in front of the round, then handed through it
+#ifdef VP_POISON_LDS
+    for (int i = tid; i < (int)((stft_lds_base(F, hop) + pv2k_lds_bytes()) / 8); i += 64 * NWV) ((lds_f64 *)smem)[i] = __builtin_nan("0x5a5a");
+    __syncthreads();
+#endif
+    FftAddr L;
+    fft_addr_init(L, lane);
+    const d2 *tw1p = (const d2 *)A.tw1 + lane * 8, *tw2p = (const d2 *)A.tw2 + lane * 8;
+    const d2 *wtop = (const d2 *)A.twTop + lane * 8, *ws = (const d2 *)A.tws + lane * 8;   // W_1024^(64 q + lane), W_2048^(64 q + lane)
+    const bool lane0 = lane == 0;
+    for (int i = tid; i < F - hop; i += 64 * NWV) carry[i] = 0.f;
+    for (int i = tid; i < nb; i += 64 * NWV) { phPrev[i] = 0.0; sum[i] = 0.0; }
+    __syncthreads();
+
+    const StftRun R = stft_run(A, run);
+    const float *xs = A.in + (size_t)s * T;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) f4 lds_f4;
+    const double invO = 1.0 / (double)O;                                       // nominal phase advance of bin 1 per hop, in turns (O a power of two: exact)
+    const double invRatio = 1.0 / A.pvRatio;
+    for (int rd = R.r0; rd < R.r1; rd++) {
+        const int f = rd * NWV + wv;
+        const bool live = f < A.nFrames;                                       // (wavefront-uniform)
+        const int lastLive = min(NWV - 1, A.nFrames - 1 - rd * NWV);
+        lds_f4 *slot = (lds_f4 *)(slots + wv * 2048);
+        C8 e;
+        double hr[8], hi[8];
+        RPairsN<8> X;
+        if (live) {
+            const float *x = xs + (size_t)f * hop;
+            C8 o;
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                const int m = lane + 64 * r;
+                f4 v;
+                if (A.aligned) v = *(const f4 *)(x + 4 * m);
+                else v = f4{x[4 * m], x[4 * m + 1], x[4 * m + 2], x[4 * m + 3]};
+                const d2 w0 = ((const d2 *)A.win)[2 * m], w1 = ((const d2 *)A.win)[2 * m + 1];
+                e.re[r] = (double)v.x * w0.x; e.im[r] = (double)v.y * w0.y;
+                o.re[r] = (double)v.z * w1.x; o.im[r] = (double)v.w * w1.y;
+            }
+            fft512_rx(e, xb, L, tw1p, tw2p);
+            fft512_rx(o, xb, L, tw1p, tw2p);
+#pragma unroll
+            for (int q = 0; q < 8; q++) {                                      // radix-2 on top: lo = E + W^k' O (kept in e), hi = E - W^k' O
+                const d2 wt = wtop[q];
+                const double tr = __builtin_fma(o.re[q], wt.x, -(o.im[q] * wt.y)), ti = __builtin_fma(o.re[q], wt.y, o.im[q] * wt.x);
+                hr[q] = e.re[q] - tr; hi[q] = e.im[q] - ti;
+                e.re[q] += tr; e.im[q] += ti;
+            }
+            rfft_split_n<8>(e.re, e.im, hr, hi, xb, lane, ws, X);
+            // ---- the stage, phases in TURNS.  Magnitude and phase of the lane's bins, straight to LDS
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const int k = 64 * q + lane, m = N - k;
+                an[2 * k] = sqrt(X.kr[q] * X.kr[q] + X.ki[q] * X.ki[q]); phPrev[(wv + 1) * nb + k] = pv_phase_turns(X.ki[q], X.kr[q]);
+                an[2 * m] = sqrt(X.mr[q] * X.mr[q] + X.mi[q] * X.mi[q]); phPrev[(wv + 1) * nb + m] = pv_phase_turns(X.mi[q], X.mr[q]);
+            }
+            if (lane0) { an[2 * (N / 2)] = sqrt(X.hr * X.hr + X.hi * X.hi); phPrev[(wv + 1) * nb + N / 2] = pv_phase_turns(X.hi, X.hr); }
+        }
+        __syncthreads();
+        // The lane's bins, their candidates and the candidates' tests do not change from round to round, and hoisted out of the loop they
+        // are some 200 vector and 140 scalar registers held for good (716 bytes of scratch in the first build): the stage takes its
+        // lane number through a register the compiler cannot see through, and recomputes them -- a twentieth of the round's instructions.
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        double mg[17], sp[17];                                                 // gathered magnitude; phase increment, then synthesis phase
+        if (live) {
+#pragma unroll
+            for (int b = 0; b < 17; b++) {
+                if (b == 16 && !lane0) continue;
+                const int k = pv2k_bin(b, ln);
+                double d = phPrev[(wv + 1) * nb + k] - phPrev[wv * nb + k] - (double)k * invO;
+                d -= rint(d);                                                  // the unwrap: deviation from the nominal advance in [-1/2, 1/2] turns
+                an[2 * k + 1] = (double)k + d * (double)O;                     // true frequency in bins
+            }
+            wave_sync();
+            // bins move to floor(k ratio + 0.5): synthesis bin kk gathers the analysis bins that land on it, in increasing k
+#pragma unroll
+            for (int b = 0; b < 17; b++) {
+                if (b == 16 && !lane0) continue;
+                const int kk = pv2k_bin(b, ln);
+                const int kc = (int)((double)kk * invRatio);
+                double sm = 0.0, sf = 0.0;
+                d2 cand[5];
+#pragma unroll
+                for (int c_ = 0; c_ < 5; c_++) cand[c_] = ana[min(max(kc - 2 + c_, 0), N)];
+#pragma unroll
+                for (int c_ = 0; c_ < 5; c_++) {
+                    const int k = kc - 2 + c_;
+                    if (k >= 0 && k <= N && (int)floor((double)k * A.pvRatio + 0.5) == kk) { sm += cand[c_].x; sf = cand[c_].y * A.pvRatio; }
+                }
+                mg[b] = sm;
+                sp[b] = sf * invO;                                             // phase advance of the synthesis bin over one hop, in turns
+            }
+        }
+        // the round's sum in frame order, in place: wavefront w's turn comes behind the turns of the frames in front of it
+#pragma unroll
+        for (int w = 0; w < NWV; w++) {
+            if (w > 0) __syncthreads();
+            if (live && wv == w) {
+#pragma unroll
+                for (int b = 0; b < 17; b++) {
+                    if (b == 16 && !lane0) continue;
+                    const int kk = pv2k_bin(b, ln);
+                    sp[b] += sum[kk];
+                    sum[kk] = (w == lastLive) ? sp[b] - rint(sp[b]) : sp[b];   // the round's last live frame leaves the next round's accumulator
+                }
+            }
+        }
+        if (live) {
+            // (every live wavefront is past its reads of the previous frame's phases: the turns' barriers, or program order when the
+            // round's only live wavefront is wavefront 0)
+            if (wv == lastLive) {
+#pragma unroll
+                for (int b = 0; b < 17; b++) {
+                    if (b == 16 && !lane0) continue;
+                    const int k = pv2k_bin(b, ln);
+                    phPrev[k] = phPrev[(wv + 1) * nb + k];
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < 17; b++) {
+                if (b == 16 && !lane0) continue;
+                double sn, cs;
+                pv_sincos_turns(sp[b], sn, cs);
+                const double re = mg[b] * cs, im = mg[b] * sn;
+                if (b == 16) { X.hr = re; X.hi = im; }
+                else if (b & 1) { X.mr[b >> 1] = re; X.mi[b >> 1] = im; }
+                else { X.kr[b >> 1] = re; X.ki[b >> 1] = im; }
+            }
+            if (lane0) { X.ki[0] = 0.0; X.mi[0] = 0.0; }                       // X[0], X[N] of a real frame are real: keep the real parts
+            // ---- merge, the radix-2 step (decimation in frequency), two transforms, window: as vp_k_stft_fused2k
+            rfft_merge_conj_n<8>(e.re, e.im, hr, hi, xb, lane, ws, X, A.c);
+            C8 o;
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const d2 wt = wtop[q];
+                const double dr = e.re[q] - hr[q], di = e.im[q] - hi[q];
+                e.re[q] += hr[q]; e.im[q] += hi[q];
+                o.re[q] = __builtin_fma(dr, wt.x, -(di * wt.y)); o.im[q] = __builtin_fma(dr, wt.y, di * wt.x);
+            }
+            fft512_rx(e, xb, L, tw1p, tw2p);                                               // y[2k'] ...
+            fft512_rx(o, xb, L, tw1p, tw2p);                                               // ... and y[2k' + 1], k' = lane + 64 r: x'[2n] = Re y[n], x'[2n + 1] = -Im y[n]
+            wave_sync();
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                const int m = lane + 64 * r;
+                const d2 w0 = ((const d2 *)A.win)[2 * m], w1 = ((const d2 *)A.win)[2 * m + 1];
+                slot[m] = f4{(float)(e.re[r] * w0.x), (float)(-(e.im[r] * w0.y)), (float)(o.re[r] * w1.x), (float)(-(o.im[r] * w1.y))};
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 8; r++) slot[lane + 64 * r] = f4{0.f, 0.f, 0.f, 0.f};
+        }
+        __syncthreads();
+        stft_overlap_add(A, slots, carry, s, rd, rd >= R.rFirst, tid);
+        __syncthreads();
+    }
+}
+
 // ---- single precision (vp_stft_set_precision(t, VP_STFT_F32); 1024-point frames) ------------------------------------------------------
 // The same kernel with the transform, split and merge in f32 (vp_fft32.inc).  Why it is a build of its own and not the default: the fp64
 // kernel is bound by its instruction stream -- 613 fp64 vector instructions per lane and frame at 4 cycles each, two wavefronts per SIMD
@@ -600,11 +797,13 @@ __global__ __launch_bounds__(64 * NWV, 3) void vp_k_stft_fused2k32(VpStftArgs A)
     }
 }
 
-// hipFuncSetAttribute acts on the CURRENT device: every handle raises the phase-vocoder build's dynamic-LDS ceiling on its own device
+// hipFuncSetAttribute acts on the CURRENT device: every handle raises the two phase-vocoder builds' dynamic-LDS ceiling on its own device
 // at create (vp_stft_create, behind hipSetDevice), and a failure is the caller's VP_ERR_HIP -- not a process-wide flag set once.
 hipError_t vp_stft_prepare_device()
 {
-    return hipFuncSetAttribute((const void *)vp_k_stft_fused<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+    const hipError_t e = hipFuncSetAttribute((const void *)vp_k_stft_fused<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void *)vp_k_stft_pv2k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
 }
 
 hipError_t vp_stft_launch(const VpStftArgs &a, int nStreams, int nRuns, hipStream_t st)
@@ -620,6 +819,8 @@ hipError_t vp_stft_launch(const VpStftArgs &a, int nStreams, int nRuns, hipStrea
         const size_t lds32 = lds + 64 * 8;                                      // + the second step's twiddle rows
         if (a.mag) hipLaunchKernelGGL((vp_k_stft_fused32<true>), grid, block, lds32, st, a);
         else hipLaunchKernelGGL((vp_k_stft_fused32<false>), grid, block, lds32, st, a);
+    } else if (a.pv && a.F == 2048) {
+        hipLaunchKernelGGL(vp_k_stft_pv2k, grid, block, lds + pv2k_lds_bytes(), st, a);       // (before the plain 2048 branch, which has no stage)
     } else if (a.F == 2048) {
         const size_t lds2 = lds + (64 + 512) * 16;                             // + the LDS copies of the 512-point transform's twiddle tables
         if (a.mag) hipLaunchKernelGGL((vp_k_stft_fused2k<true>), grid, block, lds2, st, a);

@@ -524,7 +524,9 @@ class StftRoundTrip:
         return "f32" if self.L.vp_stft_get_precision(self.h) == 1 else "f64"
 
     def pitch_shift(self, d_in, d_out, semitones, stream=None):
-        """Round trip with the phase-vocoder stage (per-bin phase unwrap / accumulate) shifting the pitch by `semitones`."""
+        """Round trip with the phase-vocoder stage (per-bin phase unwrap / accumulate) shifting the pitch by `semitones`
+        (|semitones| <= 12), for 1024- and 2048-point frames at every hop the handle admits.  Always double precision
+        (set_precision has no effect on it); every call starts from zero phase state."""
         import torch
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
         assert d_out.is_cuda and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
