@@ -343,6 +343,17 @@ int vp_stft_roundtrip(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
  * frame_len / 2 real, samples no frame covers 0.  Double precision whatever vp_stft_set_precision says.  VP_ERR_INVALID_ARG for null
  * pointers or |semitones| > 12, VP_ERR_HIP when the device refused the kernels' LDS size at create.  No reference counterpart. */
 int vp_stft_pitch_shift(vp_stft *p, const float *d_in, float *d_out, double semitones, void *hip_stream);
+/* vp_stft_pitch_shift along a pitch curve (kernels vp_k_stft_pv_curve and vp_k_stft_pv2k_curve): tests/stft_reference.py's
+ * stft_roundtrip with `ratio` replaced by ratio[s][f] in frame f -- the previous-frame phases, the accumulator's rounds of four frames and
+ * the gather are unchanged.  A curve that is constant per stream gives vp_stft_pitch_shift's bits.  Both frame lengths, every hop,
+ * always double, one workgroup per stream.
+ * d_ratio: device double [n_streams][vp_stft_num_frames(p)], the pitch ratio of frame f of stream s.
+ * Used as r = fmin(fmax(r, 0.5), 2.0), so a NaN becomes 0.5.
+ * VP_ERR_INVALID_ARG for null pointers, VP_ERR_HIP when the device refused the kernels' LDS size at create. */
+int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream);
+/* pow(2, st / 12) exactly as vp_stft_pitch_shift / vp_pv_set_semitones compute it (same bits).
+ * VP_ERR_INVALID_ARG if an entry is outside +-12 or not finite; nothing is written then.  Host arrays; no device is touched. */
+int vp_semitones_to_ratios(const double *semitones, double *ratios, long n);
 int vp_stft_is_fused(const vp_stft *p);                      /* 1 (every handle runs the fused kernel; kept for older callers) */
 /* Diagnostic: cut every stream into this many runs of frames (one workgroup each) instead of choosing from the batch size
  * (0 = automatic).  The output does not depend on it (tests). */
@@ -390,6 +401,12 @@ int vp_pv_process_block(vp_pv *p, const float *in, float *out);
 /* device float [n_blocks][S][N] -> [n_blocks][S][N] (block b's slab is what vp_pv_process_block would take), enqueued on hip_stream
  * (a hipStream_t, NULL = default stream) without synchronising, like vp_process_blocks_device */
 int vp_pv_process_blocks_device(vp_pv *p, const float *d_in, float *d_out, int n_blocks, void *hip_stream);
+/* The same call with one pitch ratio per block and stream (kernel vp_k_pv_stream_curve).
+ * d_ratio: device double [n_blocks][S]. A frame is computed with the ratio of the block in which its last sample arrives (clamped as
+ * in vp_stft_pitch_shift_curve).  Pending vp_pv_reset calls apply as in any call.  The interval set by vp_pv_set_semitones is neither
+ * used nor changed by this call: it is stored as usual and holds again from the next plain call on.  The table is read when the kernel
+ * runs: keep it unchanged until then.  No allocation. */
+int vp_pv_process_blocks_curve_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream);
 long vp_pv_debug_alloc_count(const vp_pv *p);                           /* constant across process calls */
 
 const char *vp_error_string(int code);

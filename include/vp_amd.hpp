@@ -373,6 +373,12 @@ public:
     {
         check(vp_pv_process_blocks_device(p_, dIn, dOut, nBlocks, hipStream), "processBlocksDevice");
     }
+    // the same with one pitch RATIO per block and stream, device double [nBlocks][S] (vp_semitones_to_ratios converts intervals): a frame
+    // takes the ratio of the block in which its last sample arrives; setSemitones' interval is neither used nor changed
+    void processBlocksCurve(const float *dIn, float *dOut, const double *dRatio, int nBlocks, void *hipStream = nullptr)
+    {
+        check(vp_pv_process_blocks_curve_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksCurve");
+    }
     vp_pv *handle() const { return p_; }
 
 private:

@@ -2,7 +2,15 @@
 """Diagnostic: the phase-vocoder stage (vp_stft_pitch_shift) at the bench's shape, a few intervals.
 
     [VP_AMD_LIB=...] python tools/pv_bench.py
+    [VP_AMD_LIB=...] python tools/pv_bench.py --curve [--reps 7] [--out profiles/pv_curve_bench.txt]
+
+--curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
+"steps" curve, fixed, ...): 256 streams x 65 536 samples at 1024 points / hop 256 and 2048 points / hop 512 (vp_stft_pitch_shift against
+vp_stft_pitch_shift_curve), then streaming, 16 blocks of 1024 per call, plain against curve.  Every repetition is a window of calls that
+ends in a device synchronise; mean, min and max of the repetitions' rates are printed, and the constant curve's mean over the fixed
+interval's from the same run.
 """
+import argparse
 import os
 import sys
 import time
@@ -10,7 +18,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main():
+def fixed_intervals():
     import torch
     from vocoderproject_amd import StftRoundTrip
     S, T, F, hop = 256, 65536, 1024, 256
@@ -30,6 +38,86 @@ def main():
         dt = (time.perf_counter() - t0) / n
         print(f"{semis:+5.1f} semitones: {frames / dt / 1e6:7.1f} M frames/s  {dt * 1e6:8.1f} us per call")
     st.close()
+
+
+def alternate(legs, reps, calls, warmup=3):
+    """legs: {name: callable enqueueing one call}.  Returns {name: [seconds per call, one per repetition]}, the legs taking turns."""
+    import torch
+    for fn in legs.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    out = {k: [] for k in legs}
+    for _ in range(reps):
+        for name, fn in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                fn()
+            torch.cuda.synchronize()
+            out[name].append((time.perf_counter() - t0) / calls)
+    return out
+
+
+def report(title, times, frames, base, emit):
+    emit(title)
+    rate = {k: [frames / t / 1e6 for t in v] for k, v in times.items()}
+    for k, r in rate.items():
+        mean = sum(r) / len(r)
+        emit(f"  {k:<28s} {mean:8.1f} M frames/s  (min {min(r):.1f}, max {max(r):.1f}, {len(r)} repetitions)"
+             + ("" if k == base else f"  {mean / (sum(rate[base]) / len(rate[base])):.3f} x {base}"))
+
+
+def curve_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import PhaseVocoderStream, StftRoundTrip, semitones_to_ratios
+    S, T = 256, 65536
+    rng = np.random.default_rng(9)
+    x = torch.randn(S, T, device="cuda", dtype=torch.float32) * 0.1
+    y = torch.empty_like(x)
+    for F, hop in ((1024, 256), (2048, 512)):
+        st = StftRoundTrip(S, T, F, hop)
+        nF = st.n_frames
+        const = torch.from_numpy(np.full((S, nF), semitones_to_ratios([7.0])[0])).cuda()
+        steps = torch.from_numpy(semitones_to_ratios(rng.uniform(-12.0, 12.0, (S, nF)))).cuda()
+        legs = {"fixed +7 (parent kernel)": lambda: st.pitch_shift(x, y, 7.0),
+                "curve, constant +7": lambda: st.pitch_shift_curve(x, y, d_ratio=const),
+                "curve, steps": lambda: st.pitch_shift_curve(x, y, d_ratio=steps)}
+        report(f"one-shot, {S} streams x {T} samples, F = {F}, hop = {hop}", alternate(legs, reps, 100), S * nF, "fixed +7 (parent kernel)", emit)
+        st.close()
+    N, K, hop = 1024, 16, 256
+    ps = PhaseVocoderStream(S, N, hop=hop)
+    ps.set_semitones(7.0)
+    xb = torch.randn(K, S, N, device="cuda", dtype=torch.float32) * 0.1
+    yb = torch.empty_like(xb)
+    const = torch.from_numpy(np.full((K, S), semitones_to_ratios([7.0])[0])).cuda()
+    steps = torch.from_numpy(semitones_to_ratios(rng.uniform(-12.0, 12.0, (K, S)))).cuda()
+    legs = {"plain +7 (parent kernel)": lambda: ps.process_device(xb, yb, n_blocks=K),
+            "curve, constant +7": lambda: ps.process_device(xb, yb, n_blocks=K, d_ratio=const),
+            "curve, steps": lambda: ps.process_device(xb, yb, n_blocks=K, d_ratio=steps)}
+    report(f"streaming, {S} streams, {K} blocks of {N} per call, hop = {hop}", alternate(legs, reps, 300), S * K * N // hop, "plain +7 (parent kernel)", emit)
+    ps.close()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--curve", action="store_true", help="the ratio-curve legs instead of the fixed intervals")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=None, help="--curve: also write the report to this file")
+    a = ap.parse_args()
+    if not a.curve:
+        return fixed_intervals()
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+    curve_legs(max(5, a.reps), emit)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":

@@ -1875,7 +1875,7 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     // (hipFuncSetAttribute acts on the current device).  Only vp_stft_pitch_shift needs it, so a failure is remembered and fails
     // THAT call; the plain and single-precision round trips (<= 64 KB) are served regardless.  The sticky HIP error is cleared so
     // that a later hipGetLastError() behind a launch does not report this one.
-    p->pvOk = vp_stft_prepare_device() == hipSuccess;
+    p->pvOk = vp_stft_prepare_device() == hipSuccess && vp_stft_curve_prepare_device() == hipSuccess;
     if (!p->pvOk) (void)hipGetLastError();
     p->device = device; p->F = frame_len; p->hop = hop; p->S = n_streams; p->T = n_samples;
     p->nFrames = (n_samples - frame_len) / hop + 1;
@@ -1945,7 +1945,8 @@ extern "C" int vp_stft_set_precision(vp_stft *p, int precision)
 }
 extern "C" int vp_stft_get_precision(const vp_stft *p) { return p ? (p->f32 ? VP_STFT_F32 : VP_STFT_F64) : VP_ERR_INVALID_ARG; }
 
-static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag, hipStream_t st, bool pv, double ratio)
+// (d_ratio: the phase-vocoder stage reads its ratio per frame from this table, `ratio` is unused then)
+static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag, hipStream_t st, bool pv, double ratio, const double *d_ratio = nullptr)
 {
     VpStftArgs a;
     memset(&a, 0, sizeof a);
@@ -1970,6 +1971,7 @@ static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
     }
     a.roundsPerRun = (a.nRounds + runs - 1) / runs;
     const int nRuns = (a.nRounds + a.roundsPerRun - 1) / a.roundsPerRun;
+    if (d_ratio) return vp_stft_launch_curve(a, d_ratio, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     return vp_stft_launch(a, p->S, nRuns, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
 }
 
@@ -1988,6 +1990,23 @@ extern "C" int vp_stft_pitch_shift(vp_stft *p, const float *d_in, float *d_out, 
     if (!p->pvOk) return VP_ERR_HIP;                           // (its dynamic-LDS ceiling could not be raised on this device: vp_stft_create)
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, std::pow(2.0, semitones / 12.0));
+}
+
+// the pitch shift along a ratio curve: d_ratio [S][nFrames], one workgroup per stream (vp_k_stft_pv_curve / vp_k_stft_pv2k_curve)
+extern "C" int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream)
+{
+    if (!p || !d_in || !d_out || !d_ratio) return VP_ERR_INVALID_ARG;
+    if (!p->pvOk) return VP_ERR_HIP;                           // (as vp_stft_pitch_shift)
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio);
+}
+
+extern "C" int vp_semitones_to_ratios(const double *semitones, double *ratios, long n)
+{
+    if (!semitones || !ratios || n < 0) return VP_ERR_INVALID_ARG;
+    for (long i = 0; i < n; i++) if (!(semitones[i] >= -12.0 && semitones[i] <= 12.0)) return VP_ERR_INVALID_ARG;   // (a NaN fails both tests)
+    for (long i = 0; i < n; i++) ratios[i] = std::pow(2.0, semitones[i] / 12.0);      // (as vp_stft_pitch_shift / vp_pv_set_semitones: the same bits)
+    return VP_OK;
 }
 
 // ---- streaming phase vocoder (no reference counterpart): vp_k_pv_stream of vp_stft.hip, the one-shot stage block by block -----------
@@ -2023,7 +2042,7 @@ extern "C" int vp_pv_create(int device, int n_streams, int block_size, int frame
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VP_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    if (vp_pv_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
+    if (vp_pv_prepare_device() != hipSuccess || vp_pv_curve_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
     vp_pv *p = new vp_pv();
     p->device = device; p->S = n_streams; p->N = block_size; p->F = frame_len; p->hop = hop;
     int g = block_size, b = hop;
@@ -2100,7 +2119,8 @@ extern "C" int vp_pv_reset(vp_pv *p, int stream)
 
 // the pending changes travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update launches in front of it): ordered on
 // the caller's stream, no host memory the device reads later, no allocation
-static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipStream_t st)
+// (d_ratio: one ratio per block and stream for this call, [n_blocks][S]; the pending changes travel and are stored as in any call)
+static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipStream_t st, const double *d_ratio = nullptr)
 {
     p->upd.clear();
     if (p->allRatio > 0.0 || p->allReset) p->upd.push_back(VpPvUpdate{-1, p->allReset ? 1 : 0, p->allRatio});
@@ -2119,7 +2139,7 @@ static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipSt
     }
     a.in = d_in; a.out = d_out; a.nBlocks = n_blocks; a.nUpd = (int)(p->upd.size() - i);
     for (int k = 0; k < a.nUpd; k++) a.upd[k] = p->upd[i + k];
-    if (vp_pv_launch(a, st) != hipSuccess) return VP_ERR_HIP;
+    if ((d_ratio ? vp_pv_launch_curve(a, d_ratio, st) : vp_pv_launch(a, st)) != hipSuccess) return VP_ERR_HIP;
     p->allRatio = 0.0; p->allReset = false;
     std::fill(p->ratioPend.begin(), p->ratioPend.end(), 0.0);
     std::fill(p->resetPend.begin(), p->resetPend.end(), 0);
@@ -2131,6 +2151,13 @@ extern "C" int vp_pv_process_blocks_device(vp_pv *p, const float *d_in, float *d
     if (!p || !d_in || !d_out || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream);
+}
+
+extern "C" int vp_pv_process_blocks_curve_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream)
+{
+    if (!p || !d_in || !d_out || !d_ratio || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio);
 }
 
 extern "C" int vp_pv_process_block(vp_pv *p, const float *in, float *out)

@@ -33,6 +33,10 @@ hipError_t vp_stft_launch(const VpStftArgs &a, int nStreams, int nRuns, hipStrea
 int vp_stft_supported(int F, int hop);
 // once per handle, on the handle's device (current device): the dynamic-LDS ceiling of the builds that need more than 64 KB
 hipError_t vp_stft_prepare_device();
+// the phase-vocoder builds that read the ratio per frame from d_ratio [nStreams][nFrames] (vp_k_stft_pv_curve / vp_k_stft_pv2k_curve, by
+// a.F; csrc/vp_stft_curve.inc): one workgroup per stream, a.roundsPerRun = a.nRounds; and their dynamic-LDS ceiling, as above
+hipError_t vp_stft_launch_curve(const VpStftArgs &a, const double *d_ratio, int nStreams, hipStream_t st);
+hipError_t vp_stft_curve_prepare_device();
 
 // ---- streaming phase vocoder (vp_pv_*): one workgroup per stream and call, state in HBM between calls -----------------------------
 #define VP_PV_MAX_UPDATES 16            // interval changes / resets carried in a process call's arguments
@@ -67,3 +71,6 @@ size_t vp_pv_lds_bytes();
 // the streaming kernel (grid = S workgroups); nBlocks = 0 launches the small kernel that only applies the updates
 hipError_t vp_pv_launch(const VpPvArgs &a, hipStream_t st);
 hipError_t vp_pv_prepare_device();
+// the streaming kernel with one ratio per block and stream, d_ratio [a.nBlocks][a.S] (vp_k_pv_stream_curve; a.nBlocks > 0)
+hipError_t vp_pv_launch_curve(const VpPvArgs &a, const double *d_ratio, hipStream_t st);
+hipError_t vp_pv_curve_prepare_device();

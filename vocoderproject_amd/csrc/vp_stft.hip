@@ -1106,3 +1106,6 @@ hipError_t vp_pv_launch(const VpPvArgs &a, hipStream_t st)
     else hipLaunchKernelGGL(vp_k_pv_stream, dim3(a.S), dim3(64 * NWV), vp_pv_lds_bytes(), st, a);
     return hipGetLastError();
 }
+
+// ---- the phase-vocoder kernels along a per-frame / per-block ratio curve (vp_stft_pitch_shift_curve, vp_pv_process_blocks_curve_device) ----
+#include "vp_stft_curve.inc"

@@ -13,6 +13,7 @@ There is no CPU path here either: without a GPU the processor raises.
     python -m vocoderproject_amd.offline pitch  take1.wav take2.wav --out-dir tuned/ [--key 12] [--shift +3]
     python -m vocoderproject_amd.offline vocode voice.wav --carrier synth.wav --out-dir out/
     python -m vocoderproject_amd.offline pvshift a.wav b.wav --shift 7 --out-dir out/     (streaming phase vocoder)
+    python -m vocoderproject_amd.offline pvshift a.wav --glide -12:12 --out-dir out/      (... along a glide, one interval per block)
 """
 import argparse
 import os
@@ -197,6 +198,44 @@ def pv_shift(voices, shift, N=1024, hop=256, device=0, processor=None):
     return [np.ascontiguousarray(np.stack([y[s, lat:lat + lens[s]]] * 2)) for s in range(S)]
 
 
+def glide_curve(lens, start, end, N, n_blocks):
+    """Semitones per block and recording, float64 [n_blocks][S]: a linear glide from `start` to `end` over each recording's own blocks
+    (block b of a recording of n blocks: start + (end - start) b / (n - 1)), `end` behind its last block."""
+    c = np.empty((int(n_blocks), len(lens)))
+    for s, n in enumerate(lens):
+        nb = max(1, -(-int(n) // int(N)))
+        t = np.minimum(np.arange(int(n_blocks)) / max(nb - 1, 1), 1.0)
+        c[:, s] = float(start) + (float(end) - float(start)) * t
+    return c
+
+
+def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, processor=None):
+    """pv_shift with a glide: every recording's interval moves linearly from `start` to `end` semitones over its length, one value per
+    block, through the streaming phase vocoder's ratio-curve call (PhaseVocoderStream.run(curve=...): several blocks per call, each
+    with its own interval).  Returns float32 [2][len] per recording.  `processor` (tests): an object with latency and
+    run(x, blocks_per_call, curve) to use instead of a new PhaseVocoderStream."""
+    S = len(voices)
+    if S == 0:
+        raise ValueError("no recordings")
+    if not (-12.0 <= float(start) <= 12.0 and -12.0 <= float(end) <= 12.0):
+        raise ValueError("glide: intervals within +-12 semitones expected")
+    p = processor
+    if p is None:
+        from . import PhaseVocoderStream
+        p = PhaseVocoderStream(S, int(N), hop=int(hop), device=device)
+    lens = [int(np.asarray(v).shape[-1]) for v in voices]
+    T = max(lens)
+    x = np.zeros((S, T), np.float32)
+    for s, v in enumerate(voices):
+        v = np.asarray(v, np.float32)
+        if v.ndim != 1:
+            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
+        x[s, :lens[s]] = v
+    curve = glide_curve(lens, start, end, N, -(-(T + int(p.latency)) // int(N)))
+    y = p.run(x, blocks_per_call=int(blocks_per_call), curve=curve)           # aligned with the input: the latency is off
+    return [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
+
+
 # ---- command line ---------------------------------------------------------------------------------------------------------
 
 def main(argv=None):
@@ -208,12 +247,20 @@ def main(argv=None):
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--key", type=int, default=12, help="keyPitch 0..12 (12 = chromatic, the plugin's default)")
     ap.add_argument("--shift", type=float, default=None, help="fixed interval in semitones instead of the key correction")
+    ap.add_argument("--glide", default=None, metavar="A:B",
+                    help="pvshift: a linear glide from A to B semitones over each recording, one value per block, instead of --shift")
     ap.add_argument("--lpc-voice", type=int, default=40)
     ap.add_argument("--lpc-synth", type=int, default=5)
     ap.add_argument("--block", type=int, default=1024)
     ap.add_argument("--hop", type=int, default=256, help="pvshift: hop of the 1024-point frames (64, 128, 256 or 512)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--fast", action="store_true", help="VP_IIR_FAST + certified cross-correlation YIN")
+    # (a glide that starts below zero, "--glide -12:12", looks like an option to argparse: hand it over as --glide=-12:12)
+    argv = list(sys.argv[1:] if argv is None else argv)
+    for i in range(len(argv) - 1):
+        if argv[i] == "--glide" and ":" in argv[i + 1]:
+            argv[i:i + 2] = ["--glide=" + argv[i + 1]]
+            break
     a = ap.parse_args(argv)
 
     recs = [read_wav(f) for f in a.inputs]
@@ -222,9 +269,16 @@ def main(argv=None):
         raise SystemExit("all recordings of a batch must share one sample rate (one prepareToPlay)")
     voices = [r[1][0] for r in recs]
     if a.flow == "pvshift":
-        if a.shift is None:
-            raise SystemExit("pvshift needs --shift")
-        outs = pv_shift(voices, a.shift, N=a.block, hop=a.hop, device=a.device)
+        if (a.shift is None) == (a.glide is None):
+            raise SystemExit("pvshift needs --shift or --glide A:B")
+        if a.glide is not None:
+            try:
+                g0, g1 = (float(v) for v in a.glide.split(":"))
+            except ValueError:
+                raise SystemExit("--glide: A:B expected, two intervals in semitones")
+            outs = pv_glide(voices, g0, g1, N=a.block, hop=a.hop, device=a.device)
+        else:
+            outs = pv_shift(voices, a.shift, N=a.block, hop=a.hop, device=a.device)
         return _write_outputs(a, fs, outs)
     carriers = None
     if a.flow != "pitch":

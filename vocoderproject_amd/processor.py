@@ -131,6 +131,10 @@ def load_library():
     L.vp_stft_roundtrip.argtypes = [vp, fp, fp, fp, C.c_void_p]
     L.vp_stft_pitch_shift.argtypes = [vp, fp, fp, C.c_double, C.c_void_p]
     L.vp_stft_is_fused.argtypes = [vp]
+    if hasattr(L, "vp_stft_pitch_shift_curve"):        # (the ratio-curve entries; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_stft_pitch_shift_curve.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p]
+        L.vp_semitones_to_ratios.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
+        L.vp_pv_process_blocks_curve_device.argtypes = [vp, fp, fp, C.c_void_p, C.c_int, C.c_void_p]
     L.vp_stft_set_runs.argtypes = [vp, C.c_int]
     L.vp_stft_set_precision.argtypes = [vp, C.c_int]
     L.vp_stft_get_precision.argtypes = [vp]
@@ -479,6 +483,30 @@ class BatchVocoderProcessor:
         return self.L.vp_vocoder_kernel_name(self.h).decode()
 
 
+def semitones_to_ratios(semitones):
+    """Pitch ratios 2^(st / 12) of an array of intervals, float64 of the same shape, through the library's vp_semitones_to_ratios:
+    the bits vp_stft_pitch_shift and vp_pv_set_semitones use (numpy.power's may differ).  VpError for an entry outside +-12 or not finite."""
+    L = load_library()
+    st = np.ascontiguousarray(semitones, dtype=np.float64)
+    r = np.empty_like(st)
+    rc = L.vp_semitones_to_ratios(st.ctypes.data, r.ctypes.data, st.size)
+    if rc:
+        raise VpError(rc, L.vp_error_string(rc).decode())
+    return r
+
+
+def _upload_ratios(tables, semitones, dev):
+    """The ratios of a table of intervals (already in the kernel's layout) in a device table of that shape, allocated once per shape in
+    the caller's `tables`; the copy goes on torch's current stream."""
+    import torch
+    r = semitones_to_ratios(semitones)
+    tab = tables.get(r.shape)
+    if tab is None:
+        tab = tables[r.shape] = torch.empty(r.shape, dtype=torch.float64, device=dev)
+    tab.copy_(torch.from_numpy(r))
+    return tab
+
+
 class StftRoundTrip:
     """Standalone batched STFT -> iSTFT (no reference counterpart; see include/vp_amd.h vp_stft_*)."""
 
@@ -533,6 +561,29 @@ class StftRoundTrip:
         if stream is None:
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
         rc = self.L.vp_stft_pitch_shift(self.h, d_in.data_ptr(), d_out.data_ptr(), float(semitones), C.c_void_p(stream))
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+
+    def pitch_shift_curve(self, d_in, d_out, semitones=None, stream=None, d_ratio=None):
+        """pitch_shift along a pitch curve (vp_stft_pitch_shift_curve): `semitones` is array-like [n_frames] (every stream follows it) or
+        [S][n_frames], each |value| <= 12; frame f of stream s is shifted by semitones[s][f].  The intervals become ratios through
+        semitones_to_ratios and are uploaded into a device table the handle allocates once (on torch's current stream: with another
+        `stream`, order it behind that one).  d_ratio instead: a device float64 tensor [S][n_frames] of ratios, used as it is (the
+        kernel clamps to [0.5, 2])."""
+        import torch
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
+        assert d_out.is_cuda and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
+        assert (semitones is None) != (d_ratio is None), "one of semitones and d_ratio"
+        if d_ratio is None:
+            st = np.asarray(semitones, dtype=np.float64)
+            assert st.shape in ((self.n_frames,), (self.S, self.n_frames)), st.shape
+            if not hasattr(self, "_curve_tables"):
+                self._curve_tables = {}
+            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(st, (self.S, self.n_frames)), d_in.device)
+        assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (self.S, self.n_frames) and d_ratio.is_contiguous()
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        rc = self.L.vp_stft_pitch_shift_curve(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), C.c_void_p(stream))
         if rc:
             raise VpError(rc, self.L.vp_error_string(rc).decode())
 
@@ -595,21 +646,40 @@ class PhaseVocoderStream:
         self._chk(self.L.vp_pv_process_block(self.h, x.ctypes.data, y.ctypes.data))
         return y
 
-    def process_device(self, d_in, d_out, n_blocks=1, stream=None):
+    def process_device(self, d_in, d_out, n_blocks=1, stream=None, semitones_per_block=None, d_ratio=None):
         """n_blocks blocks on the device: torch float32 [n_blocks][S][N] (or [S][N] for one block), enqueued on `stream`
-        (default: the current torch stream) without synchronising."""
+        (default: the current torch stream) without synchronising.
+        semitones_per_block: array-like [n_blocks] or [n_blocks][S], |value| <= 12 -- this call's frames take the interval of the block in
+        which their last sample arrives (vp_pv_process_blocks_curve_device); set_semitones' interval is neither used nor changed.  The
+        table is uploaded on torch's current stream into a device table kept per n_blocks.  d_ratio instead: a device float64 tensor
+        [n_blocks][S] of ratios, used as it is."""
         import torch
         shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
         assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == shape and d_out.is_contiguous()
         if stream is None:
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        if semitones_per_block is not None:
+            assert d_ratio is None, "one of semitones_per_block and d_ratio"
+            st = np.asarray(semitones_per_block, dtype=np.float64)
+            assert st.shape in ((int(n_blocks),), (int(n_blocks), self.S)), st.shape
+            if not hasattr(self, "_curve_tables"):
+                self._curve_tables = {}
+            st = np.broadcast_to(st.reshape(int(n_blocks), -1), (int(n_blocks), self.S))
+            d_ratio = _upload_ratios(self._curve_tables, st, d_in.device)
+        if d_ratio is not None:
+            assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (int(n_blocks), self.S) and d_ratio.is_contiguous()
+            self._chk(self.L.vp_pv_process_blocks_curve_device(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), int(n_blocks),
+                                                               C.c_void_p(stream)))
+            return
         self._chk(self.L.vp_pv_process_blocks_device(self.h, d_in.data_ptr(), d_out.data_ptr(), int(n_blocks), C.c_void_p(stream)))
 
-    def run(self, x, blocks_per_call=8):
+    def run(self, x, blocks_per_call=8, curve=None):
         """Whole signals float [S][T] -> output aligned with the input, [S][T]: the input padded with `latency` zeros (and up to
         whole blocks), streamed through the device entry point `blocks_per_call` blocks at a time, the first `latency` samples
-        dropped.  Continues from the handle's state (reset() first for a fresh start)."""
+        dropped.  Continues from the handle's state (reset() first for a fresh start).
+        curve: semitones per block, array-like [n] or [n][S] with n >= 1; block b takes row min(b, n - 1) (the padding keeps the last
+        row), through process_device(semitones_per_block=...)."""
         import torch
         x = np.asarray(x, dtype=np.float32)
         assert x.ndim == 2 and x.shape[0] == self.S, x.shape
@@ -617,13 +687,20 @@ class PhaseVocoderStream:
         nb = -(-(T + Lat) // N)
         xp = np.zeros((self.S, nb * N), np.float32)
         xp[:, :T] = x
+        if curve is not None:
+            curve = np.asarray(curve, dtype=np.float64)
+            assert curve.ndim in (1, 2) and curve.shape[0] >= 1 and (curve.ndim == 1 or curve.shape[1] == self.S), curve.shape
+            curve = curve[np.minimum(np.arange(nb), curve.shape[0] - 1)]
         dev = torch.device("cuda", self.device)
         d_in = torch.from_numpy(np.ascontiguousarray(xp.reshape(self.S, nb, N).transpose(1, 0, 2))).to(dev)
         d_out = torch.empty_like(d_in)
         b = 0
         while b < nb:
             k = min(int(blocks_per_call), nb - b)
-            self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k)
+            if curve is None:
+                self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k)
+            else:
+                self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k, semitones_per_block=curve[b:b + k])
             b += k
         torch.cuda.synchronize(dev)
         y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, nb * N)
