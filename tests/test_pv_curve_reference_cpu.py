@@ -1,7 +1,9 @@
 """CPU-side checks of the ratio-curve pitch shift (vp_stft_pitch_shift_curve, vp_pv_process_blocks_curve_device): the reference of a
 time-varying ratio is well conditioned on every case the GPU tests compare against it (the gate), a curve that is one frame off cannot
 hide inside the bound (teeth), a constant curve is the fixed-interval definition, vp_semitones_to_ratios gives the library's bits, the
-symbols and their argument checks, and the offline glide's plumbing.  The kernels are checked on the GPU (tests/test_gpu_pv_curve.py)."""
+symbols and their argument checks, and the offline glide's plumbing.  The same gate and teeth hold for every list that
+tests/test_gpu_pv_curve_edges.py compares pointwise: the one-shot edges, the streaming cases, the scenarios of curve and plain calls, and
+the streams checked in the batch of 300.  The kernels are checked on the GPU (tests/test_gpu_pv_curve.py, tests/test_gpu_pv_curve_edges.py)."""
 import ctypes as C
 import os
 import sys
@@ -57,6 +59,87 @@ def test_gate_and_teeth(c):
         assert gate <= tol, (s, gate)
         assert not np.array_equal(np.roll(ratio[s], 1), ratio[s])
         assert teeth > CC.TEETH * bnd, (s, teeth / bnd)
+
+
+def _gate_and_teeth(tag, what, ref, turns, others, bound_of):
+    """Per stream: the radians and turns forms agree to GATE_TOL max(1, max |ref|); every reference of `others` ({name: [S][T]}), the
+    schedule off by one, is more than TEETH bounds away."""
+    for s in range(ref.shape[0]):
+        gate = np.abs(ref[s] - turns[s]).max()
+        tol = CC.GATE_TOL * max(1.0, np.abs(ref[s]).max())
+        bnd = bound_of(ref[s])
+        teeth = {k: np.abs(ref[s] - o[s]).max() / bnd for k, o in others.items()}
+        print(f"{tag} {what} stream {s}: gate {gate:.3g} (tol {tol:.3g})  " + "  ".join(f"{k}/bound {v:.3g}" for k, v in teeth.items()))
+        assert gate <= tol, (s, gate)
+        for k, v in teeth.items():
+            assert v > CC.TEETH, (s, k, v)
+
+
+def test_the_new_lists_are_the_ones_the_issue_names():
+    assert {(c.F, c.hop) for c in CC.EDGE_CASES} == {(c.F, c.hop) for c in CC.CASES}
+    for F in (1024, 2048):
+        for hop in CC.HOPS[F]:
+            cs = [c for c in CC.EDGE_CASES if (c.F, c.hop) == (F, hop)]
+            assert sorted((c.nF, c.extra, c.curve) for c in cs) == sorted(
+                [(1, hop - 1, "steps")] + [(nF, ex, cv) for nF, ex in ((2, 0), (5, hop - 1), (6, 2)) for cv in ("glide", "steps")])
+    for c in CC.EDGE_CASES:
+        T, st = CC.edge_length(c), CC.semitones_of(c)
+        assert (T - c.F) // c.hop + 1 == c.nF and T - (c.F + (c.nF - 1) * c.hop) == c.extra < c.hop
+        assert (c.nF - 1) % 4 + 1 in (1, 2)                                             # frames of the last round
+        assert st.shape == (CC.N_STREAMS, c.nF) and np.abs(st).max() <= 12.0
+    assert {(c.hop, c.N) for c in CC.STREAM_CURVE_CASES} == {(h, n) for h in (64, 128, 256, 512) for n in (17, 64, 100, 1000, 1024, 4096)}
+    for c in CC.STREAM_CURVE_CASES:
+        assert c.n_blocks == max(-(-10 * 1024 // c.N), 5) and CC.stream_curve_semitones(c).shape == (c.n_blocks, CC.N_STREAMS)
+    assert [c.hop for c in CC.CURVE_SCENARIOS] == list(pv_cases.HOPS)
+    for c in CC.CURVE_SCENARIOS:
+        spans = pv_cases.call_spans(c.n_blocks, c.calls)
+        assert (c.N, c.n_blocks, c.calls) == (100, 124, (1, 3, 16, 2)) and sorted(c.resets) == [4, 8, 13]
+        assert not any(CC.scenario_is_plain(i) for i in c.resets)                     # every reset precedes a curve call
+        assert 0 < sum(CC.scenario_is_plain(i) for i in range(len(spans))) < len(spans) // 4 + 1
+
+
+@pytest.mark.parametrize("c", CC.EDGE_CASES, ids=CC.edge_id)
+def test_gate_and_teeth_edges(c):
+    """Last rounds of one and two frames, one- and two-frame signals, a tail of hop - 1 samples.  Teeth: the curve rolled by a frame; on
+    one frame every stream with its neighbour stream's ratio."""
+    ratio = CC.ratios_of(c)
+    off = np.roll(ratio, 1, axis=1) if c.nF >= 2 else np.roll(ratio, -1, axis=0)
+    assert all(not np.array_equal(off[s], ratio[s]) for s in range(CC.N_STREAMS))
+    _gate_and_teeth("CURVE", CC.edge_id(c), CC.edge_reference(c), CC.edge_reference(c, "turns"), {"off": CC.edge_reference(c, off=True)},
+                    lambda r: CC.bound(c, r))
+
+
+@pytest.mark.parametrize("c", CC.STREAM_CURVE_CASES, ids=CC.stream_curve_id)
+def test_gate_and_teeth_stream_curve(c):
+    """The streaming curve cases.  Teeth: every block with the ratio of the block behind it, and of the block in front of it."""
+    _gate_and_teeth("CURVESTREAM", CC.stream_curve_id(c), CC.stream_curve_reference(c), CC.stream_curve_reference(c, "turns"),
+                    {"next": CC.stream_curve_reference(c, shift=1), "prev": CC.stream_curve_reference(c, shift=-1)},
+                    lambda r: pv_cases.bound(c.hop, r))
+
+
+@pytest.mark.parametrize("c", CC.CURVE_SCENARIOS, ids=pv_cases.scenario_id)
+def test_gate_and_teeth_curve_scenarios_and_where_their_resets_land(c):
+    ref, landed, held = CC.scenario_reference(c)
+    hits = {i: (fr, m) for per_stream in landed for i, fr, m in per_stream}
+    assert sorted(hits) == [4, 8, 13]
+    assert hits[4][0] != 0 and hits[8][0] != 0, hits                                  # in the middle of a round, at every hop
+    assert any(fr != 0 and m < pv_cases.F for fr, m in hits.values()), hits           # ... followed by a call shorter than a frame
+    assert held == [-12.0, 5.0, 0.37, -4.0]                                           # the last change of every stream
+    _gate_and_teeth("CURVESCENARIO", pv_cases.scenario_id(c), ref, CC.scenario_reference(c, "turns")[0],
+                    {"next": CC.scenario_reference(c, shift=1)[0], "all-plain": CC.scenario_reference(c, all_plain=True)[0]},
+                    lambda r: pv_cases.bound(c.hop, r))
+
+
+@pytest.mark.parametrize("g", CC.BIG_LEGS, ids=CC.big_id)
+def test_gate_and_teeth_of_the_streams_checked_in_the_large_batch(g):
+    ref, turns, off = CC.big_reference(g), CC.big_reference(g, "turns"), CC.big_reference(g, off=True)
+    O = g.F // g.hop
+    assert sorted(ref) == sorted(CC.BIG_CHECKED) and (g.T % 2 == 1 or g.F == 2048 or g.kind == "stream")
+
+    def rows(d):
+        return np.stack([d[s] for s in CC.BIG_CHECKED])
+    _gate_and_teeth("CURVEBIG", CC.big_id(g), rows(ref), rows(turns), {"off": rows(off)},
+                    lambda r: 4.0 * O * 2.0 ** -24 * max(1.0, float(np.abs(r).max())))
 
 
 @pytest.mark.parametrize("F,hop", [(1024, 64), (1024, 256), (1024, 512), (2048, 128), (2048, 512), (2048, 1024)])
