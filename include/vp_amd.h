@@ -354,6 +354,23 @@ int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d_out, const
 /* pow(2, st / 12) exactly as vp_stft_pitch_shift / vp_pv_set_semitones compute it (same bits).
  * VP_ERR_INVALID_ARG if an entry is outside +-12 or not finite; nothing is written then.  Host arrays; no device is touched. */
 int vp_semitones_to_ratios(const double *semitones, double *ratios, long n);
+/* Time stretch (kernels vp_k_stft_pv_stretch and vp_k_stft_pv2k_stretch): vp_stft_pitch_shift with the frames ANALYSED at caller-given
+ * positions.  The handle's n_samples is the OUTPUT row length T; frame f of stream s is read at input sample
+ * q = clamp(d_pos[s][f], 0, n_in - frame_len) and overlap-added at output sample f hop, so duration and pitch are independent.  The
+ * definition is tests/pv_stretch_reference.py: stft_roundtrip's stage with the unwrap taking the frame's own analysis advance
+ * D_0 = hop, D_f = clamp(q_f - q_(f-1), 1, frame_len) -- d = (p - p_prev) / 2 pi - (k D) / frame_len, wrapped to [-1/2, 1/2] turns, true
+ * frequency k + d (frame_len / D) -- and the synthesis increment unchanged (the synthesis hop is hop).  Any table is defined and gives a
+ * finite output; the table d_pos[s][f] = f hop with n_in = T gives vp_stft_pitch_shift's bits.  Both frame lengths, every hop, always
+ * double, one workgroup per stream, no allocation.
+ * d_in: device float [n_streams][n_in]; d_pos: device int [n_streams][vp_stft_num_frames(p)]; d_out: device float [n_streams][T];
+ * semitones in [-12, 12], 0 = pure stretch.  The table is read when the kernel runs: keep it unchanged until then.
+ * VP_ERR_INVALID_ARG for null pointers, n_in < frame_len or |semitones| > 12 (checked before the device is touched), VP_ERR_HIP when the
+ * device refused the kernels' LDS size at create. */
+int vp_stft_time_stretch(vp_stft *p, const float *d_in, int n_in, const int *d_pos, float *d_out, double semitones, void *hip_stream);
+/* A constant stretch's table: pos[f] = min(floor(f hop / stretch), n_in - frame_len), f < n_frames; stretch = output duration / input
+ * duration in [0.25, 4].  VP_ERR_INVALID_ARG outside that range, for a stretch that is not finite, n_in < frame_len or hop <= 0; nothing
+ * is written then.  Host array; no device is touched. */
+int vp_stretch_positions(int *pos, int n_frames, int hop, double stretch, int n_in, int frame_len);
 int vp_stft_is_fused(const vp_stft *p);                      /* 1 (every handle runs the fused kernel; kept for older callers) */
 /* Diagnostic: cut every stream into this many runs of frames (one workgroup each) instead of choosing from the batch size
  * (0 = automatic).  The output does not depend on it (tests). */

@@ -3,12 +3,18 @@
 
     [VP_AMD_LIB=...] python tools/pv_bench.py
     [VP_AMD_LIB=...] python tools/pv_bench.py --curve [--reps 7] [--out profiles/pv_curve_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --stretch [--reps 7] [--out profiles/pv_stretch_bench.txt]
 
 --curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
 "steps" curve, fixed, ...): 256 streams x 65 536 samples at 1024 points / hop 256 and 2048 points / hop 512 (vp_stft_pitch_shift against
 vp_stft_pitch_shift_curve), then streaming, 16 blocks of 1024 per call, plain against curve.  Every repetition is a window of calls that
 ends in a device synchronise; mean, min and max of the repetitions' rates are printed, and the constant curve's mean over the fixed
 interval's from the same run.
+
+--stretch: the time-stretch builds (vp_stft_time_stretch) beside their fixed-grid parents, in the same process and the same alternation:
+256 streams, 65 536 output samples, 1024 points / hop 256 and 2048 points / hop 512; the parent at +7 semitones, then the stretch kernel at
++7 with the tables of stretch 1 (the identity table f hop: the parent's work), 0.5 and 2.  The identity table's mean over the parent's
+from the same run is the comparison; the kernels' resource listings follow.
 """
 import argparse
 import os
@@ -100,20 +106,61 @@ def curve_legs(reps, emit):
     ps.close()
 
 
+def stretch_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import StftRoundTrip, stretch_positions
+    S, T = 256, 65536
+    parent = "fixed +7 (parent kernel)"
+    for F, hop in ((1024, 256), (2048, 512)):
+        st = StftRoundTrip(S, T, F, hop)
+        nF = st.n_frames
+        y = torch.empty(S, T, device="cuda", dtype=torch.float32)
+        legs = {}
+        for a in (1.0, 0.5, 2.0):
+            n_in = T if a == 1.0 else int(T / a) + F                        # (stretch 1: the parent's input, row for row)
+            x = torch.randn(S, n_in, device="cuda", dtype=torch.float32) * 0.1
+            pos = torch.from_numpy(np.tile(stretch_positions(nF, hop, a, n_in, F), (S, 1))).cuda()
+            if a == 1.0:
+                assert np.array_equal(pos[0].cpu().numpy(), np.arange(nF) * hop)
+                legs[parent] = lambda x=x: st.pitch_shift(x, y, 7.0)
+            legs[f"stretch {a:g}, +7" + (" (identity table)" if a == 1.0 else "")] = lambda x=x, pos=pos: st.time_stretch(x, y, d_pos=pos, semitones=7.0)
+        report(f"time stretch, {S} streams x {T} output samples, F = {F}, hop = {hop}", alternate(legs, reps, 100), S * nF, parent, emit)
+        st.close()
+
+
+def resource_listing(emit):
+    try:
+        import kernel_resources
+        from vocoderproject_amd import processor
+        res = kernel_resources.kernel_resources(processor.LIB_PATH)
+    except Exception as e:                                                  # (no llvm tools next to the runtime)
+        emit(f"kernel resources: not available ({type(e).__name__})")
+        return
+    emit("kernel resources (tools/kernel_resources.py):")
+    for k in ("vp_k_stft_fused<true, false>", "vp_k_stft_pv_stretch", "vp_k_stft_pv2k", "vp_k_stft_pv2k_stretch"):
+        emit(f"  {k:<30s} {res.get(k)}")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--curve", action="store_true", help="the ratio-curve legs instead of the fixed intervals")
+    ap.add_argument("--stretch", action="store_true", help="the time-stretch legs instead of the fixed intervals")
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None, help="--curve: also write the report to this file")
+    ap.add_argument("--out", default=None, help="--curve / --stretch: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve:
+    if not a.curve and not a.stretch:
         return fixed_intervals()
     lines = []
 
     def emit(s):
         print(s, flush=True)
         lines.append(s)
-    curve_legs(max(5, a.reps), emit)
+    if a.curve:
+        curve_legs(max(5, a.reps), emit)
+    if a.stretch:
+        stretch_legs(max(5, a.reps), emit)
+        resource_listing(emit)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

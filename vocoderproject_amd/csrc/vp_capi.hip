@@ -1875,7 +1875,7 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     // (hipFuncSetAttribute acts on the current device).  Only vp_stft_pitch_shift needs it, so a failure is remembered and fails
     // THAT call; the plain and single-precision round trips (<= 64 KB) are served regardless.  The sticky HIP error is cleared so
     // that a later hipGetLastError() behind a launch does not report this one.
-    p->pvOk = vp_stft_prepare_device() == hipSuccess && vp_stft_curve_prepare_device() == hipSuccess;
+    p->pvOk = vp_stft_prepare_device() == hipSuccess && vp_stft_curve_prepare_device() == hipSuccess && vp_stft_stretch_prepare_device() == hipSuccess;
     if (!p->pvOk) (void)hipGetLastError();
     p->device = device; p->F = frame_len; p->hop = hop; p->S = n_streams; p->T = n_samples;
     p->nFrames = (n_samples - frame_len) / hop + 1;
@@ -1945,8 +1945,10 @@ extern "C" int vp_stft_set_precision(vp_stft *p, int precision)
 }
 extern "C" int vp_stft_get_precision(const vp_stft *p) { return p ? (p->f32 ? VP_STFT_F32 : VP_STFT_F64) : VP_ERR_INVALID_ARG; }
 
-// (d_ratio: the phase-vocoder stage reads its ratio per frame from this table, `ratio` is unused then)
-static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag, hipStream_t st, bool pv, double ratio, const double *d_ratio = nullptr)
+// (d_ratio: the phase-vocoder stage reads its ratio per frame from this table, `ratio` is unused then; d_pos: it reads frame f at input
+// sample d_pos[s][f] of rows of n_in samples -- the time stretch)
+static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag, hipStream_t st, bool pv, double ratio, const double *d_ratio = nullptr,
+                      const int *d_pos = nullptr, int n_in = 0)
 {
     VpStftArgs a;
     memset(&a, 0, sizeof a);
@@ -1972,6 +1974,7 @@ static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
     a.roundsPerRun = (a.nRounds + runs - 1) / runs;
     const int nRuns = (a.nRounds + a.roundsPerRun - 1) / a.roundsPerRun;
     if (d_ratio) return vp_stft_launch_curve(a, d_ratio, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
+    if (d_pos) return vp_stft_launch_stretch(a, d_pos, n_in, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     return vp_stft_launch(a, p->S, nRuns, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
 }
 
@@ -1999,6 +2002,24 @@ extern "C" int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d
     if (!p->pvOk) return VP_ERR_HIP;                           // (as vp_stft_pitch_shift)
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio);
+}
+
+// the time stretch: frame f of stream s is read at input sample d_pos[s][f] (clamped by the kernel) of d_in [S][n_in] and written at output
+// sample f hop of d_out [S][T] (vp_k_stft_pv_stretch / vp_k_stft_pv2k_stretch), with the pitch shift of `semitones` on top
+extern "C" int vp_stft_time_stretch(vp_stft *p, const float *d_in, int n_in, const int *d_pos, float *d_out, double semitones, void *hip_stream)
+{
+    if (!p || !d_in || !d_pos || !d_out || n_in < p->F || !(semitones >= -12.0 && semitones <= 12.0)) return VP_ERR_INVALID_ARG;
+    if (!p->pvOk) return VP_ERR_HIP;                           // (as vp_stft_pitch_shift)
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, std::pow(2.0, semitones / 12.0), nullptr, d_pos, n_in);
+}
+
+extern "C" int vp_stretch_positions(int *pos, int n_frames, int hop, double stretch, int n_in, int frame_len)
+{
+    if (!pos || n_frames < 0 || hop <= 0 || frame_len <= 0 || n_in < frame_len || !(stretch >= 0.25 && stretch <= 4.0)) return VP_ERR_INVALID_ARG;   // (a NaN fails both tests)
+    const long long last = (long long)n_in - frame_len;
+    for (int f = 0; f < n_frames; f++) pos[f] = (int)std::min((long long)std::floor((double)((long long)f * hop) / stretch), last);
+    return VP_OK;
 }
 
 extern "C" int vp_semitones_to_ratios(const double *semitones, double *ratios, long n)

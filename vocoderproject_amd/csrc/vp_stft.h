@@ -37,6 +37,12 @@ hipError_t vp_stft_prepare_device();
 // a.F; csrc/vp_stft_curve.inc): one workgroup per stream, a.roundsPerRun = a.nRounds; and their dynamic-LDS ceiling, as above
 hipError_t vp_stft_launch_curve(const VpStftArgs &a, const double *d_ratio, int nStreams, hipStream_t st);
 hipError_t vp_stft_curve_prepare_device();
+// the phase-vocoder builds that read frame f of stream s at input sample d_pos[s][f] (int32 [nStreams][nFrames], clamped to [0, nIn - F])
+// of an input row of nIn samples and write it at output sample f hop of a row of a.T samples (vp_k_stft_pv_stretch /
+// vp_k_stft_pv2k_stretch, by a.F; csrc/vp_stft_stretch.inc): one workgroup per stream, a.roundsPerRun = a.nRounds, a.aligned unused; and
+// their dynamic-LDS ceiling, as above
+hipError_t vp_stft_launch_stretch(const VpStftArgs &a, const int *d_pos, int nIn, int nStreams, hipStream_t st);
+hipError_t vp_stft_stretch_prepare_device();
 
 // ---- streaming phase vocoder (vp_pv_*): one workgroup per stream and call, state in HBM between calls -----------------------------
 #define VP_PV_MAX_UPDATES 16            // interval changes / resets carried in a process call's arguments

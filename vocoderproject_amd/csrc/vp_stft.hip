@@ -1109,3 +1109,6 @@ hipError_t vp_pv_launch(const VpPvArgs &a, hipStream_t st)
 
 // ---- the phase-vocoder kernels along a per-frame / per-block ratio curve (vp_stft_pitch_shift_curve, vp_pv_process_blocks_curve_device) ----
 #include "vp_stft_curve.inc"
+
+// ---- the phase-vocoder kernels with frames analysed at caller-given positions: time stretch (vp_stft_time_stretch) ----
+#include "vp_stft_stretch.inc"

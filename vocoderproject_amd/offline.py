@@ -14,6 +14,7 @@ There is no CPU path here either: without a GPU the processor raises.
     python -m vocoderproject_amd.offline vocode voice.wav --carrier synth.wav --out-dir out/
     python -m vocoderproject_amd.offline pvshift a.wav b.wav --shift 7 --out-dir out/     (streaming phase vocoder)
     python -m vocoderproject_amd.offline pvshift a.wav --glide -12:12 --out-dir out/      (... along a glide, one interval per block)
+    python -m vocoderproject_amd.offline stretch a.wav b.wav --stretch 1.5 [--shift 3] --out-dir out/   (time stretch, one-shot phase vocoder)
 """
 import argparse
 import os
@@ -236,11 +237,68 @@ def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, 
     return [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
 
 
+class _StretchRunner:
+    """StftRoundTrip.time_stretch from host arrays: x float32 [S][n_in], pos int32 [S][n_frames] -> float32 [S][T]."""
+
+    def __init__(self, F, hop, device):
+        self.F, self.hop, self.device = int(F), int(hop), device
+
+    def run(self, x, pos, T, semitones):
+        import torch
+        from . import StftRoundTrip
+        dev = torch.device("cuda", self.device)
+        st = StftRoundTrip(x.shape[0], int(T), self.F, self.hop, device=self.device)
+        try:
+            d_in = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
+            d_out = torch.empty((x.shape[0], int(T)), dtype=torch.float32, device=dev)
+            st.time_stretch(d_in, d_out, positions=pos, semitones=float(semitones))
+            torch.cuda.synchronize(dev)
+            return d_out.cpu().numpy()
+        finally:
+            st.close()
+
+
+def pv_stretch(voices, stretch, shift=0.0, F=1024, hop=256, device=0, processor=None):
+    """A batch of recordings through the one-shot phase vocoder's time stretch (StftRoundTrip.time_stretch: one stream per recording).
+    stretch: output duration / input duration in [0.25, 4], one value or one per recording; shift: the pitch shift on top, semitones.
+    The recordings are padded to a common input length, each has its own position table (pos[f] = floor(f hop / stretch), held at its
+    own last frame), the outputs share one length and each is trimmed to ceil(len stretch) samples.  Returns float32 [2][ceil(len
+    stretch)] per recording (the signal on both channels).  `processor` (tests): an object with run(x, pos, T, semitones) to use instead
+    of the GPU."""
+    S = len(voices)
+    if S == 0:
+        raise ValueError("no recordings")
+    per = [float(v) for v in stretch] if isinstance(stretch, (list, tuple, np.ndarray)) else [float(stretch)] * S
+    if len(per) != S:
+        raise ValueError("stretch: one value per recording expected")
+    if not all(0.25 <= v <= 4.0 for v in per):
+        raise ValueError("stretch: factors within [0.25, 4] expected")
+    if not -12.0 <= float(shift) <= 12.0:
+        raise ValueError("shift: an interval within +-12 semitones expected")
+    F, hop = int(F), int(hop)
+    lens = [int(np.asarray(v).shape[-1]) for v in voices]
+    outs = [int(np.ceil(n * a)) for n, a in zip(lens, per)]
+    n_in = max(max(lens), F)
+    x = np.zeros((S, n_in), np.float32)
+    for s, v in enumerate(voices):
+        v = np.asarray(v, np.float32)
+        if v.ndim != 1:
+            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
+        x[s, :lens[s]] = v
+    T = F + -(-max(outs) // hop) * hop                                         # every output sample under the full overlap of frames
+    nF = (T - F) // hop + 1
+    # (the formula of vp_stretch_positions, against each recording's own length: behind its end a recording repeats its last frame)
+    pos = np.stack([np.minimum(np.floor(np.arange(nF, dtype=np.int64) * hop / a), max(n, F) - F) for n, a in zip(lens, per)]).astype(np.int32)
+    p = processor if processor is not None else _StretchRunner(F, hop, device)
+    y = p.run(x, pos, T, float(shift))
+    return [np.ascontiguousarray(np.stack([y[s, :outs[s]]] * 2)) for s in range(S)]
+
+
 # ---- command line ---------------------------------------------------------------------------------------------------------
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m vocoderproject_amd.offline", description=__doc__.split("\n\n")[0])
-    ap.add_argument("flow", choices=["pitch", "vocode", "both", "pvshift"])
+    ap.add_argument("flow", choices=["pitch", "vocode", "both", "pvshift", "stretch"])
     ap.add_argument("inputs", nargs="+", help="voice recordings (WAV; channel 0 is used, like the notebook)")
     ap.add_argument("--carrier", action="append", default=None,
                     help="side-chain recording(s) for vocode/both: one for all voices or one per voice")
@@ -249,6 +307,8 @@ def main(argv=None):
     ap.add_argument("--shift", type=float, default=None, help="fixed interval in semitones instead of the key correction")
     ap.add_argument("--glide", default=None, metavar="A:B",
                     help="pvshift: a linear glide from A to B semitones over each recording, one value per block, instead of --shift")
+    ap.add_argument("--stretch", type=float, default=None, help="stretch: output duration / input duration, 0.25 to 4 (--shift: semitones on top)")
+    ap.add_argument("--frame", type=int, default=1024, help="stretch: frame length (1024 or 2048)")
     ap.add_argument("--lpc-voice", type=int, default=40)
     ap.add_argument("--lpc-synth", type=int, default=5)
     ap.add_argument("--block", type=int, default=1024)
@@ -268,6 +328,14 @@ def main(argv=None):
     if any(r[0] != fs for r in recs):
         raise SystemExit("all recordings of a batch must share one sample rate (one prepareToPlay)")
     voices = [r[1][0] for r in recs]
+    if a.flow == "stretch":
+        if a.stretch is None:
+            raise SystemExit("stretch needs --stretch FACTOR")
+        try:
+            outs = pv_stretch(voices, a.stretch, shift=0.0 if a.shift is None else a.shift, F=a.frame, hop=a.hop, device=a.device)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        return _write_outputs(a, fs, outs)
     if a.flow == "pvshift":
         if (a.shift is None) == (a.glide is None):
             raise SystemExit("pvshift needs --shift or --glide A:B")

@@ -135,6 +135,9 @@ def load_library():
         L.vp_stft_pitch_shift_curve.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p]
         L.vp_semitones_to_ratios.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
         L.vp_pv_process_blocks_curve_device.argtypes = [vp, fp, fp, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "vp_stft_time_stretch"):             # (the time stretch; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_stft_time_stretch.argtypes = [vp, fp, C.c_int, C.c_void_p, fp, C.c_double, C.c_void_p]
+        L.vp_stretch_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]
     L.vp_stft_set_runs.argtypes = [vp, C.c_int]
     L.vp_stft_set_precision.argtypes = [vp, C.c_int]
     L.vp_stft_get_precision.argtypes = [vp]
@@ -495,6 +498,18 @@ def semitones_to_ratios(semitones):
     return r
 
 
+def stretch_positions(n_frames, hop, stretch, n_in, frame_len=1024):
+    """The position table of a constant time stretch, int32 [n_frames] through the library's vp_stretch_positions:
+    pos[f] = min(floor(f hop / stretch), n_in - frame_len), stretch = output duration / input duration in [0.25, 4].  VpError outside
+    that range or for a stretch that is not finite.  No device is touched."""
+    L = load_library()
+    pos = np.empty(int(n_frames), dtype=np.int32)
+    rc = L.vp_stretch_positions(pos.ctypes.data, int(n_frames), int(hop), float(stretch), int(n_in), int(frame_len))
+    if rc:
+        raise VpError(rc, L.vp_error_string(rc).decode())
+    return pos
+
+
 def _upload_ratios(tables, semitones, dev):
     """The ratios of a table of intervals (already in the kernel's layout) in a device table of that shape, allocated once per shape in
     the caller's `tables`; the copy goes on torch's current stream."""
@@ -584,6 +599,45 @@ class StftRoundTrip:
         if stream is None:
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
         rc = self.L.vp_stft_pitch_shift_curve(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), C.c_void_p(stream))
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+
+    def time_stretch(self, d_in, d_out, positions=None, stretch=None, semitones=0.0, stream=None, d_pos=None):
+        """Time stretch (vp_stft_time_stretch): pitch_shift with frame f of stream s analysed at input sample positions[s][f] and written
+        at output sample f hop, so duration and pitch are independent.  d_in is float32 [S][n_in] with any n_in >= frame_len, d_out
+        [S][n_samples] (the handle's length is the OUTPUT's).  One of
+          positions: array-like int [n_frames] (every stream follows it) or [S][n_frames];
+          stretch:   output duration / input duration in [0.25, 4], a scalar or [S] -- tables through stretch_positions;
+          d_pos:     a device int32 tensor [S][n_frames], used as it is.
+        The kernel clamps positions to [0, n_in - frame_len]; any table gives a finite output.  positions and stretch are uploaded into a
+        device table the handle allocates once per shape (on torch's current stream: with another `stream`, order it behind that one).
+        semitones (|value| <= 12): the pitch shift on top, 0 = pure stretch.  Always double precision; every call starts from zero phase
+        state."""
+        import torch
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and d_in.dim() == 2 and d_in.shape[0] == self.S and d_in.is_contiguous()
+        assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
+        n_in = int(d_in.shape[1])
+        assert n_in >= self.F, n_in
+        assert (positions is not None) + (stretch is not None) + (d_pos is not None) == 1, "one of positions, stretch and d_pos"
+        if d_pos is None:
+            if stretch is not None:
+                a = np.broadcast_to(np.asarray(stretch, dtype=np.float64).reshape(-1), (self.S,))
+                pos = np.stack([stretch_positions(self.n_frames, self.hop, v, n_in, self.F) for v in a])
+            else:
+                pos = np.asarray(positions)
+                assert pos.dtype.kind in "iu" and pos.shape in ((self.n_frames,), (self.S, self.n_frames)), (pos.dtype, pos.shape)
+                pos = np.clip(np.broadcast_to(pos, (self.S, self.n_frames)), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
+            if not hasattr(self, "_stretch_tables"):
+                self._stretch_tables = {}
+            tab = self._stretch_tables.get(pos.shape)
+            if tab is None:
+                tab = self._stretch_tables[pos.shape] = torch.empty(pos.shape, dtype=torch.int32, device=d_in.device)
+            tab.copy_(torch.from_numpy(np.ascontiguousarray(pos)))
+            d_pos = tab
+        assert d_pos.is_cuda and d_pos.dtype == torch.int32 and tuple(d_pos.shape) == (self.S, self.n_frames) and d_pos.is_contiguous()
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        rc = self.L.vp_stft_time_stretch(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), float(semitones), C.c_void_p(stream))
         if rc:
             raise VpError(rc, self.L.vp_error_string(rc).decode())
 
