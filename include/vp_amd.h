@@ -371,6 +371,31 @@ int vp_stft_time_stretch(vp_stft *p, const float *d_in, int n_in, const int *d_p
  * duration in [0.25, 4].  VP_ERR_INVALID_ARG outside that range, for a stretch that is not finite, n_in < frame_len or hop <= 0; nothing
  * is written then.  Host array; no device is touched. */
 int vp_stretch_positions(int *pos, int n_frames, int hop, double stretch, int n_in, int frame_len);
+/* Pitch tracker and automatic correction (kernel vp_k_yin_track, csrc/vp_track.hip): PitchProcess's own decision -- YIN, the key's
+ * nearest note, beta = closestFreq / pitch, with the plugin's numbers fMin 100, fMax 800, yinTol 0.25 and the Notes tables -- for every
+ * frame of the handle at once, one wavefront per frame.  The definition is tests/pv_track_reference.py, and the result equals it
+ * bit for bit (period and ratio; no tolerance):
+ *   tauMax = ceil(fs / 100), tau0 = floor(fs / 800); 8000 <= sample_rate <= 51200 (tauMax <= 512) and n_samples >= frame_len + tauMax;
+ *   frame f reads the frame_len + tauMax samples from b = min(f hop, n_samples - (frame_len + tauMax)) on -- the last frames of a row share a
+ *   clamped window, no frame reads outside its row;
+ *   d[k] = sum_{i < frame_len} (x[b + i] - x[b + i + k])^2 in double, each its own left-to-right sum; d[0] = 1, then tmp += d[k],
+ *   d[k] *= k / tmp in increasing k; d[tauMax] = 0; the threshold walk of PitchProcess.cpp:429-447 gives the period, or 0 (unvoiced);
+ *   period > 0: pitch = fs / period, ratio = closest(pitch, key) / pitch; period 0: ratio = 1.0 exactly.
+ * Frames are independent: no gate, no hold of the last voiced ratio, no smoothing.  Float32-denormal input samples are outside the
+ * definition's domain (the kernels widen them to 0).
+ * d_in: device float [n_streams][n_samples]; d_key: device int [n_streams], Notes::key 0..12 (12 = chromatic; any other value counts
+ * as 12), or NULL = chromatic everywhere; d_period: device int [n_streams][vp_stft_num_frames(p)] or NULL; d_ratio: device double of
+ * that shape or NULL; not both NULL.  No allocation, no synchronisation.
+ * VP_ERR_INVALID_ARG (null handle or input, both outputs NULL, sample rate out of range) and VP_ERR_GEOMETRY (rows shorter than
+ * frame_len + tauMax) are reported before the device is touched; vp_stft_last_error says which. */
+int vp_track_tau_max(double sample_rate);                    /* ceil(sample_rate / 100), or VP_ERR_INVALID_ARG outside 8000 .. 51200 */
+int vp_stft_track_pitch(vp_stft *p, const float *d_in, double sample_rate, const int *d_key, int *d_period, double *d_ratio, void *hip_stream);
+/* vp_stft_track_pitch followed by vp_stft_pitch_shift_curve along its table, on the same stream: the output has the bits of those two
+ * calls.  d_ratio is required (result and scratch), d_period optional.  Both frame lengths, every hop.  Errors as the two calls'. */
+int vp_stft_autotune(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int *d_period, double *d_ratio,
+                     void *hip_stream);
+/* The message of the last tracker / autotune call that failed on this handle ("" before any; the pointer is valid until the next call). */
+const char *vp_stft_last_error(const vp_stft *p);
 int vp_stft_is_fused(const vp_stft *p);                      /* 1 (every handle runs the fused kernel; kept for older callers) */
 /* Diagnostic: cut every stream into this many runs of frames (one workgroup each) instead of choosing from the batch size
  * (0 = automatic).  The output does not depend on it (tests). */

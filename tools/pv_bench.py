@@ -4,6 +4,7 @@
     [VP_AMD_LIB=...] python tools/pv_bench.py
     [VP_AMD_LIB=...] python tools/pv_bench.py --curve [--reps 7] [--out profiles/pv_curve_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --stretch [--reps 7] [--out profiles/pv_stretch_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --track [--reps 7] [--out profiles/pv_track_bench.txt]
 
 --curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
 "steps" curve, fixed, ...): 256 streams x 65 536 samples at 1024 points / hop 256 and 2048 points / hop 512 (vp_stft_pitch_shift against
@@ -15,6 +16,11 @@ interval's from the same run.
 256 streams, 65 536 output samples, 1024 points / hop 256 and 2048 points / hop 512; the parent at +7 semitones, then the stretch kernel at
 +7 with the tables of stretch 1 (the identity table f hop: the parent's work), 0.5 and 2.  The identity table's mean over the parent's
 from the same run is the comparison; the kernels' resource listings follow.
+
+--track: the pitch tracker (vp_stft_track_pitch, kernel vp_k_yin_track), vp_stft_pitch_shift_curve alone on the tracker's table and
+vp_stft_autotune (the two on one stream), alternating in one process: 256 streams x 65 536 samples of voiced signals (a harmonic tone with
+vibrato per stream, every fourth stream noise) at 44.1 kHz, 1024 points / hop 256 and 2048 points / hop 512.  Printed: each leg's frames/s,
+the tracker's beside the curve kernel's, and autotune's time per call against the sum of its parts'.
 """
 import argparse
 import os
@@ -129,7 +135,45 @@ def stretch_legs(reps, emit):
         st.close()
 
 
-def resource_listing(emit):
+def track_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import StftRoundTrip
+    S, T, fs = 256, 65536, 44100.0
+    rng = np.random.default_rng(11)
+    t = np.arange(T) / fs
+    rows = []
+    for s in range(S):
+        if s % 4 == 3:
+            rows.append(0.1 * rng.standard_normal(T))
+            continue
+        f0 = rng.uniform(110.0, 440.0) * 2.0 ** (0.3 / 12.0 * np.sin(2.0 * np.pi * rng.uniform(3.0, 7.0) * t))
+        ph = 2.0 * np.pi * np.cumsum(f0) / fs
+        rows.append(0.3 * np.sin(ph) + 0.15 * np.sin(2.0 * ph + 1.0) + 0.08 * np.sin(3.0 * ph + 2.0))
+    x = torch.from_numpy(np.stack(rows).astype(np.float32)).cuda()
+    y = torch.empty_like(x)
+    keys = torch.from_numpy((np.arange(S) % 13).astype(np.int32)).cuda()
+    for F, hop in ((1024, 256), (2048, 512)):
+        st = StftRoundTrip(S, T, F, hop)
+        nF = st.n_frames
+        period, table = st.track_pitch(x, fs, keys=keys)
+        torch.cuda.synchronize()
+        voiced = float((period > 0).float().mean())
+        legs = {"tracker": lambda: st.track_pitch(x, fs, keys=keys),
+                "curve on the tracker's table": lambda: st.pitch_shift_curve(x, y, d_ratio=table),
+                "autotune": lambda: st.autotune(x, y, fs, keys=keys)}
+        times = alternate(legs, reps, 20)
+        report(f"pitch tracker, {S} streams x {T} samples at {fs:g} Hz, F = {F}, hop = {hop}, {100.0 * voiced:.0f} % of the frames voiced",
+               times, S * nF, "curve on the tracker's table", emit)
+        mean = {k: sum(v) / len(v) for k, v in times.items()}
+        curve = mean["curve on the tracker's table"]
+        parts = mean["tracker"] + curve
+        emit(f"  per call: tracker {mean['tracker'] * 1e3:.3f} ms + curve {curve * 1e3:.3f} ms = {parts * 1e3:.3f} ms; "
+             f"autotune {mean['autotune'] * 1e3:.3f} ms = {mean['autotune'] / parts:.3f} x the sum")
+        st.close()
+
+
+def resource_listing(emit, kernels=("vp_k_stft_fused<true, false>", "vp_k_stft_pv_stretch", "vp_k_stft_pv2k", "vp_k_stft_pv2k_stretch")):
     try:
         import kernel_resources
         from vocoderproject_amd import processor
@@ -138,7 +182,7 @@ def resource_listing(emit):
         emit(f"kernel resources: not available ({type(e).__name__})")
         return
     emit("kernel resources (tools/kernel_resources.py):")
-    for k in ("vp_k_stft_fused<true, false>", "vp_k_stft_pv_stretch", "vp_k_stft_pv2k", "vp_k_stft_pv2k_stretch"):
+    for k in kernels:
         emit(f"  {k:<30s} {res.get(k)}")
 
 
@@ -146,10 +190,11 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--curve", action="store_true", help="the ratio-curve legs instead of the fixed intervals")
     ap.add_argument("--stretch", action="store_true", help="the time-stretch legs instead of the fixed intervals")
+    ap.add_argument("--track", action="store_true", help="the pitch-tracker legs instead of the fixed intervals")
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None, help="--curve / --stretch: also write the report to this file")
+    ap.add_argument("--out", default=None, help="--curve / --stretch / --track: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve and not a.stretch:
+    if not a.curve and not a.stretch and not a.track:
         return fixed_intervals()
     lines = []
 
@@ -161,6 +206,9 @@ def main():
     if a.stretch:
         stretch_legs(max(5, a.reps), emit)
         resource_listing(emit)
+    if a.track:
+        track_legs(max(5, a.reps), emit)
+        resource_listing(emit, ("vp_k_yin_track", "vp_k_stft_pv_curve", "vp_k_stft_pv2k_curve"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

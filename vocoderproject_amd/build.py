@@ -19,9 +19,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libvp_amd.so")
-SOURCES = ["vp_kernels.hip", "vp_voc2.hip", "vp_stft.hip", "vp_channels.hip", "vp_capi.hip"]
+SOURCES = ["vp_kernels.hip", "vp_voc2.hip", "vp_stft.hip", "vp_channels.hip", "vp_track.hip", "vp_capi.hip"]
 PARTS = ["vp_fft.inc", "vp_filters.inc", "vp_vocoder_wg.inc", "vp_pitch.inc", "vp_pitch_ws.inc", "vp_pitch_ws_body.inc"]      # included by vp_kernels.hip
-DEPS = SOURCES + PARTS + ["vp_common.h", "vp_kernels.h", "vp_voc2.h", "vp_stft.h", "vp_fft32.inc", "vp_channels.h", "vp_stft_curve.inc", "vp_stft_stretch.inc"]
+DEPS = SOURCES + PARTS + ["vp_common.h", "vp_kernels.h", "vp_voc2.h", "vp_stft.h", "vp_fft32.inc", "vp_channels.h", "vp_stft_curve.inc", "vp_stft_stretch.inc", "vp_track.h"]
 ARCH = "gfx950"
 NUM_TUS = 9          # groups of kernels in vp_kernels.hip (VP_TU)
 
@@ -127,6 +127,8 @@ def build(force=False, verbose=False, stamps=False, poison=False):
         # (VP_STFT_EXTRA_FLAGS: experiment builds, tools/ab.sh)
         jobs.append((os.path.join(CSRC, "vp_stft.hip"), os.path.join(tmp, "stft.o"), os.environ.get("VP_STFT_EXTRA_FLAGS", "-fno-slp-vectorize -ffp-contract=fast").split()))
         jobs.append((os.path.join(CSRC, "vp_channels.hip"), os.path.join(tmp, "channels.o"), []))   # pointer table <-> packed slab (self-contained)
+        # the pitch tracker of the phase-vocoder path (self-contained): the default flags, -ffp-contract=off is what makes its sums the oracle's
+        jobs.append((os.path.join(CSRC, "vp_track.hip"), os.path.join(tmp, "track.o"), []))
         jobs.append((os.path.join(CSRC, "vp_capi.hip"), os.path.join(tmp, "capi.o"), []))
 
         def compile_one(job):
@@ -138,7 +140,8 @@ def build(force=False, verbose=False, stamps=False, poison=False):
             deps = {"vp_kernels.hip": ["vp_kernels.hip", "vp_common.h"] + PARTS,
                     "vp_voc2.hip": ["vp_voc2.hip", "vp_voc2.h", "vp_kernels.hip", "vp_common.h"] + PARTS,
                     "vp_stft.hip": ["vp_stft.hip", "vp_stft.h", "vp_fft.inc", "vp_fft32.inc", "vp_stft_curve.inc", "vp_stft_stretch.inc"],
-                    "vp_channels.hip": ["vp_channels.hip", "vp_channels.h"]}.get(os.path.basename(src))
+                    "vp_channels.hip": ["vp_channels.hip", "vp_channels.h"],
+                    "vp_track.hip": ["vp_track.hip", "vp_track.h", "vp_common.h"]}.get(os.path.basename(src))
             if deps is None:
                 deps = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.basename(src), os.path.join(ROOT, "include", "vp_amd.h")]
             for dep in deps:

@@ -23,6 +23,7 @@
 #include "vp_voc2.h"
 #include "vp_stft.h"
 #include "vp_channels.h"
+#include "vp_track.h"
 
 struct vp_handle {
     int device = 0;
@@ -1851,6 +1852,9 @@ struct vp_stft {
     bool pvOk = false;                // the phase-vocoder builds' dynamic-LDS ceiling could be raised on this device (vp_stft_pitch_shift needs it)
     int runsPerStream = 0;            // 0: chosen from the batch so that the grid fills the chip; > 0: vp_stft_set_runs (tests)
     int f32 = 0;                      // vp_stft_set_precision
+    double *notes = nullptr;          // [13][VP_NOTES_STRIDE] the Notes tables of the pitch tracker (vp_stft_track_pitch), fMin 100 / fMax 800
+    int *notesN = nullptr;            // [13]
+    std::string lastError;            // vp_stft_last_error
 };
 
 static float stft_host_tables(int frame_len, int hop, std::vector<double> &w, std::vector<double> &t1, std::vector<double> &t2,
@@ -1859,6 +1863,7 @@ static float stft_host_tables(int frame_len, int hop, std::vector<double> &w, st
 static void stft_free(vp_stft *p)
 {
     (void)hipFree(p->win); (void)hipFree(p->tw1); (void)hipFree(p->tw2); (void)hipFree(p->tws); (void)hipFree(p->twTop);
+    (void)hipFree(p->notes); (void)hipFree(p->notesN);
 }
 
 extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int frame_len, int hop, vp_stft **out)
@@ -1885,6 +1890,13 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
         return hipMalloc(d, v.size() * 8) == hipSuccess && hipMemcpy(*d, v.data(), v.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
     };
     if (!(up(&p->win, w) && up(&p->tw1, t1) && up(&p->tw2, t2) && up(&p->tws, ts) && (frame_len != 2048 || up(&p->twTop, tt)))) { stft_free(p); delete p; return VP_ERR_OOM; }
+    // the pitch tracker's note tables, one per key (PluginProcessor.cpp:148: fMin 100, fMax 800), here so that its calls allocate nothing
+    std::vector<double> notes(13 * VP_NOTES_STRIDE, 0.0);
+    int notesN[13];
+    for (int k = 0; k < 13; k++) notesN[k] = build_notes(k, VP_TRACK_FMIN, VP_TRACK_FMAX, notes.data() + (size_t)k * VP_NOTES_STRIDE);
+    if (!(up(&p->notes, notes) && hipMalloc(&p->notesN, sizeof notesN) == hipSuccess && hipMemcpy(p->notesN, notesN, sizeof notesN, hipMemcpyHostToDevice) == hipSuccess)) {
+        stft_free(p); delete p; return VP_ERR_OOM;
+    }
     *out = p;
     return VP_OK;
 }
@@ -2028,6 +2040,64 @@ extern "C" int vp_semitones_to_ratios(const double *semitones, double *ratios, l
     for (long i = 0; i < n; i++) if (!(semitones[i] >= -12.0 && semitones[i] <= 12.0)) return VP_ERR_INVALID_ARG;   // (a NaN fails both tests)
     for (long i = 0; i < n; i++) ratios[i] = std::pow(2.0, semitones[i] / 12.0);      // (as vp_stft_pitch_shift / vp_pv_set_semitones: the same bits)
     return VP_OK;
+}
+
+// ---- pitch tracker of the phase-vocoder path (csrc/vp_track.hip): YIN per frame, the key's nearest note, one ratio per frame -------
+extern "C" int vp_track_tau_max(double sample_rate)
+{
+    if (!(sample_rate >= 8000.0 && sample_rate <= 51200.0)) return VP_ERR_INVALID_ARG;          // (a NaN fails both tests)
+    return (int)std::ceil(sample_rate / VP_TRACK_FMIN);                                         // PitchProcess.cpp:100
+}
+
+extern "C" const char *vp_stft_last_error(const vp_stft *p) { return p ? p->lastError.c_str() : ""; }
+
+// every argument of a tracker call, checked before the device is touched
+static int track_check(vp_stft *p, const float *d_in, double fs, const int *d_period, const double *d_ratio)
+{
+    if (!p) return VP_ERR_INVALID_ARG;
+    if (!d_in) { p->lastError = "pitch tracker: null input"; return VP_ERR_INVALID_ARG; }
+    if (!d_period && !d_ratio) { p->lastError = "pitch tracker: period and ratio outputs are both null"; return VP_ERR_INVALID_ARG; }
+    const int tauMax = vp_track_tau_max(fs);
+    if (tauMax < 0) { p->lastError = "pitch tracker: sample rate outside 8000 .. 51200 Hz"; return VP_ERR_INVALID_ARG; }
+    if (p->T < p->F + tauMax) {
+        p->lastError = "pitch tracker: rows of " + std::to_string(p->T) + " samples are shorter than frame_len + tauMax = " + std::to_string(p->F + tauMax);
+        return VP_ERR_GEOMETRY;
+    }
+    return VP_OK;
+}
+
+static int track_launch(vp_stft *p, const float *d_in, double fs, const int *d_key, int *d_period, double *d_ratio, hipStream_t st)
+{
+    VpTrackArgs a;
+    memset(&a, 0, sizeof a);
+    a.in = d_in; a.key = d_key; a.period = d_period; a.ratio = d_ratio; a.notes = p->notes; a.notesN = p->notesN;
+    a.fs = fs; a.S = p->S; a.T = p->T; a.F = p->F; a.hop = p->hop; a.nFrames = p->nFrames;
+    a.tauMax = vp_track_tau_max(fs);
+    a.tau0 = (int)std::floor(fs / VP_TRACK_FMAX);                                               // PitchProcess.cpp:429
+    if (vp_track_launch(a, st) != hipSuccess) { p->lastError = "pitch tracker: kernel launch failed"; return VP_ERR_HIP; }
+    return VP_OK;
+}
+
+extern "C" int vp_stft_track_pitch(vp_stft *p, const float *d_in, double sample_rate, const int *d_key, int *d_period, double *d_ratio, void *hip_stream)
+{
+    const int rc = track_check(p, d_in, sample_rate, d_period, d_ratio);
+    if (rc) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return track_launch(p, d_in, sample_rate, d_key, d_period, d_ratio, (hipStream_t)hip_stream);
+}
+
+// the tracker, then vp_stft_pitch_shift_curve along its table, on the same stream
+extern "C" int vp_stft_autotune(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int *d_period, double *d_ratio,
+                                void *hip_stream)
+{
+    if (p && (!d_out || !d_ratio)) { p->lastError = "autotune: null output or ratio table (the table is result and scratch)"; return VP_ERR_INVALID_ARG; }
+    int rc = track_check(p, d_in, sample_rate, d_period, d_ratio);
+    if (rc) return rc;
+    if (!p->pvOk) { p->lastError = "autotune: the device refused the phase-vocoder kernels' LDS size at create"; return VP_ERR_HIP; }   // (as vp_stft_pitch_shift)
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    rc = track_launch(p, d_in, sample_rate, d_key, d_period, d_ratio, (hipStream_t)hip_stream);
+    if (rc) return rc;
+    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio);
 }
 
 // ---- streaming phase vocoder (no reference counterpart): vp_k_pv_stream of vp_stft.hip, the one-shot stage block by block -----------

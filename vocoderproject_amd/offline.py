@@ -15,6 +15,7 @@ There is no CPU path here either: without a GPU the processor raises.
     python -m vocoderproject_amd.offline pvshift a.wav b.wav --shift 7 --out-dir out/     (streaming phase vocoder)
     python -m vocoderproject_amd.offline pvshift a.wav --glide -12:12 --out-dir out/      (... along a glide, one interval per block)
     python -m vocoderproject_amd.offline stretch a.wav b.wav --stretch 1.5 [--shift 3] --out-dir out/   (time stretch, one-shot phase vocoder)
+    python -m vocoderproject_amd.offline pvtune a.wav b.wav --key 0 --out-dir out/ [--track-csv]        (pitch tracker + phase-vocoder correction)
 """
 import argparse
 import os
@@ -294,11 +295,80 @@ def pv_stretch(voices, stretch, shift=0.0, F=1024, hop=256, device=0, processor=
     return [np.ascontiguousarray(np.stack([y[s, :outs[s]]] * 2)) for s in range(S)]
 
 
+class _AutotuneRunner:
+    """StftRoundTrip.autotune from host arrays: x float32 [S][T], keys [S] -> (y float32 [S][T], period int32 [S][nF], ratio float64 [S][nF])."""
+
+    def __init__(self, F, hop, device):
+        self.F, self.hop, self.device = int(F), int(hop), device
+
+    def run(self, x, fs, keys):
+        import torch
+        from . import StftRoundTrip
+        dev = torch.device("cuda", self.device)
+        st = StftRoundTrip(x.shape[0], x.shape[1], self.F, self.hop, device=self.device)
+        try:
+            d_in = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
+            d_out = torch.empty_like(d_in)
+            period, ratio = st.autotune(d_in, d_out, float(fs), keys=[int(k) for k in keys])
+            torch.cuda.synchronize(dev)
+            return d_out.cpu().numpy(), period.cpu().numpy(), ratio.cpu().numpy()
+        finally:
+            st.close()
+
+
+def tune_length(max_len, fs, F, hop):
+    """Common row length of a pvtune batch: every sample of the longest recording under the full overlap of frames, and never shorter than
+    the tracker's window of F + ceil(fs / 100) samples."""
+    F, hop = int(F), int(hop)
+    return max(F + -(-int(max_len) // hop) * hop, F + int(np.ceil(float(fs) / 100.0)))
+
+
+def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, with_track=False):
+    """A batch of recordings through the pitch tracker and the one-shot phase vocoder (StftRoundTrip.autotune: one stream per recording):
+    every frame is moved onto the nearest note of its recording's key.  key: Notes::key 0..12 (12 = chromatic), one value or one per
+    recording.  The recordings are zero-padded to a common length (tune_length).  Returns float32 [2][len] per recording (the corrected
+    signal on both channels); with_track: also period int32 [S][nF] and ratio float64 [S][nF] of the padded batch.  `processor` (tests): an
+    object with run(x, fs, keys) to use instead of the GPU."""
+    S = len(voices)
+    if S == 0:
+        raise ValueError("no recordings")
+    keys = [int(k) for k in key] if isinstance(key, (list, tuple, np.ndarray)) else [int(key)] * S
+    if len(keys) != S:
+        raise ValueError("key: one value per recording expected")
+    if not all(0 <= k <= 12 for k in keys):
+        raise ValueError("key: 0..12 expected (12 = chromatic)")
+    if not 8000.0 <= float(fs) <= 51200.0:
+        raise ValueError("pvtune: sample rates from 8000 to 51200 Hz are served")
+    lens = [int(np.asarray(v).shape[-1]) for v in voices]
+    T = tune_length(max(lens), fs, F, hop)
+    x = np.zeros((S, T), np.float32)
+    for s, v in enumerate(voices):
+        v = np.asarray(v, np.float32)
+        if v.ndim != 1:
+            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
+        x[s, :lens[s]] = v
+    p = processor if processor is not None else _AutotuneRunner(F, hop, device)
+    y, period, ratio = p.run(x, float(fs), keys)
+    outs = [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
+    return (outs, period, ratio) if with_track else outs
+
+
+def write_track_csv(path, fs, hop, period, ratio, n_samples=None):
+    """One recording's track: a line per frame with its start time in seconds, the period in samples (0 = unvoiced) and the correction in
+    semitones (12 log2 ratio); n_samples: only the frames that start inside the recording."""
+    with open(path, "w") as f:
+        f.write("time_s,period,semitones\n")
+        for i, (p, r) in enumerate(zip(period, ratio)):
+            if n_samples is not None and i * int(hop) >= int(n_samples) and i > 0:
+                break
+            f.write("%.6f,%d,%.6f\n" % (i * int(hop) / float(fs), int(p), 12.0 * np.log2(float(r))))
+
+
 # ---- command line ---------------------------------------------------------------------------------------------------------
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m vocoderproject_amd.offline", description=__doc__.split("\n\n")[0])
-    ap.add_argument("flow", choices=["pitch", "vocode", "both", "pvshift", "stretch"])
+    ap.add_argument("flow", choices=["pitch", "vocode", "both", "pvshift", "stretch", "pvtune"])
     ap.add_argument("inputs", nargs="+", help="voice recordings (WAV; channel 0 is used, like the notebook)")
     ap.add_argument("--carrier", action="append", default=None,
                     help="side-chain recording(s) for vocode/both: one for all voices or one per voice")
@@ -308,7 +378,8 @@ def main(argv=None):
     ap.add_argument("--glide", default=None, metavar="A:B",
                     help="pvshift: a linear glide from A to B semitones over each recording, one value per block, instead of --shift")
     ap.add_argument("--stretch", type=float, default=None, help="stretch: output duration / input duration, 0.25 to 4 (--shift: semitones on top)")
-    ap.add_argument("--frame", type=int, default=1024, help="stretch: frame length (1024 or 2048)")
+    ap.add_argument("--frame", type=int, default=1024, help="stretch, pvtune: frame length (1024 or 2048)")
+    ap.add_argument("--track-csv", action="store_true", help="pvtune: also write NAME_pvtune.csv per recording (time, period, correction in semitones per frame)")
     ap.add_argument("--lpc-voice", type=int, default=40)
     ap.add_argument("--lpc-synth", type=int, default=5)
     ap.add_argument("--block", type=int, default=1024)
@@ -336,6 +407,18 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit(str(e))
         return _write_outputs(a, fs, outs)
+    if a.flow == "pvtune":
+        try:
+            outs, period, ratio = pv_autotune(voices, fs, key=a.key, F=a.frame, hop=a.hop, device=a.device, with_track=True)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        rc = _write_outputs(a, fs, outs)
+        if a.track_csv:
+            for s, f in enumerate(a.inputs):
+                out = os.path.join(a.out_dir, os.path.splitext(os.path.basename(f))[0] + "_pvtune.csv")
+                write_track_csv(out, fs, a.hop, period[s], ratio[s], n_samples=voices[s].shape[-1])
+                print(out)
+        return rc
     if a.flow == "pvshift":
         if (a.shift is None) == (a.glide is None):
             raise SystemExit("pvshift needs --shift or --glide A:B")

@@ -138,6 +138,12 @@ def load_library():
     if hasattr(L, "vp_stft_time_stretch"):             # (the time stretch; absent from older libraries loaded through VP_AMD_LIB)
         L.vp_stft_time_stretch.argtypes = [vp, fp, C.c_int, C.c_void_p, fp, C.c_double, C.c_void_p]
         L.vp_stretch_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]
+    if hasattr(L, "vp_stft_track_pitch"):              # (the pitch tracker; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_track_tau_max.argtypes = [C.c_double]
+        L.vp_stft_track_pitch.argtypes = [vp, fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_stft_autotune.argtypes = [vp, fp, fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_stft_last_error.argtypes = [vp]
+        L.vp_stft_last_error.restype = C.c_char_p
     L.vp_stft_set_runs.argtypes = [vp, C.c_int]
     L.vp_stft_set_precision.argtypes = [vp, C.c_int]
     L.vp_stft_get_precision.argtypes = [vp]
@@ -640,6 +646,61 @@ class StftRoundTrip:
         rc = self.L.vp_stft_time_stretch(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), float(semitones), C.c_void_p(stream))
         if rc:
             raise VpError(rc, self.L.vp_error_string(rc).decode())
+
+    def _track_tables(self, keys, dev):
+        """(d_key or None, period, ratio): the call's key table and outputs.  The key table is kept per handle (one device int32 [S],
+        rewritten on torch's current stream when `keys` is host data); the outputs are new tensors, the caller's to keep."""
+        import torch
+        d_key = None
+        if keys is not None:
+            if isinstance(keys, torch.Tensor):
+                assert keys.is_cuda and keys.dtype == torch.int32 and tuple(keys.shape) == (self.S,) and keys.is_contiguous()
+                d_key = keys
+            else:
+                k = np.asarray(keys)
+                assert k.dtype.kind in "iu" and k.shape in ((), (self.S,)), (k.dtype, k.shape)
+                k = np.ascontiguousarray(np.broadcast_to(k, (self.S,)), dtype=np.int32)
+                if getattr(self, "_key_table", None) is None:
+                    self._key_table = torch.empty((self.S,), dtype=torch.int32, device=dev)
+                self._key_table.copy_(torch.from_numpy(k))
+                d_key = self._key_table
+        period = torch.empty((self.S, self.n_frames), dtype=torch.int32, device=dev)
+        ratio = torch.empty((self.S, self.n_frames), dtype=torch.float64, device=dev)
+        return d_key, period, ratio
+
+    def _track_chk(self, rc):
+        if rc:
+            msg = self.L.vp_stft_last_error(self.h).decode()
+            raise VpError(rc, msg or self.L.vp_error_string(rc).decode())
+
+    def track_pitch(self, d_in, sample_rate, keys=None, stream=None):
+        """The pitch tracker (vp_stft_track_pitch): PitchProcess's YIN and nearest note for every frame of the batch at once.  Returns
+        (period, ratio), device tensors int32 / float64 [S][n_frames]: the period in samples (0 = unvoiced) and the ratio
+        closestFreq / pitch that moves the frame onto its key's nearest note (1.0 where unvoiced) -- the table pitch_shift_curve(d_ratio=...)
+        takes.  keys: Notes::key per stream, 0..12 (12 = chromatic, also for any value outside the range): an int, a sequence of S ints or
+        a device int32 tensor [S]; None = chromatic.  8000 <= sample_rate <= 51200 and n_samples >= frame_len + ceil(sample_rate / 100)
+        (VpError otherwise).  Frames are independent: no smoothing, no hold across unvoiced frames."""
+        import torch
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
+        d_key, period, ratio = self._track_tables(keys, d_in.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        self._track_chk(self.L.vp_stft_track_pitch(self.h, d_in.data_ptr(), float(sample_rate), d_key.data_ptr() if d_key is not None else None,
+                                                   period.data_ptr(), ratio.data_ptr(), C.c_void_p(stream)))
+        return period, ratio
+
+    def autotune(self, d_in, d_out, sample_rate, keys=None, stream=None):
+        """Automatic pitch correction (vp_stft_autotune): track_pitch, then pitch_shift_curve along its ratios, on one stream; d_out has
+        the bits of those two calls.  Returns track_pitch's (period, ratio)."""
+        import torch
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
+        assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
+        d_key, period, ratio = self._track_tables(keys, d_in.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        self._track_chk(self.L.vp_stft_autotune(self.h, d_in.data_ptr(), d_out.data_ptr(), float(sample_rate),
+                                                d_key.data_ptr() if d_key is not None else None, period.data_ptr(), ratio.data_ptr(), C.c_void_p(stream)))
+        return period, ratio
 
     def close(self):
         if getattr(self, "h", None):
