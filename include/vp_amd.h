@@ -381,7 +381,7 @@ int vp_stretch_positions(int *pos, int n_frames, int hop, double stretch, int n_
  *   d[k] = sum_{i < frame_len} (x[b + i] - x[b + i + k])^2 in double, each its own left-to-right sum; d[0] = 1, then tmp += d[k],
  *   d[k] *= k / tmp in increasing k; d[tauMax] = 0; the threshold walk of PitchProcess.cpp:429-447 gives the period, or 0 (unvoiced);
  *   period > 0: pitch = fs / period, ratio = closest(pitch, key) / pitch; period 0: ratio = 1.0 exactly.
- * Frames are independent: no gate, no hold of the last voiced ratio, no smoothing.  Float32-denormal input samples are outside the
+ * Frames are independent: no gate, no hold of the last voiced ratio, no smoothing (the streaming tracker below, vp_pv_tracker_*, has both).  Float32-denormal input samples are outside the
  * definition's domain (the kernels widen them to 0).
  * d_in: device float [n_streams][n_samples]; d_key: device int [n_streams], Notes::key 0..12 (12 = chromatic; any other value counts
  * as 12), or NULL = chromatic everywhere; d_period: device int [n_streams][vp_stft_num_frames(p)] or NULL; d_ratio: device double of
@@ -450,6 +450,43 @@ int vp_pv_process_blocks_device(vp_pv *p, const float *d_in, float *d_out, int n
  * runs: keep it unchanged until then.  No allocation. */
 int vp_pv_process_blocks_curve_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream);
 long vp_pv_debug_alloc_count(const vp_pv *p);                           /* constant across process calls */
+
+/* Streaming pitch tracker and automatic correction for the stream above (kernels vp_k_yin_track_stream and vp_k_track_follow,
+ * csrc/vp_track.hip): vp_stft_track_pitch's decision once per block and stream, from the audio received so far, followed across unvoiced
+ * blocks and over time -- the table vp_pv_process_blocks_curve_device takes.  The definition is tests/pv_track_stream_reference.py, and
+ * period and ratio equal it bit for bit.  One handle holds S streams, block size N >= 1, the sample rate (8000 .. 51200) and an analysis
+ * length F of 1024 or 2048 (VP_ERR_GEOMETRY otherwise) that is the tracker's own: the shifter's frame length does not enter.
+ *  - tauMax = ceil(fs / 100), W = F + tauMax.  Per stream, x is everything received since create or the stream's last reset and
+ *    n_b = (b + 1) N the count after block b.  n_b < W: period 0, raw ratio 1.0 (no zero-padded window is analysed).  Otherwise the raw
+ *    decision is vp_stft_track_pitch's for the window x[n_b - W, n_b) taken as a row of W samples: causal, no added latency.
+ *  - Follow stage, per stream (tgt = 1.0, age = 0, cur = 1.0), per handle hold_blocks H and glide g (defaults 0 and 1.0: the raw ratio):
+ *      period > 0: tgt = raw ratio, age = 0;  else: age = min(age + 1, INT_MAX), and tgt = 1.0 once age > H;
+ *      cur = tgt when g == 1.0, else cur + g * (tgt - cur) in double (product and add separate);  ratio[b][s] = cur.
+ *  - How blocks are grouped into calls does not change a bit of either table.
+ *  - vp_pv_tracker_reset(stream; -1 = all) takes effect at the next process call issued after it (a call already enqueued does not see
+ *    it) and travels in the arguments of a launch in front of that call; the stream then equals a fresh handle's: no history, follow
+ *    state (1.0, 0, 1.0).  vp_pv_tracker_set_follow applies to every stream from the next call on and travels as kernel arguments;
+ *    0 <= hold_blocks <= 2^20 and 0 < glide <= 1 (VP_ERR_INVALID_ARG otherwise, also for a glide that is not finite).
+ * d_in: device float [n_blocks][S][N], the slab the vp_pv_* calls take; d_key: device int [S] or NULL, as vp_stft_track_pitch's;
+ * d_period: device int [n_blocks][S] or NULL; d_ratio: device double [n_blocks][S] or NULL; not both NULL.  The state advances whichever
+ * outputs are given.  No allocation (device memory at create only: per stream a ring of its last W samples, about 6 KB at F = 1024, a
+ * 64-bit sample counter and the follow state; vp_pv_tracker_debug_alloc_count stays constant), no synchronisation.  The cost of a decision
+ * does not depend on N: N = 64 costs 16 times as much per second of audio as N = 1024.  VP_ERR_INVALID_ARG (null pointer, both outputs
+ * NULL, n_blocks <= 0, sample rate, stream or follow parameter out of range) is reported before the device is touched. */
+typedef struct vp_pv_tracker vp_pv_tracker;
+int vp_pv_tracker_create(int device, int n_streams, int block_size, int frame_len, double sample_rate, vp_pv_tracker **out);
+int vp_pv_tracker_destroy(vp_pv_tracker *t);
+long vp_pv_tracker_debug_alloc_count(const vp_pv_tracker *t);            /* constant across process calls */
+int vp_pv_tracker_reset(vp_pv_tracker *t, int stream);                  /* stream -1 = all */
+int vp_pv_tracker_set_follow(vp_pv_tracker *t, int hold_blocks, double glide);
+int vp_pv_tracker_process_blocks_device(vp_pv_tracker *t, const float *d_in, const int *d_key, int *d_period, double *d_ratio, int n_blocks,
+                                        void *hip_stream);
+/* vp_pv_tracker_process_blocks_device followed by vp_pv_process_blocks_curve_device along its table, on the same stream: the output has
+ * the bits of those two calls.  d_ratio is required (result and scratch), d_period optional.  VP_ERR_GEOMETRY if S, N or the device
+ * differ between the two handles.  vp_pv_reset does not reach the tracker and vp_pv_tracker_reset does not reach the shifter: a caller
+ * that restarts a stream resets both. */
+int vp_pv_autotune_blocks_device(vp_pv *p, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, int *d_period, double *d_ratio,
+                                 int n_blocks, void *hip_stream);
 
 const char *vp_error_string(int code);
 const char *vp_last_error(const vp_handle *h);

@@ -341,6 +341,40 @@ private:
 };
 
 // ------------------------------------------------------------------------------------------------
+// vp::StreamingPitchTracker -- the streaming pitch tracker (vp_pv_tracker_*, vp_amd.h): one ratio per block and stream from the audio received
+// so far (YIN on the last frameLen + ceil(sampleRate / 100) samples, the key's nearest note), the last voiced ratio held over holdBlocks
+// unvoiced blocks, the ratio moved the fraction `glide` of the way to its target per block.  Its table is what
+// StreamingPitchShifter::processBlocksCurve takes; StreamingPitchShifter::autotuneBlocks runs both.
+class StreamingPitchTracker {
+public:
+    StreamingPitchTracker(int device, int nStreams, int blockSize, double sampleRate, int frameLen = 1024)
+    {
+        check(vp_pv_tracker_create(device, nStreams, blockSize, frameLen, sampleRate, &t_), "vp_pv_tracker_create");
+    }
+    ~StreamingPitchTracker() { if (t_) vp_pv_tracker_destroy(t_); }
+    StreamingPitchTracker(const StreamingPitchTracker &) = delete;
+    StreamingPitchTracker &operator=(const StreamingPitchTracker &) = delete;
+
+    // every stream, from the next process call on; 0 <= holdBlocks <= 2^20, 0 < glide <= 1 (defaults 0 and 1: the raw ratio)
+    void setFollow(int holdBlocks, double glide) { check(vp_pv_tracker_set_follow(t_, holdBlocks, glide), "setFollow"); }
+    // takes effect at the next process call; stream = -1: all streams.  The shifter has its own reset.
+    void reset(int stream = -1) { check(vp_pv_tracker_reset(t_, stream), "reset"); }
+    // device float [nBlocks][S][N] -> period int [nBlocks][S] and/or ratio double [nBlocks][S] (one may be null); dKey: device int [S] or
+    // null (chromatic); enqueued on hipStream without synchronising
+    void processBlocksDevice(const float *dIn, const int *dKey, int *dPeriod, double *dRatio, int nBlocks, void *hipStream = nullptr)
+    {
+        check(vp_pv_tracker_process_blocks_device(t_, dIn, dKey, dPeriod, dRatio, nBlocks, hipStream), "processBlocksDevice");
+    }
+    vp_pv_tracker *handle() const { return t_; }
+
+private:
+    static void check(int rc, const std::string &what)
+    {
+        if (rc != VP_OK) throw Error(rc, what + ": " + vp_error_string(rc));
+    }
+    vp_pv_tracker *t_ = nullptr;
+};
+
 // vp::StreamingPitchShifter -- the streaming phase vocoder (vp_pv_*, vp_amd.h): S streams, blocks of N samples, state kept across calls.
 // Output sample t of a stream is sample t - latency() of the one-shot vp_stft_pitch_shift on everything the stream received.
 //
@@ -378,6 +412,13 @@ public:
     void processBlocksCurve(const float *dIn, float *dOut, const double *dRatio, int nBlocks, void *hipStream = nullptr)
     {
         check(vp_pv_process_blocks_curve_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksCurve");
+    }
+    // automatic correction: the tracker's call, then processBlocksCurve along its table (dRatio: result and scratch, required; dPeriod
+    // may be null), on one stream.  The tracker must have this shifter's streams, block size and device.  reset() does not reach it.
+    void autotuneBlocks(StreamingPitchTracker &tracker, const float *dIn, float *dOut, const int *dKey, int *dPeriod, double *dRatio, int nBlocks,
+                        void *hipStream = nullptr)
+    {
+        check(vp_pv_autotune_blocks_device(p_, tracker.handle(), dIn, dOut, dKey, dPeriod, dRatio, nBlocks, hipStream), "autotuneBlocks");
     }
     vp_pv *handle() const { return p_; }
 

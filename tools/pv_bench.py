@@ -5,6 +5,7 @@
     [VP_AMD_LIB=...] python tools/pv_bench.py --curve [--reps 7] [--out profiles/pv_curve_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --stretch [--reps 7] [--out profiles/pv_stretch_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --track [--reps 7] [--out profiles/pv_track_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --track-stream [--reps 7] [--out profiles/pv_track_stream_bench.txt]
 
 --curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
 "steps" curve, fixed, ...): 256 streams x 65 536 samples at 1024 points / hop 256 and 2048 points / hop 512 (vp_stft_pitch_shift against
@@ -21,6 +22,13 @@ from the same run is the comparison; the kernels' resource listings follow.
 vp_stft_autotune (the two on one stream), alternating in one process: 256 streams x 65 536 samples of voiced signals (a harmonic tone with
 vibrato per stream, every fourth stream noise) at 44.1 kHz, 1024 points / hop 256 and 2048 points / hop 512.  Printed: each leg's frames/s,
 the tracker's beside the curve kernel's, and autotune's time per call against the sum of its parts'.
+
+--track-stream: the streaming tracker (vp_pv_tracker_process_blocks_device, kernels vp_k_yin_track_stream and vp_k_track_follow) beside the
+batch tracker, alternating in one process: 256 streams at 44.1 kHz, 1024 points, the same signals.  The batch tracker runs at --track's shape
+(65 536 samples, hop 256: the yardstick) and at the streaming call's number of decisions (16 frames per stream, hop 512); the streaming
+tracker takes 16 blocks of 1024 per call and, as its own line, one block per call.  Then the streaming autotune
+(vp_pv_autotune_blocks_device) against the tracker call and the curve call that make it up.  Every repetition is a window of about a tenth of a second of calls.  Printed: decisions/s per leg and autotune's
+time per call against the sum of its parts'.
 """
 import argparse
 import os
@@ -53,7 +61,8 @@ def fixed_intervals():
 
 
 def alternate(legs, reps, calls, warmup=3):
-    """legs: {name: callable enqueueing one call}.  Returns {name: [seconds per call, one per repetition]}, the legs taking turns."""
+    """legs: {name: callable enqueueing one call}.  Returns {name: [seconds per call, one per repetition]}, the legs taking turns.
+    calls: calls per repetition, one number or one per leg ({name: n}: short calls need more of them to fill a window)."""
     import torch
     for fn in legs.values():
         for _ in range(warmup):
@@ -64,10 +73,11 @@ def alternate(legs, reps, calls, warmup=3):
         for name, fn in legs.items():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for _ in range(calls):
+            n = calls[name] if isinstance(calls, dict) else calls
+            for _ in range(n):
                 fn()
             torch.cuda.synchronize()
-            out[name].append((time.perf_counter() - t0) / calls)
+            out[name].append((time.perf_counter() - t0) / n)
     return out
 
 
@@ -140,17 +150,7 @@ def track_legs(reps, emit):
     import torch
     from vocoderproject_amd import StftRoundTrip
     S, T, fs = 256, 65536, 44100.0
-    rng = np.random.default_rng(11)
-    t = np.arange(T) / fs
-    rows = []
-    for s in range(S):
-        if s % 4 == 3:
-            rows.append(0.1 * rng.standard_normal(T))
-            continue
-        f0 = rng.uniform(110.0, 440.0) * 2.0 ** (0.3 / 12.0 * np.sin(2.0 * np.pi * rng.uniform(3.0, 7.0) * t))
-        ph = 2.0 * np.pi * np.cumsum(f0) / fs
-        rows.append(0.3 * np.sin(ph) + 0.15 * np.sin(2.0 * ph + 1.0) + 0.08 * np.sin(3.0 * ph + 2.0))
-    x = torch.from_numpy(np.stack(rows).astype(np.float32)).cuda()
+    x = torch.from_numpy(voiced_rows(S, T, fs)).cuda()
     y = torch.empty_like(x)
     keys = torch.from_numpy((np.arange(S) % 13).astype(np.int32)).cuda()
     for F, hop in ((1024, 256), (2048, 512)):
@@ -173,6 +173,82 @@ def track_legs(reps, emit):
         st.close()
 
 
+def voiced_rows(S, T, fs, seed=11):
+    """--track's signals: a harmonic tone with vibrato per stream, every fourth stream noise; float32 [S][T]."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    t = np.arange(T) / fs
+    rows = []
+    for s in range(S):
+        if s % 4 == 3:
+            rows.append(0.1 * rng.standard_normal(T))
+            continue
+        f0 = rng.uniform(110.0, 440.0) * 2.0 ** (0.3 / 12.0 * np.sin(2.0 * np.pi * rng.uniform(3.0, 7.0) * t))
+        ph = 2.0 * np.pi * np.cumsum(f0) / fs
+        rows.append(0.3 * np.sin(ph) + 0.15 * np.sin(2.0 * ph + 1.0) + 0.08 * np.sin(3.0 * ph + 2.0))
+    return np.stack(rows).astype(np.float32)
+
+
+def track_stream_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import PhaseVocoderStream, StftRoundTrip, StreamingPitchTracker
+    S, T, fs, F, N, K = 256, 65536, 44100.0, 1024, 1024, 16
+    rows = voiced_rows(S, T, fs)
+    x = torch.from_numpy(rows).cuda()
+    keys = torch.from_numpy((np.arange(S) % 13).astype(np.int32)).cuda()
+    # the batch tracker: the yardstick's shape, and the streaming call's number of decisions (K frames per stream)
+    st = StftRoundTrip(S, T, F, 256)
+    Tk = F + (K - 1) * 512 + 441
+    stk = StftRoundTrip(S, Tk, F, 512)
+    xk = x[:, :Tk].contiguous()
+    assert stk.n_frames == K
+    # the streaming tracker: two blocks of history first (W = 1465 samples), then every decision has a full window
+    blocks = torch.from_numpy(np.ascontiguousarray(rows[:, :(K + 2) * N].reshape(S, K + 2, N).transpose(1, 0, 2))).cuda()
+    trk, trk1 = StreamingPitchTracker(S, N, fs, F), StreamingPitchTracker(S, N, fs, F)
+    for t in (trk, trk1):
+        t.process_device(blocks[:2], n_blocks=2, keys=keys)
+    slab, one = blocks[2:].contiguous(), blocks[2:3].contiguous()
+    period, _ = trk.process_device(slab, n_blocks=K, keys=keys)
+    torch.cuda.synchronize()
+    voiced = float((period > 0).float().mean())
+    legs = {"batch, 65 536 samples, hop 256": lambda: st.track_pitch(x, fs, keys=keys),
+            f"batch, {K} frames per stream": lambda: stk.track_pitch(xk, fs, keys=keys),
+            f"streaming, {K} blocks per call": lambda: trk.process_device(slab, n_blocks=K, keys=keys),
+            "streaming, 1 block per call": lambda: trk1.process_device(one, n_blocks=1, keys=keys)}
+    decisions = {"batch, 65 536 samples, hop 256": S * st.n_frames, f"batch, {K} frames per stream": S * K, f"streaming, {K} blocks per call": S * K,
+                 "streaming, 1 block per call": S}
+    calls = dict(zip(legs, (40, 500, 500, 2000)))                            # (windows of about a tenth of a second each)
+    times = alternate(legs, reps, calls)
+    emit(f"streaming pitch tracker, {S} streams at {fs:g} Hz, F = {F}, blocks of {N}, {100.0 * voiced:.0f} % of the decisions voiced")
+    rate = {k: [decisions[k] / t / 1e6 for t in v] for k, v in times.items()}
+    mean = {k: sum(r) / len(r) for k, r in rate.items()}
+    for k, r in rate.items():
+        emit(f"  {k:<32s} {mean[k]:8.2f} M decisions/s  (min {min(r):.2f}, max {max(r):.2f}, {len(r)} repetitions)  "
+             f"{sum(times[k]) / len(times[k]) * 1e6:8.1f} us per call")
+    emit(f"  streaming, {K} blocks per call = {mean[f'streaming, {K} blocks per call'] / mean['batch, 65 536 samples, hop 256']:.3f} x the batch tracker at its "
+         f"bench shape, {mean[f'streaming, {K} blocks per call'] / mean[f'batch, {K} frames per stream']:.3f} x the batch tracker at {K} frames per stream")
+    for h in (st, stk, trk, trk1):
+        h.close()
+    # autotune against its parts: separate handle pairs, the same slab
+    y = torch.empty_like(slab)
+    pv_a, pv_b, trk_a, trk_b = PhaseVocoderStream(S, N), PhaseVocoderStream(S, N), StreamingPitchTracker(S, N, fs, F), StreamingPitchTracker(S, N, fs, F)
+    for t in (trk_a, trk_b):
+        t.process_device(blocks[:2], n_blocks=2, keys=keys)
+    _, table = trk_a.process_device(slab, n_blocks=K, keys=keys)
+    legs = {"tracker": lambda: trk_a.process_device(slab, n_blocks=K, keys=keys),
+            "curve on the tracker's table": lambda: pv_a.process_device(slab, y, n_blocks=K, d_ratio=table),
+            "autotune": lambda: pv_b.autotune_device(trk_b, slab, y, n_blocks=K, keys=keys)}
+    times = alternate(legs, reps, 300)
+    m = {k: sum(v) / len(v) for k, v in times.items()}
+    parts = m["tracker"] + m["curve on the tracker's table"]
+    emit(f"streaming autotune, {S} streams, {K} blocks of {N} per call, hop = 256")
+    emit(f"  per call: tracker {m['tracker'] * 1e3:.3f} ms + curve {m['curve on the tracker' + chr(39) + 's table'] * 1e3:.3f} ms = {parts * 1e3:.3f} ms; "
+         f"autotune {m['autotune'] * 1e3:.3f} ms = {m['autotune'] / parts:.3f} x the sum")
+    for h in (pv_a, pv_b, trk_a, trk_b):
+        h.close()
+
+
 def resource_listing(emit, kernels=("vp_k_stft_fused<true, false>", "vp_k_stft_pv_stretch", "vp_k_stft_pv2k", "vp_k_stft_pv2k_stretch")):
     try:
         import kernel_resources
@@ -191,10 +267,11 @@ def main():
     ap.add_argument("--curve", action="store_true", help="the ratio-curve legs instead of the fixed intervals")
     ap.add_argument("--stretch", action="store_true", help="the time-stretch legs instead of the fixed intervals")
     ap.add_argument("--track", action="store_true", help="the pitch-tracker legs instead of the fixed intervals")
+    ap.add_argument("--track-stream", action="store_true", help="the streaming-tracker legs instead of the fixed intervals")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="--curve / --stretch / --track: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve and not a.stretch and not a.track:
+    if not a.curve and not a.stretch and not a.track and not a.track_stream:
         return fixed_intervals()
     lines = []
 
@@ -209,6 +286,9 @@ def main():
     if a.track:
         track_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_yin_track", "vp_k_stft_pv_curve", "vp_k_stft_pv2k_curve"))
+    if a.track_stream:
+        track_stream_legs(max(5, a.reps), emit)
+        resource_listing(emit, ("vp_k_yin_track", "vp_k_yin_track_stream", "vp_k_track_follow", "vp_k_track_reset", "vp_k_pv_stream_curve"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

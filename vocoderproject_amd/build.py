@@ -21,7 +21,7 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libvp_amd.so")
 SOURCES = ["vp_kernels.hip", "vp_voc2.hip", "vp_stft.hip", "vp_channels.hip", "vp_track.hip", "vp_capi.hip"]
 PARTS = ["vp_fft.inc", "vp_filters.inc", "vp_vocoder_wg.inc", "vp_pitch.inc", "vp_pitch_ws.inc", "vp_pitch_ws_body.inc"]      # included by vp_kernels.hip
-DEPS = SOURCES + PARTS + ["vp_common.h", "vp_kernels.h", "vp_voc2.h", "vp_stft.h", "vp_fft32.inc", "vp_channels.h", "vp_stft_curve.inc", "vp_stft_stretch.inc", "vp_track.h"]
+DEPS = SOURCES + PARTS + ["vp_common.h", "vp_kernels.h", "vp_voc2.h", "vp_stft.h", "vp_fft32.inc", "vp_channels.h", "vp_stft_curve.inc", "vp_stft_stretch.inc", "vp_track.h", "vp_track_body.inc"]
 ARCH = "gfx950"
 NUM_TUS = 9          # groups of kernels in vp_kernels.hip (VP_TU)
 
@@ -141,7 +141,7 @@ def build(force=False, verbose=False, stamps=False, poison=False):
                     "vp_voc2.hip": ["vp_voc2.hip", "vp_voc2.h", "vp_kernels.hip", "vp_common.h"] + PARTS,
                     "vp_stft.hip": ["vp_stft.hip", "vp_stft.h", "vp_fft.inc", "vp_fft32.inc", "vp_stft_curve.inc", "vp_stft_stretch.inc"],
                     "vp_channels.hip": ["vp_channels.hip", "vp_channels.h"],
-                    "vp_track.hip": ["vp_track.hip", "vp_track.h", "vp_common.h"]}.get(os.path.basename(src))
+                    "vp_track.hip": ["vp_track.hip", "vp_track.h", "vp_track_body.inc", "vp_common.h"]}.get(os.path.basename(src))
             if deps is None:
                 deps = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.basename(src), os.path.join(ROOT, "include", "vp_amd.h")]
             for dep in deps:

@@ -2262,3 +2262,162 @@ extern "C" int vp_pv_process_block(vp_pv *p, const float *in, float *out)
     if (hipMemcpyAsync(out, p->stageOut, bytes, hipMemcpyDeviceToHost, p->ownStream) != hipSuccess) return VP_ERR_HIP;
     return hipStreamSynchronize(p->ownStream) == hipSuccess ? VP_OK : VP_ERR_HIP;
 }
+
+// ---- streaming pitch tracker of the phase-vocoder stream (csrc/vp_track.hip): vp_k_yin_track_stream, then vp_k_track_follow -----------
+#define TRKS_SCRATCH_BLOCKS 64          // blocks per launch pair when an output is NULL and the handle's scratch stands in for it
+
+struct vp_pv_tracker {
+    int device = 0, S = 0, N = 0, F = 0, W = 0, tauMax = 0, tau0 = 0;
+    double fs = 0;
+    unsigned char *state = nullptr;             // ring [S][W] float, then count [S] int64, tgt [S], cur [S] double, age [S] int
+    float *ring = nullptr; long long *count = nullptr; double *tgt = nullptr, *cur = nullptr; int *age = nullptr;   // (into state)
+    int *scrPeriod = nullptr; double *scrRatio = nullptr;   // [TRKS_SCRATCH_BLOCKS][S]: the raw table the caller did not ask for
+    double *notes = nullptr; int *notesN = nullptr;
+    long nAllocs = 0;
+    int hold = 0; double glide = 1.0;           // what the next call uses
+    bool allReset = false;
+    std::vector<char> resetPend;                // [S]
+};
+
+static void trks_free(vp_pv_tracker *t)
+{
+    (void)hipFree(t->state); (void)hipFree(t->scrPeriod); (void)hipFree(t->scrRatio); (void)hipFree(t->notes); (void)hipFree(t->notesN);
+}
+
+extern "C" int vp_pv_tracker_create(int device, int n_streams, int block_size, int frame_len, double sample_rate, vp_pv_tracker **out)
+{
+    if (!out || n_streams <= 0 || block_size <= 0) return VP_ERR_INVALID_ARG;
+    if ((long long)n_streams * block_size > (1LL << 28) || (long long)block_size > (1 << 24)) return VP_ERR_INVALID_ARG;   // (as vp_pv_create)
+    const int tauMax = vp_track_tau_max(sample_rate);
+    if (tauMax < 0) return VP_ERR_INVALID_ARG;
+    if (frame_len != 1024 && frame_len != 2048) return VP_ERR_GEOMETRY;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VP_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    vp_pv_tracker *t = new vp_pv_tracker();
+    t->device = device; t->S = n_streams; t->N = block_size; t->F = frame_len; t->fs = sample_rate;
+    t->tauMax = tauMax; t->W = frame_len + tauMax;
+    t->tau0 = (int)std::floor(sample_rate / VP_TRACK_FMAX);                                     // PitchProcess.cpp:429
+    t->resetPend.assign(n_streams, 0);
+    const size_t S = (size_t)n_streams;
+    const size_t ringBytes = (S * t->W * sizeof(float) + 7) & ~(size_t)7;
+    std::vector<unsigned char> st(ringBytes + S * (8 + 8 + 8 + 4), 0);                          // count 0, age 0, ring zeros (never read before written)
+    for (size_t s = 0; s < 2 * S; s++) { const double one = 1.0; memcpy(&st[ringBytes + S * 8 + s * 8], &one, 8); }   // tgt = cur = 1.0
+    std::vector<double> notes(13 * VP_NOTES_STRIDE, 0.0);
+    int notesN[13];
+    for (int k = 0; k < 13; k++) notesN[k] = build_notes(k, VP_TRACK_FMIN, VP_TRACK_FMAX, notes.data() + (size_t)k * VP_NOTES_STRIDE);
+    auto al = [t](void **d, size_t bytes) { if (hipMalloc(d, bytes) != hipSuccess) return false; t->nAllocs++; return true; };
+    const bool ok = al((void **)&t->state, st.size()) && hipMemcpy(t->state, st.data(), st.size(), hipMemcpyHostToDevice) == hipSuccess
+        && al((void **)&t->scrPeriod, TRKS_SCRATCH_BLOCKS * S * sizeof(int)) && al((void **)&t->scrRatio, TRKS_SCRATCH_BLOCKS * S * sizeof(double))
+        && al((void **)&t->notes, notes.size() * 8) && hipMemcpy(t->notes, notes.data(), notes.size() * 8, hipMemcpyHostToDevice) == hipSuccess
+        && al((void **)&t->notesN, sizeof notesN) && hipMemcpy(t->notesN, notesN, sizeof notesN, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) { trks_free(t); delete t; (void)hipGetLastError(); return VP_ERR_OOM; }
+    t->ring = (float *)t->state;
+    t->count = (long long *)(t->state + ringBytes);
+    t->tgt = (double *)(t->count + S); t->cur = t->tgt + S; t->age = (int *)(t->cur + S);
+    *out = t;
+    return VP_OK;
+}
+
+extern "C" int vp_pv_tracker_destroy(vp_pv_tracker *t)
+{
+    if (!t) return VP_ERR_INVALID_ARG;
+    (void)hipSetDevice(t->device);
+    (void)hipDeviceSynchronize();
+    trks_free(t);
+    delete t;
+    return VP_OK;
+}
+
+extern "C" long vp_pv_tracker_debug_alloc_count(const vp_pv_tracker *t) { return t ? t->nAllocs : VP_ERR_INVALID_ARG; }
+
+extern "C" int vp_pv_tracker_reset(vp_pv_tracker *t, int stream)
+{
+    if (!t || stream < -1 || stream >= t->S) return VP_ERR_INVALID_ARG;
+    if (stream < 0) {
+        t->allReset = true;
+        std::fill(t->resetPend.begin(), t->resetPend.end(), 0);
+    } else t->resetPend[stream] = 1;
+    return VP_OK;
+}
+
+extern "C" int vp_pv_tracker_set_follow(vp_pv_tracker *t, int hold_blocks, double glide)
+{
+    if (!t || hold_blocks < 0 || hold_blocks > (1 << 20) || !(glide > 0.0 && glide <= 1.0)) return VP_ERR_INVALID_ARG;   // (a NaN fails the test)
+    t->hold = hold_blocks; t->glide = glide;
+    return VP_OK;
+}
+
+// every argument of a streaming tracker call, checked before the device is touched
+static int trks_check(const vp_pv_tracker *t, const float *d_in, const int *d_period, const double *d_ratio, int n_blocks)
+{
+    if (!t || !d_in || (!d_period && !d_ratio) || n_blocks <= 0 || (long long)n_blocks * t->N > (1 << 28)) return VP_ERR_INVALID_ARG;
+    return VP_OK;
+}
+
+// the pending resets travel in the arguments of update launches in front of the call: ordered on the caller's stream, no host memory
+// the device reads later, no allocation.  An output the caller left out is replaced by the handle's scratch, TRKS_SCRATCH_BLOCKS blocks
+// per launch pair (how blocks are grouped into launches does not change a bit).
+static int trks_run(vp_pv_tracker *t, const float *d_in, const int *d_key, int *d_period, double *d_ratio, int n_blocks, hipStream_t st)
+{
+    VpTrackUpdArgs u;
+    memset(&u, 0, sizeof u);
+    u.count = t->count; u.tgt = t->tgt; u.cur = t->cur; u.age = t->age; u.S = t->S;
+    if (t->allReset) u.stream[u.n++] = -1;
+    else
+        for (int s = 0; s < t->S; s++) {
+            if (!t->resetPend[s]) continue;
+            u.stream[u.n++] = s;
+            if (u.n == VP_TRKS_MAX_UPDATES) {
+                if (vp_track_reset_launch(u, st) != hipSuccess) return VP_ERR_HIP;
+                u.n = 0;
+            }
+        }
+    if (u.n && vp_track_reset_launch(u, st) != hipSuccess) return VP_ERR_HIP;
+    t->allReset = false;
+    std::fill(t->resetPend.begin(), t->resetPend.end(), 0);
+
+    VpTrackStreamArgs a;
+    memset(&a, 0, sizeof a);
+    a.key = d_key; a.notes = t->notes; a.notesN = t->notesN; a.ring = t->ring; a.count = t->count;
+    a.fs = t->fs; a.S = t->S; a.N = t->N; a.F = t->F; a.tauMax = t->tauMax; a.tau0 = t->tau0;
+    VpTrackFollowArgs f;
+    memset(&f, 0, sizeof f);
+    f.ring = t->ring; f.count = t->count; f.tgt = t->tgt; f.cur = t->cur; f.age = t->age;
+    f.glide = t->glide; f.hold = t->hold; f.S = t->S; f.N = t->N; f.W = t->W;
+    const int chunk = (d_period && d_ratio) ? n_blocks : std::min(n_blocks, TRKS_SCRATCH_BLOCKS);
+    for (int b = 0; b < n_blocks; b += chunk) {
+        const int nb = std::min(chunk, n_blocks - b);
+        const size_t row = (size_t)b * t->S;
+        a.in = f.in = d_in + row * t->N;
+        a.period = d_period ? d_period + row : t->scrPeriod;
+        a.ratio = f.ratio = d_ratio ? d_ratio + row : t->scrRatio;
+        f.period = a.period;
+        a.nBlocks = f.nBlocks = nb;
+        if (vp_track_stream_launch(a, st) != hipSuccess || vp_track_follow_launch(f, st) != hipSuccess) return VP_ERR_HIP;
+    }
+    return VP_OK;
+}
+
+extern "C" int vp_pv_tracker_process_blocks_device(vp_pv_tracker *t, const float *d_in, const int *d_key, int *d_period, double *d_ratio, int n_blocks,
+                                                   void *hip_stream)
+{
+    const int rc = trks_check(t, d_in, d_period, d_ratio, n_blocks);
+    if (rc) return rc;
+    if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
+}
+
+// the tracker call, then vp_pv_process_blocks_curve_device along its table, on the same stream
+extern "C" int vp_pv_autotune_blocks_device(vp_pv *p, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, int *d_period, double *d_ratio,
+                                            int n_blocks, void *hip_stream)
+{
+    if (!p || !d_out || !d_ratio) return VP_ERR_INVALID_ARG;
+    int rc = trks_check(t, d_in, d_period, d_ratio, n_blocks);
+    if (rc) return rc;
+    if (p->S != t->S || p->N != t->N || p->device != t->device) return VP_ERR_GEOMETRY;
+    if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
+    if (rc) return rc;
+    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio);
+}

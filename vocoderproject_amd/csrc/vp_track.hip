@@ -1,4 +1,5 @@
-// vp_track.hip -- batch pitch tracker for the phase-vocoder path: YIN per STFT frame, the key's nearest note, one ratio per frame.
+// vp_track.hip -- pitch trackers for the phase-vocoder path: YIN per STFT frame, the key's nearest note, one ratio per frame (the batch
+// tracker), and the same decision per block of a stream with per-stream history (the streaming tracker, at the end of this file).
 //
 // The definition is tests/pv_track_reference.py: PitchProcess's own decision (computeYinTemp, PitchProcess.cpp:350-403; the
 // threshold walk, :429-447; beta = closestFreq / pitch, :595-596) with the plugin's numbers (fMin 100, fMax 800, yinTol 0.25, the
@@ -81,99 +82,7 @@ __global__ __launch_bounds__(64 * VP_TRACK_WAVES) void vp_k_yin_track(VpTrackArg
     for (int p = lane; p < nRows * 8; p += 64) xs[p + (p >> 3)] = p < win ? row[p] : 0.0f;
     trk_wave_sync();
 
-    // d[8 lane + j] = sum over i of (x[i] - x[i + 8 lane + j])^2, i ascending; w[m] = x[i0 + 8 lane + m]
-    double acc[VP_TRACK_LAGS], w[2 * VP_TRACK_LAGS];
-    const trk_lds_f32 *wl = xs + TRK_ROW * lane;
-#pragma unroll
-    for (int j = 0; j < VP_TRACK_LAGS; j++) { acc[j] = 0.0; w[j] = (double)wl[j]; }
-    for (int blk = 0; blk < F / 8; blk++) {
-        const trk_lds_f32 *nx = wl + TRK_ROW * (blk + 1), *vb = xs + TRK_ROW * blk;
-        double v[8];
-#pragma unroll
-        for (int m = 0; m < 8; m++) { w[8 + m] = (double)nx[m]; v[m] = (double)vb[m]; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-#pragma unroll
-            for (int j = 0; j < VP_TRACK_LAGS; j++) {
-                const double d = v[u] - w[u + j];
-                acc[j] += d * d;
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < 8; m++) w[m] = w[8 + m];
-    }
-    trk_wave_sync();                                                          // (the slice is rewritten below)
-
-    // :395-403: d[0] = 1, tmp += d[k], d[k] *= k / tmp in increasing k -- tmp starts at 0 and 0 + d[1] is d[1], so lag 0 enters as 0
-    if (lane == 0) acc[0] = 0.0;
-    double cum[VP_TRACK_LAGS], carry = 0.0;
-#pragma unroll
-    for (int j = 0; j < VP_TRACK_LAGS; j++) cum[j] = 1.0;
-    const int nOwners = (tauMax + VP_TRACK_LAGS - 1) / VP_TRACK_LAGS;
-    for (int l = 0; l < nOwners; l++) {
-        double t = carry;
-        if (lane == l) {
-#pragma unroll
-            for (int j = 0; j < VP_TRACK_LAGS; j++) { t += acc[j]; cum[j] = t; }
-        }
-        carry = trk_readlane(t, l);
-    }
-    trk_lds_f64 *dn = (trk_lds_f64 *)xs;
-#pragma unroll
-    for (int j = 0; j < VP_TRACK_LAGS; j++) {
-        const int k = VP_TRACK_LAGS * lane + j;
-        const double q = (double)k / cum[j];
-        double y = acc[j] * q;                                                // (silence: 0 * inf = NaN, which fails the tolerance test)
-        if (k == 0) y = 1.0;
-        if (k >= tauMax) y = 0.0;                                             // the guard slot d[tauMax] = 0; lags behind it are not read
-        dn[k] = y;
-    }
-    if (lane == 0) dn[TRK_MAXLAG] = 0.0;                                      // (the guard slot at tauMax = 512)
-    trk_wave_sync();
-
-    // :429-447 on ballots, lag 64 q + lane: under[q] = d[k] < yinTol for tau0 <= k < tauMax, stop[q] = !(d[k + 1] < d[k])
-    unsigned long long under[TRK_MAXLAG / 64], stop[TRK_MAXLAG / 64];
-#pragma unroll
-    for (int q = 0; q < TRK_MAXLAG / 64; q++) {
-        const int k = 64 * q + lane;
-        const double y0 = dn[k], y1 = dn[k + 1];
-        under[q] = __ballot(k >= A.tau0 && k < tauMax && y0 < 0.25);
-        stop[q] = __ballot(!(y1 < y0));
-    }
-    int first = INT_MAX;                                                      // first lag under the tolerance
-#pragma unroll
-    for (int q = TRK_MAXLAG / 64 - 1; q >= 0; q--)
-        if (under[q]) first = 64 * q + (int)__builtin_ctzll(under[q]);
-    int tau = 0;
-    if (first != INT_MAX) {
-        int ks = TRK_MAXLAG;                                                  // first lag >= first at which the descent stops
-#pragma unroll
-        for (int q = TRK_MAXLAG / 64 - 1; q >= 0; q--) {
-            unsigned long long m = stop[q];
-            if (64 * q + 63 < first) m = 0;
-            else if (64 * q < first) m &= ~0ULL << (first - 64 * q);
-            if (m) ks = 64 * q + (int)__builtin_ctzll(m);
-        }
-        // the walk leaves at tauMax - 1 without looking further (:438-439); started there, it looks once, at the guard slot
-        if (first + 1 >= tauMax) tau = ks > first ? first + 1 : first;
-        else tau = ks < tauMax - 1 ? ks : tauMax - 1;
-    }
-    tau = __builtin_amdgcn_readfirstlane(tau);
-
-    double ratio = 1.0;
-    if (tau > 0) {
-        // Notes::getClosestFreq (Notes.cpp:79-110): lower_bound = entries below the pitch; idx == size reads the popped slot (:99)
-        const double pitch = A.fs / tau;
-        const int idx = __builtin_amdgcn_readfirstlane(__popcll(__ballot(lane < notesN && nf0 < pitch)) + __popcll(__ballot(lane + 64 < notesN && nf1 < pitch)));
-        const double fi = idx >= 64 ? trk_readlane(nf1, idx & 63) : trk_readlane(nf0, idx & 63);
-        double closest = fi;
-        if (idx > 0) {
-            const int im = idx - 1;
-            const double fim = im >= 64 ? trk_readlane(nf1, im & 63) : trk_readlane(nf0, im & 63);
-            if (!(fabs(fi - pitch) <= fabs(fim - pitch))) closest = fim;
-        }
-        ratio = closest / pitch;                                              // :595-596
-    }
+#include "vp_track_body.inc"
     if (lane == 0) {
         if (A.period) A.period[g] = tau;
         if (A.ratio) A.ratio[g] = ratio;
@@ -185,5 +94,137 @@ hipError_t vp_track_launch(const VpTrackArgs &a, hipStream_t st)
     const long long frames = (long long)a.S * a.nFrames;
     const unsigned grid = (unsigned)((frames + VP_TRACK_WAVES - 1) / VP_TRACK_WAVES);
     hipLaunchKernelGGL(vp_k_yin_track, dim3(grid), dim3(64 * VP_TRACK_WAVES), vp_track_lds_bytes(a.F), st, a);
+    return hipGetLastError();
+}
+
+// ---- the streaming tracker: one decision per (block, stream) from the last F + tauMax samples the stream received --------------------
+// The definition is tests/pv_track_stream_reference.py.  vp_k_yin_track_stream is vp_k_yin_track with another gather: window sample p of
+// the decision of block b is the stream's sample n_b - W + p (n_b = count + (b + 1) N, W = F + tauMax), taken from the call's slab when the
+// call brought it and from the stream's ring otherwise.  vp_k_track_follow runs behind it on the same stream: it follows the raw table
+// (hold across unvoiced blocks, glide), advances the counters and only then overwrites the ring with the call's last samples.
+__global__ __launch_bounds__(64 * VP_TRACK_WAVES) void vp_k_yin_track_stream(VpTrackStreamArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char trk_smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int F = A.F, tauMax = A.tauMax, nRows = F / 8 + 64;
+    trk_lds_f32 *xs = (trk_lds_f32 *)(trk_smem + (size_t)wave * trk_wave_bytes(F));
+#ifdef VP_POISON_LDS
+    for (int i = lane; i < nRows * TRK_ROW; i += 64) xs[i] = __builtin_nanf("0x5a5a");
+    trk_wave_sync();
+#endif
+    const long long g = (long long)blockIdx.x * VP_TRACK_WAVES + wave;       // decision of the call: [block][stream]
+    if (g >= (long long)A.S * A.nBlocks) return;
+    const int b = (int)(g / A.S), s = (int)(g - (long long)b * A.S);
+    const int win = F + tauMax, N = A.N;
+    const int jEnd = (b + 1) * N;                                             // the block's end, counted from the call's first sample
+    const long long nb = A.count[s] + jEnd;                                   // ... and from the stream's
+    if (nb < win) {                                                           // not enough history yet: unvoiced, nothing is analysed
+        if (lane == 0) { A.period[g] = 0; A.ratio[g] = 1.0; }
+        return;
+    }
+
+    // the note table of the stream's key: freq[lane], freq[64 + lane]
+    int key = A.key ? A.key[s] : 12;
+    if (key < 0 || key > 12) key = 12;
+    const double *freq = A.notes + (size_t)key * VP_NOTES_STRIDE;
+    const int notesN = A.notesN[key];
+    const double nf0 = freq[lane], nf1 = (lane + 64 < VP_NOTES_STRIDE) ? freq[lane + 64] : 0.0;
+
+    // the window, zeros behind it.  Sample p lies jEnd - win + p samples into the call: in block blk at offset off when that is >= 0
+    // (kept as a floored quotient, K blocks added before the division so that it divides a non-negative number), else in the ring at
+    // slot (nb - win + p) % win = (nb % win + p) % win
+    const int K = (win + N - 1) / N, q64 = 64 / N, r64 = 64 % N;
+    const int jj = jEnd - win + K * N + lane;
+    int blk = jj / N, off = jj - blk * N;
+    blk -= K;
+    const int r0 = (int)(nb % win);
+    const float *ring = A.ring + (size_t)s * win;
+    for (int p = lane; p < nRows * 8; p += 64) {
+        float v = 0.0f;
+        if (p < win) {
+            const int slot = r0 + p < win ? r0 + p : r0 + p - win;
+            v = blk >= 0 ? A.in[((size_t)blk * A.S + s) * N + off] : ring[slot];
+        }
+        xs[p + (p >> 3)] = v;
+        blk += q64; off += r64;
+        if (off >= N) { off -= N; blk++; }
+    }
+    trk_wave_sync();
+
+#include "vp_track_body.inc"
+    if (lane == 0) { A.period[g] = tau; A.ratio[g] = ratio; }
+}
+
+__global__ __launch_bounds__(256) void vp_k_track_follow(VpTrackFollowArgs A)
+{
+    __shared__ int slot0[VP_TRKS_GROUP];
+    const int tid = threadIdx.x, s0 = blockIdx.x * VP_TRKS_GROUP;
+    const int nS = A.S - s0 < VP_TRKS_GROUP ? A.S - s0 : VP_TRKS_GROUP;
+    const int total = A.nBlocks * A.N;                                        // (<= 2^28: checked by the caller)
+    const int cnt = total < A.W ? total : A.W, j0 = total - cnt;              // the call's last cnt samples go to the ring
+    long long n0 = 0;
+    if (tid < nS) {
+        n0 = A.count[s0 + tid];
+        slot0[tid] = (int)((n0 + j0) % A.W);
+    }
+    __syncthreads();                                                          // (every read of the counters lies before this)
+    if (tid < nS) {
+        // one lane per stream walks the blocks: rows of the tables are read across the lanes
+        const int s = s0 + tid;
+        double tgt = A.tgt[s], cur = A.cur[s];
+        int age = A.age[s];
+        for (int b = 0; b < A.nBlocks; b++) {
+            const size_t i = (size_t)b * A.S + s;
+            if (A.period[i] > 0) { tgt = A.ratio[i]; age = 0; }
+            else {
+                if (age < INT_MAX) age++;
+                if (age > A.hold) tgt = 1.0;
+            }
+            if (A.glide == 1.0) cur = tgt;
+            else {
+                const double step = A.glide * (tgt - cur);                    // (product and add separate: -ffp-contract=off)
+                cur = cur + step;
+            }
+            A.ratio[i] = cur;
+        }
+        A.tgt[s] = tgt; A.cur[s] = cur; A.age[s] = age;
+        A.count[s] = n0 + total;
+    }
+    for (int e = tid; e < nS * cnt; e += 256) {
+        const int sl = e / cnt, k = e - sl * cnt, s = s0 + sl;
+        const int j = j0 + k, blk = j / A.N, off = j - blk * A.N;
+        const int slot = slot0[sl] + k < A.W ? slot0[sl] + k : slot0[sl] + k - A.W;
+        A.ring[(size_t)s * A.W + slot] = A.in[((size_t)blk * A.S + s) * A.N + off];
+    }
+}
+
+// a reset stream is a fresh one: no history, follow state (1.0, 0, 1.0)
+__global__ __launch_bounds__(256) void vp_k_track_reset(VpTrackUpdArgs A)
+{
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= A.S) return;
+    bool hit = false;
+    for (int k = 0; k < A.n; k++) hit = hit || A.stream[k] < 0 || A.stream[k] == s;
+    if (hit) { A.count[s] = 0; A.tgt[s] = 1.0; A.cur[s] = 1.0; A.age[s] = 0; }
+}
+
+hipError_t vp_track_stream_launch(const VpTrackStreamArgs &a, hipStream_t st)
+{
+    const long long n = (long long)a.S * a.nBlocks;
+    const unsigned grid = (unsigned)((n + VP_TRACK_WAVES - 1) / VP_TRACK_WAVES);
+    hipLaunchKernelGGL(vp_k_yin_track_stream, dim3(grid), dim3(64 * VP_TRACK_WAVES), vp_track_lds_bytes(a.F), st, a);
+    return hipGetLastError();
+}
+
+hipError_t vp_track_follow_launch(const VpTrackFollowArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(vp_k_track_follow, dim3((a.S + VP_TRKS_GROUP - 1) / VP_TRKS_GROUP), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t vp_track_reset_launch(const VpTrackUpdArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(vp_k_track_reset, dim3((a.S + 255) / 256), dim3(256), 0, st, a);
     return hipGetLastError();
 }

@@ -158,6 +158,15 @@ def load_library():
         L.vp_pv_process_blocks_device.argtypes = [vp, fp, fp, C.c_int, C.c_void_p]
         L.vp_pv_debug_alloc_count.argtypes = [vp]
         L.vp_pv_debug_alloc_count.restype = C.c_long
+    if hasattr(L, "vp_pv_tracker_create"):             # (the streaming pitch tracker; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_pv_tracker_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp)]
+        L.vp_pv_tracker_destroy.argtypes = [vp]
+        L.vp_pv_tracker_debug_alloc_count.argtypes = [vp]
+        L.vp_pv_tracker_debug_alloc_count.restype = C.c_long
+        L.vp_pv_tracker_reset.argtypes = [vp, C.c_int]
+        L.vp_pv_tracker_set_follow.argtypes = [vp, C.c_int, C.c_double]
+        L.vp_pv_tracker_process_blocks_device.argtypes = [vp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.vp_pv_autotune_blocks_device.argtypes = [vp, vp, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.vp_error_string.argtypes = [C.c_int]
     L.vp_error_string.restype = C.c_char_p
     L.vp_last_error.argtypes = [vp]
@@ -528,6 +537,24 @@ def _upload_ratios(tables, semitones, dev):
     return tab
 
 
+def _device_keys(owner, keys, dev):
+    """The key table of a tracker call, or None: a device int32 tensor [S] as it is; host data (an int or S ints) goes into one device
+    table kept on `owner` (owner._key_table), rewritten on torch's current stream."""
+    import torch
+    if keys is None:
+        return None
+    if isinstance(keys, torch.Tensor):
+        assert keys.is_cuda and keys.dtype == torch.int32 and tuple(keys.shape) == (owner.S,) and keys.is_contiguous()
+        return keys
+    k = np.asarray(keys)
+    assert k.dtype.kind in "iu" and k.shape in ((), (owner.S,)), (k.dtype, k.shape)
+    k = np.ascontiguousarray(np.broadcast_to(k, (owner.S,)), dtype=np.int32)
+    if getattr(owner, "_key_table", None) is None:
+        owner._key_table = torch.empty((owner.S,), dtype=torch.int32, device=dev)
+    owner._key_table.copy_(torch.from_numpy(k))
+    return owner._key_table
+
+
 class StftRoundTrip:
     """Standalone batched STFT -> iSTFT (no reference counterpart; see include/vp_amd.h vp_stft_*)."""
 
@@ -651,19 +678,7 @@ class StftRoundTrip:
         """(d_key or None, period, ratio): the call's key table and outputs.  The key table is kept per handle (one device int32 [S],
         rewritten on torch's current stream when `keys` is host data); the outputs are new tensors, the caller's to keep."""
         import torch
-        d_key = None
-        if keys is not None:
-            if isinstance(keys, torch.Tensor):
-                assert keys.is_cuda and keys.dtype == torch.int32 and tuple(keys.shape) == (self.S,) and keys.is_contiguous()
-                d_key = keys
-            else:
-                k = np.asarray(keys)
-                assert k.dtype.kind in "iu" and k.shape in ((), (self.S,)), (k.dtype, k.shape)
-                k = np.ascontiguousarray(np.broadcast_to(k, (self.S,)), dtype=np.int32)
-                if getattr(self, "_key_table", None) is None:
-                    self._key_table = torch.empty((self.S,), dtype=torch.int32, device=dev)
-                self._key_table.copy_(torch.from_numpy(k))
-                d_key = self._key_table
+        d_key = _device_keys(self, keys, dev)
         period = torch.empty((self.S, self.n_frames), dtype=torch.int32, device=dev)
         ratio = torch.empty((self.S, self.n_frames), dtype=torch.float64, device=dev)
         return d_key, period, ratio
@@ -789,12 +804,31 @@ class PhaseVocoderStream:
             return
         self._chk(self.L.vp_pv_process_blocks_device(self.h, d_in.data_ptr(), d_out.data_ptr(), int(n_blocks), C.c_void_p(stream)))
 
-    def run(self, x, blocks_per_call=8, curve=None):
+    def autotune_device(self, tracker, d_in, d_out, n_blocks=1, keys=None, stream=None):
+        """Automatic pitch correction block by block (vp_pv_autotune_blocks_device): `tracker` (a StreamingPitchTracker of the same
+        streams, block size and device) decides one ratio per block and stream from the audio received so far, this stream shifts along
+        that table, both on `stream`; d_out has the bits of tracker.process_device followed by process_device(d_ratio=...).  Returns the
+        tracker's (period, ratio), device tensors [n_blocks][S].  reset() does not reach the tracker: reset both."""
+        import torch
+        shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
+        assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == shape and d_out.is_contiguous()
+        d_key, period, ratio = tracker._tables(keys, int(n_blocks), d_in.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        self._chk(self.L.vp_pv_autotune_blocks_device(self.h, tracker.h, d_in.data_ptr(), d_out.data_ptr(), d_key.data_ptr() if d_key is not None else None,
+                                                      period.data_ptr(), ratio.data_ptr(), int(n_blocks), C.c_void_p(stream)))
+        return period, ratio
+
+    def run(self, x, blocks_per_call=8, curve=None, autotune=None, keys=None):
         """Whole signals float [S][T] -> output aligned with the input, [S][T]: the input padded with `latency` zeros (and up to
         whole blocks), streamed through the device entry point `blocks_per_call` blocks at a time, the first `latency` samples
         dropped.  Continues from the handle's state (reset() first for a fresh start).
         curve: semitones per block, array-like [n] or [n][S] with n >= 1; block b takes row min(b, n - 1) (the padding keeps the last
-        row), through process_device(semitones_per_block=...)."""
+        row), through process_device(semitones_per_block=...).
+        autotune: a StreamingPitchTracker instead -- every call goes through autotune_device(autotune, ..., keys=keys), and the result is
+        (output, period, ratio) with the tracker's tables as numpy arrays [n_blocks][S] (the padding blocks included)."""
+        assert curve is None or autotune is None, "one of curve and autotune"
         import torch
         x = np.asarray(x, dtype=np.float32)
         assert x.ndim == 2 and x.shape[0] == self.S, x.shape
@@ -809,17 +843,22 @@ class PhaseVocoderStream:
         dev = torch.device("cuda", self.device)
         d_in = torch.from_numpy(np.ascontiguousarray(xp.reshape(self.S, nb, N).transpose(1, 0, 2))).to(dev)
         d_out = torch.empty_like(d_in)
-        b = 0
+        b, tables = 0, []
         while b < nb:
             k = min(int(blocks_per_call), nb - b)
-            if curve is None:
+            if autotune is not None:
+                tables.append(self.autotune_device(autotune, d_in[b:b + k], d_out[b:b + k], n_blocks=k, keys=keys))
+            elif curve is None:
                 self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k)
             else:
                 self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k, semitones_per_block=curve[b:b + k])
             b += k
         torch.cuda.synchronize(dev)
         y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, nb * N)
-        return np.ascontiguousarray(y[:, Lat:Lat + T])
+        y = np.ascontiguousarray(y[:, Lat:Lat + T])
+        if autotune is not None:
+            return y, torch.cat([p for p, _ in tables]).cpu().numpy(), torch.cat([r for _, r in tables]).cpu().numpy()
+        return y
 
     def debug_alloc_count(self):
         return self.L.vp_pv_debug_alloc_count(self.h)
@@ -827,6 +866,75 @@ class PhaseVocoderStream:
     def close(self):
         if getattr(self, "h", None):
             self.L.vp_pv_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class StreamingPitchTracker:
+    """Streaming pitch tracker (include/vp_amd.h vp_pv_tracker_*): StftRoundTrip.track_pitch's decision once per block and stream, from the
+    last frame_len + ceil(sample_rate / 100) samples the stream has received (period 0, ratio 1.0 until it has that many), then followed:
+    the last voiced ratio is held for `hold_blocks` unvoiced blocks before the target returns to 1.0, and the ratio moves the fraction
+    `glide` of the way to its target per block (1.0: at once).  frame_len (1024 or 2048) is the tracker's own analysis length.  The ratio
+    table is what PhaseVocoderStream.process_device(d_ratio=...) takes; PhaseVocoderStream.autotune_device runs both."""
+
+    def __init__(self, n_streams, block_size, sample_rate, frame_len=1024, hold_blocks=0, glide=1.0, device=0):
+        try:
+            import torch  # noqa: F401  (process_device() uses torch: load its HIP runtime before the library loads one)
+        except ImportError:
+            pass
+        self.L = load_library()
+        h = C.c_void_p()
+        rc = self.L.vp_pv_tracker_create(int(device), int(n_streams), int(block_size), int(frame_len), float(sample_rate), C.byref(h))
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+        self.h, self.S, self.N, self.F, self.fs, self.device = h, int(n_streams), int(block_size), int(frame_len), float(sample_rate), device
+        if hold_blocks != 0 or glide != 1.0:
+            self.set_follow(hold_blocks, glide)
+
+    def _chk(self, rc):
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+
+    def set_follow(self, hold_blocks, glide):
+        """0 <= hold_blocks <= 2^20 unvoiced blocks the last voiced ratio outlives, 0 < glide <= 1; every stream, from the next call on."""
+        self._chk(self.L.vp_pv_tracker_set_follow(self.h, int(hold_blocks), float(glide)))
+
+    def reset(self, stream=-1):
+        """The stream (-1: all) starts again like a fresh one at the next process call: no history, no held ratio."""
+        self._chk(self.L.vp_pv_tracker_reset(self.h, int(stream)))
+
+    def _tables(self, keys, n_blocks, dev):
+        """(d_key or None, period, ratio) of a call of n_blocks blocks: the key table is kept per handle (one device int32 [S], rewritten
+        on torch's current stream when `keys` is host data); the outputs are new tensors, the caller's to keep."""
+        import torch
+        d_key = _device_keys(self, keys, dev)
+        return d_key, torch.empty((n_blocks, self.S), dtype=torch.int32, device=dev), torch.empty((n_blocks, self.S), dtype=torch.float64, device=dev)
+
+    def process_device(self, d_in, n_blocks=1, keys=None, stream=None):
+        """n_blocks blocks on the device: torch float32 [n_blocks][S][N] (or [S][N] for one block), the slab PhaseVocoderStream takes,
+        enqueued on `stream` (default: the current torch stream) without synchronising.  keys as StftRoundTrip.track_pitch's.  Returns
+        (period, ratio), device tensors int32 / float64 [n_blocks][S]: the period in samples (0 = unvoiced) and the followed ratio."""
+        import torch
+        shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
+        d_key, period, ratio = self._tables(keys, int(n_blocks), d_in.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        self._chk(self.L.vp_pv_tracker_process_blocks_device(self.h, d_in.data_ptr(), d_key.data_ptr() if d_key is not None else None,
+                                                             period.data_ptr(), ratio.data_ptr(), int(n_blocks), C.c_void_p(stream)))
+        return period, ratio
+
+    def debug_alloc_count(self):
+        return self.L.vp_pv_tracker_debug_alloc_count(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vp_pv_tracker_destroy(self.h)
             self.h = None
 
     def __del__(self):
