@@ -351,6 +351,23 @@ int vp_stft_pitch_shift(vp_stft *p, const float *d_in, float *d_out, double semi
  * Used as r = fmin(fmax(r, 0.5), 2.0), so a NaN becomes 0.5.
  * VP_ERR_INVALID_ARG for null pointers, VP_ERR_HIP when the device refused the kernels' LDS size at create. */
 int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream);
+/* vp_stft_pitch_shift_curve with the spectral envelope kept apart from the pitch (kernel vp_k_stft_pv_formant): the formants stay where
+ * they were, or move by a ratio of their own, while the pitch follows d_ratio.  The definition is tests/pv_formant_reference.py.  Per
+ * frame, with m the analysis magnitudes, r the frame's pitch ratio and phi the stream's formant ratio (both clamped to [0.5, 2] as in
+ * vp_stft_pitch_shift_curve):
+ *   L[k] = 0.5 log(m[k]^2 + 1e-12), k <= 512;  c = irfft(L, 1024);  c[n] kept for n < lifter, halved at n = lifter, 0 beyond
+ *   (symmetric);  le = rfft(c).real, the smoothed log envelope;  at(rho)[kk] = le interpolated linearly at clip(kk / rho, 0, 512);
+ *   every gathered synthesis magnitude is multiplied by exp(clip(at(phi)[kk] - at(r)[kk], -ln 16, ln 16)).
+ * phi = 1 preserves the formants, phi = 2^(st / 12) moves them by st semitones, phi = r gives vp_stft_pitch_shift_curve's bits.  The
+ * correction has no state across frames.  1024-point frames, every hop, always double, one workgroup per stream, no allocation.
+ * d_ratio: device double [n_streams][vp_stft_num_frames(p)]; d_formant: device double [n_streams] or NULL = 1.0 everywhere;
+ * lifter: VP_FORMANT_LIFTER_MIN .. VP_FORMANT_LIFTER_MAX samples (callers default it to 32).  The tables are read when the kernel runs.
+ * VP_ERR_INVALID_ARG (null handle, input, output or ratio table; lifter out of range) and VP_ERR_GEOMETRY (a 2048-point handle: that
+ * build is not made) are reported before the device is touched and vp_stft_last_error says which; VP_ERR_HIP as vp_stft_pitch_shift. */
+#define VP_FORMANT_LIFTER_MIN 4
+#define VP_FORMANT_LIFTER_MAX 64
+int vp_stft_pitch_shift_formant(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, const double *d_formant, int lifter,
+                                void *hip_stream);
 /* pow(2, st / 12) exactly as vp_stft_pitch_shift / vp_pv_set_semitones compute it (same bits).
  * VP_ERR_INVALID_ARG if an entry is outside +-12 or not finite; nothing is written then.  Host arrays; no device is touched. */
 int vp_semitones_to_ratios(const double *semitones, double *ratios, long n);
@@ -394,7 +411,11 @@ int vp_stft_track_pitch(vp_stft *p, const float *d_in, double sample_rate, const
  * calls.  d_ratio is required (result and scratch), d_period optional.  Both frame lengths, every hop.  Errors as the two calls'. */
 int vp_stft_autotune(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int *d_period, double *d_ratio,
                      void *hip_stream);
-/* The message of the last tracker / autotune call that failed on this handle ("" before any; the pointer is valid until the next call). */
+/* vp_stft_track_pitch followed by vp_stft_pitch_shift_formant along its table, on the same stream: the bits of those two calls.
+ * Arguments as vp_stft_autotune's plus d_formant and lifter; errors as the two calls', all before the device is touched. */
+int vp_stft_autotune_formant(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int *d_period, double *d_ratio,
+                             const double *d_formant, int lifter, void *hip_stream);
+/* The message of the last tracker / autotune / formant call that failed on this handle ("" before any; the pointer is valid until the next call). */
 const char *vp_stft_last_error(const vp_stft *p);
 int vp_stft_is_fused(const vp_stft *p);                      /* 1 (every handle runs the fused kernel; kept for older callers) */
 /* Diagnostic: cut every stream into this many runs of frames (one workgroup each) instead of choosing from the batch size
@@ -449,6 +470,13 @@ int vp_pv_process_blocks_device(vp_pv *p, const float *d_in, float *d_out, int n
  * used nor changed by this call: it is stored as usual and holds again from the next plain call on.  The table is read when the kernel
  * runs: keep it unchanged until then.  No allocation. */
 int vp_pv_process_blocks_curve_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream);
+/* vp_pv_process_blocks_curve_device with vp_stft_pitch_shift_formant's correction (kernel vp_k_pv_stream_formant): d_formant device
+ * double [S] or NULL = 1.0, lifter as there (VP_ERR_INVALID_ARG outside 4 .. 64, before the device is touched).  The stream's state
+ * record, latency and call bookkeeping are the curve call's, so formant, curve and plain calls mix freely on one handle; pending resets
+ * and interval changes behave exactly as in a curve call.  The output, less the latency, is bit-identical to vp_stft_pitch_shift_formant
+ * on the concatenated input with the table expanded per frame.  No allocation. */
+int vp_pv_process_blocks_formant_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, const double *d_formant, int lifter,
+                                        int n_blocks, void *hip_stream);
 long vp_pv_debug_alloc_count(const vp_pv *p);                           /* constant across process calls */
 
 /* Streaming pitch tracker and automatic correction for the stream above (kernels vp_k_yin_track_stream and vp_k_track_follow,
@@ -487,6 +515,10 @@ int vp_pv_tracker_process_blocks_device(vp_pv_tracker *t, const float *d_in, con
  * that restarts a stream resets both. */
 int vp_pv_autotune_blocks_device(vp_pv *p, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, int *d_period, double *d_ratio,
                                  int n_blocks, void *hip_stream);
+/* vp_pv_tracker_process_blocks_device followed by vp_pv_process_blocks_formant_device along its table, on the same stream: the bits of
+ * those two calls.  Arguments as vp_pv_autotune_blocks_device's plus d_formant and lifter. */
+int vp_pv_autotune_blocks_formant_device(vp_pv *p, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, int *d_period,
+                                         double *d_ratio, const double *d_formant, int lifter, int n_blocks, void *hip_stream);
 
 const char *vp_error_string(int code);
 const char *vp_last_error(const vp_handle *h);

@@ -420,6 +420,21 @@ public:
     {
         check(vp_pv_autotune_blocks_device(p_, tracker.handle(), dIn, dOut, dKey, dPeriod, dRatio, nBlocks, hipStream), "autotuneBlocks");
     }
+    // processBlocksCurve with the spectral envelope kept apart from the pitch (vp_pv_process_blocks_formant_device): dFormant device double
+    // [S] of formant ratios, or null = 1.0 (the formants stay where they were); lifter: the cepstral lifter's length, 4 .. 64 samples.
+    // The stream's state is the curve call's: formant, curve and plain calls mix freely
+    void processBlocksFormant(const float *dIn, float *dOut, const double *dRatio, const double *dFormant, int nBlocks, int lifter = 32,
+                              void *hipStream = nullptr)
+    {
+        check(vp_pv_process_blocks_formant_device(p_, dIn, dOut, dRatio, dFormant, lifter, nBlocks, hipStream), "processBlocksFormant");
+    }
+    // automatic correction that keeps the formants: the tracker's call, then processBlocksFormant along its table
+    void autotuneBlocks(StreamingPitchTracker &tracker, const float *dIn, float *dOut, const int *dKey, int *dPeriod, double *dRatio,
+                        const double *dFormant, int lifter, int nBlocks, void *hipStream = nullptr)
+    {
+        check(vp_pv_autotune_blocks_formant_device(p_, tracker.handle(), dIn, dOut, dKey, dPeriod, dRatio, dFormant, lifter, nBlocks, hipStream),
+              "autotuneBlocks (formant)");
+    }
     vp_pv *handle() const { return p_; }
 
 private:

@@ -1880,7 +1880,8 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     // (hipFuncSetAttribute acts on the current device).  Only vp_stft_pitch_shift needs it, so a failure is remembered and fails
     // THAT call; the plain and single-precision round trips (<= 64 KB) are served regardless.  The sticky HIP error is cleared so
     // that a later hipGetLastError() behind a launch does not report this one.
-    p->pvOk = vp_stft_prepare_device() == hipSuccess && vp_stft_curve_prepare_device() == hipSuccess && vp_stft_stretch_prepare_device() == hipSuccess;
+    p->pvOk = vp_stft_prepare_device() == hipSuccess && vp_stft_curve_prepare_device() == hipSuccess && vp_stft_stretch_prepare_device() == hipSuccess
+        && vp_stft_formant_prepare_device() == hipSuccess;
     if (!p->pvOk) (void)hipGetLastError();
     p->device = device; p->F = frame_len; p->hop = hop; p->S = n_streams; p->T = n_samples;
     p->nFrames = (n_samples - frame_len) / hop + 1;
@@ -1958,9 +1959,10 @@ extern "C" int vp_stft_set_precision(vp_stft *p, int precision)
 extern "C" int vp_stft_get_precision(const vp_stft *p) { return p ? (p->f32 ? VP_STFT_F32 : VP_STFT_F64) : VP_ERR_INVALID_ARG; }
 
 // (d_ratio: the phase-vocoder stage reads its ratio per frame from this table, `ratio` is unused then; d_pos: it reads frame f at input
-// sample d_pos[s][f] of rows of n_in samples -- the time stretch)
+// sample d_pos[s][f] of rows of n_in samples -- the time stretch; lifter > 0: the ratio-curve build with the formant correction, d_formant
+// [S] or null)
 static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag, hipStream_t st, bool pv, double ratio, const double *d_ratio = nullptr,
-                      const int *d_pos = nullptr, int n_in = 0)
+                      const int *d_pos = nullptr, int n_in = 0, const double *d_formant = nullptr, int lifter = 0)
 {
     VpStftArgs a;
     memset(&a, 0, sizeof a);
@@ -1985,6 +1987,7 @@ static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
     }
     a.roundsPerRun = (a.nRounds + runs - 1) / runs;
     const int nRuns = (a.nRounds + a.roundsPerRun - 1) / a.roundsPerRun;
+    if (d_ratio && lifter > 0) return vp_stft_launch_formant(a, d_ratio, d_formant, lifter, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     if (d_ratio) return vp_stft_launch_curve(a, d_ratio, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     if (d_pos) return vp_stft_launch_stretch(a, d_pos, n_in, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     return vp_stft_launch(a, p->S, nRuns, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
@@ -2014,6 +2017,31 @@ extern "C" int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d
     if (!p->pvOk) return VP_ERR_HIP;                           // (as vp_stft_pitch_shift)
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio);
+}
+
+// every argument of a formant call that the curve call does not have, checked before the device is touched
+static int formant_check(vp_stft *p, int lifter)
+{
+    if (lifter < VP_FORMANT_LIFTER_MIN || lifter > VP_FORMANT_LIFTER_MAX) { p->lastError = "formant: lifter outside 4 .. 64 samples"; return VP_ERR_INVALID_ARG; }
+    if (p->F != 1024) {
+        p->lastError = "formant: 2048-point frames are not built (the envelope needs a wavefront's exchange buffer to hold the frame's 1025 bins; it holds 1024 doubles)";
+        return VP_ERR_GEOMETRY;
+    }
+    return VP_OK;
+}
+
+// vp_stft_pitch_shift_curve with the cepstral formant correction: d_formant [S] formant ratios or NULL (1.0: the envelope stays where it
+// was), lifter the cepstral lifter's length in samples (vp_k_stft_pv_formant; 1024-point frames)
+extern "C" int vp_stft_pitch_shift_formant(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, const double *d_formant, int lifter,
+                                           void *hip_stream)
+{
+    if (!p) return VP_ERR_INVALID_ARG;
+    if (!d_in || !d_out || !d_ratio) { p->lastError = "formant: null input, output or ratio table"; return VP_ERR_INVALID_ARG; }
+    const int rc = formant_check(p, lifter);
+    if (rc) return rc;
+    if (!p->pvOk) { p->lastError = "formant: the device refused the phase-vocoder kernels' LDS size at create"; return VP_ERR_HIP; }   // (as vp_stft_pitch_shift)
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio, nullptr, 0, d_formant, lifter);
 }
 
 // the time stretch: frame f of stream s is read at input sample d_pos[s][f] (clamped by the kernel) of d_in [S][n_in] and written at output
@@ -2100,6 +2128,22 @@ extern "C" int vp_stft_autotune(vp_stft *p, const float *d_in, float *d_out, dou
     return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio);
 }
 
+// the tracker, then vp_stft_pitch_shift_formant along its table, on the same stream
+extern "C" int vp_stft_autotune_formant(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int *d_period, double *d_ratio,
+                                        const double *d_formant, int lifter, void *hip_stream)
+{
+    if (p && (!d_out || !d_ratio)) { p->lastError = "autotune: null output or ratio table (the table is result and scratch)"; return VP_ERR_INVALID_ARG; }
+    int rc = track_check(p, d_in, sample_rate, d_period, d_ratio);
+    if (rc) return rc;
+    rc = formant_check(p, lifter);
+    if (rc) return rc;
+    if (!p->pvOk) { p->lastError = "autotune: the device refused the phase-vocoder kernels' LDS size at create"; return VP_ERR_HIP; }   // (as vp_stft_pitch_shift)
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    rc = track_launch(p, d_in, sample_rate, d_key, d_period, d_ratio, (hipStream_t)hip_stream);
+    if (rc) return rc;
+    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio, nullptr, 0, d_formant, lifter);
+}
+
 // ---- streaming phase vocoder (no reference counterpart): vp_k_pv_stream of vp_stft.hip, the one-shot stage block by block -----------
 struct vp_pv {
     int device = 0, S = 0, N = 0, F = 0, hop = 0, L = 0;
@@ -2133,7 +2177,7 @@ extern "C" int vp_pv_create(int device, int n_streams, int block_size, int frame
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VP_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    if (vp_pv_prepare_device() != hipSuccess || vp_pv_curve_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
+    if (vp_pv_prepare_device() != hipSuccess || vp_pv_curve_prepare_device() != hipSuccess || vp_pv_formant_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
     vp_pv *p = new vp_pv();
     p->device = device; p->S = n_streams; p->N = block_size; p->F = frame_len; p->hop = hop;
     int g = block_size, b = hop;
@@ -2210,8 +2254,10 @@ extern "C" int vp_pv_reset(vp_pv *p, int stream)
 
 // the pending changes travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update launches in front of it): ordered on
 // the caller's stream, no host memory the device reads later, no allocation
-// (d_ratio: one ratio per block and stream for this call, [n_blocks][S]; the pending changes travel and are stored as in any call)
-static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipStream_t st, const double *d_ratio = nullptr)
+// (d_ratio: one ratio per block and stream for this call, [n_blocks][S]; the pending changes travel and are stored as in any call;
+// lifter > 0: the curve call with the formant correction, d_formant [S] or null)
+static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipStream_t st, const double *d_ratio = nullptr, const double *d_formant = nullptr,
+                  int lifter = 0)
 {
     p->upd.clear();
     if (p->allRatio > 0.0 || p->allReset) p->upd.push_back(VpPvUpdate{-1, p->allReset ? 1 : 0, p->allRatio});
@@ -2230,7 +2276,8 @@ static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipSt
     }
     a.in = d_in; a.out = d_out; a.nBlocks = n_blocks; a.nUpd = (int)(p->upd.size() - i);
     for (int k = 0; k < a.nUpd; k++) a.upd[k] = p->upd[i + k];
-    if ((d_ratio ? vp_pv_launch_curve(a, d_ratio, st) : vp_pv_launch(a, st)) != hipSuccess) return VP_ERR_HIP;
+    if ((d_ratio && lifter > 0 ? vp_pv_launch_formant(a, d_ratio, d_formant, lifter, st) : d_ratio ? vp_pv_launch_curve(a, d_ratio, st) : vp_pv_launch(a, st)) != hipSuccess)
+        return VP_ERR_HIP;
     p->allRatio = 0.0; p->allReset = false;
     std::fill(p->ratioPend.begin(), p->ratioPend.end(), 0.0);
     std::fill(p->resetPend.begin(), p->resetPend.end(), 0);
@@ -2249,6 +2296,16 @@ extern "C" int vp_pv_process_blocks_curve_device(vp_pv *p, const float *d_in, fl
     if (!p || !d_in || !d_out || !d_ratio || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio);
+}
+
+// the curve call with the cepstral formant correction (vp_k_pv_stream_formant): d_formant [S] or NULL (1.0), lifter in samples
+extern "C" int vp_pv_process_blocks_formant_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, const double *d_formant, int lifter,
+                                                   int n_blocks, void *hip_stream)
+{
+    if (!p || !d_in || !d_out || !d_ratio || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
+    if (lifter < VP_FORMANT_LIFTER_MIN || lifter > VP_FORMANT_LIFTER_MAX) return VP_ERR_INVALID_ARG;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio, d_formant, lifter);
 }
 
 extern "C" int vp_pv_process_block(vp_pv *p, const float *in, float *out)
@@ -2420,4 +2477,18 @@ extern "C" int vp_pv_autotune_blocks_device(vp_pv *p, vp_pv_tracker *t, const fl
     rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
     if (rc) return rc;
     return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio);
+}
+
+// the tracker call, then vp_pv_process_blocks_formant_device along its table, on the same stream
+extern "C" int vp_pv_autotune_blocks_formant_device(vp_pv *p, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, int *d_period,
+                                                    double *d_ratio, const double *d_formant, int lifter, int n_blocks, void *hip_stream)
+{
+    if (!p || !d_out || !d_ratio || lifter < VP_FORMANT_LIFTER_MIN || lifter > VP_FORMANT_LIFTER_MAX) return VP_ERR_INVALID_ARG;
+    int rc = trks_check(t, d_in, d_period, d_ratio, n_blocks);
+    if (rc) return rc;
+    if (p->S != t->S || p->N != t->N || p->device != t->device) return VP_ERR_GEOMETRY;
+    if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
+    if (rc) return rc;
+    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio, d_formant, lifter);
 }

@@ -43,6 +43,10 @@ hipError_t vp_stft_curve_prepare_device();
 // their dynamic-LDS ceiling, as above
 hipError_t vp_stft_launch_stretch(const VpStftArgs &a, const int *d_pos, int nIn, int nStreams, hipStream_t st);
 hipError_t vp_stft_stretch_prepare_device();
+// the 1024-point ratio-curve build with the cepstral formant correction (vp_k_stft_pv_formant; csrc/vp_stft_formant.inc): d_ratio as in
+// vp_stft_launch_curve, d_formant [nStreams] formant ratios or nullptr (1), nc the lifter length in samples (4 .. 64); a.F == 1024
+hipError_t vp_stft_launch_formant(const VpStftArgs &a, const double *d_ratio, const double *d_formant, int nc, int nStreams, hipStream_t st);
+hipError_t vp_stft_formant_prepare_device();
 
 // ---- streaming phase vocoder (vp_pv_*): one workgroup per stream and call, state in HBM between calls -----------------------------
 #define VP_PV_MAX_UPDATES 16            // interval changes / resets carried in a process call's arguments
@@ -80,3 +84,6 @@ hipError_t vp_pv_prepare_device();
 // the streaming kernel with one ratio per block and stream, d_ratio [a.nBlocks][a.S] (vp_k_pv_stream_curve; a.nBlocks > 0)
 hipError_t vp_pv_launch_curve(const VpPvArgs &a, const double *d_ratio, hipStream_t st);
 hipError_t vp_pv_curve_prepare_device();
+// ... and with the cepstral formant correction (vp_k_pv_stream_formant): d_formant [a.S] or nullptr (1), nc the lifter length (4 .. 64)
+hipError_t vp_pv_launch_formant(const VpPvArgs &a, const double *d_ratio, const double *d_formant, int nc, hipStream_t st);
+hipError_t vp_pv_formant_prepare_device();

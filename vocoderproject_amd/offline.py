@@ -212,16 +212,19 @@ def glide_curve(lens, start, end, N, n_blocks):
     return c
 
 
-def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, processor=None):
+def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, processor=None, formant=None, lifter=32):
     """pv_shift with a glide: every recording's interval moves linearly from `start` to `end` semitones over its length, one value per
     block, through the streaming phase vocoder's ratio-curve call (PhaseVocoderStream.run(curve=...): several blocks per call, each
     with its own interval).  Returns float32 [2][len] per recording.  `processor` (tests): an object with latency and
-    run(x, blocks_per_call, curve) to use instead of a new PhaseVocoderStream."""
+    run(x, blocks_per_call, curve) to use instead of a new PhaseVocoderStream.  formant (semitones; None: the call above, unchanged): the
+    formant-preserving call instead -- the spectral envelope moves by `formant` semitones (0: it stays) whatever the pitch does, with a
+    cepstral lifter of `lifter` samples; run then also receives formant_semitones and lifter."""
     S = len(voices)
     if S == 0:
         raise ValueError("no recordings")
     if not (-12.0 <= float(start) <= 12.0 and -12.0 <= float(end) <= 12.0):
         raise ValueError("glide: intervals within +-12 semitones expected")
+    _check_formant(formant, lifter)
     p = processor
     if p is None:
         from . import PhaseVocoderStream
@@ -235,7 +238,75 @@ def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, 
             raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
         x[s, :lens[s]] = v
     curve = glide_curve(lens, start, end, N, -(-(T + int(p.latency)) // int(N)))
-    y = p.run(x, blocks_per_call=int(blocks_per_call), curve=curve)           # aligned with the input: the latency is off
+    kw = {} if formant is None else dict(formant_semitones=float(formant), lifter=int(lifter))
+    y = p.run(x, blocks_per_call=int(blocks_per_call), curve=curve, **kw)     # aligned with the input: the latency is off
+    return [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
+
+
+def _check_formant(formant, lifter):
+    if formant is not None and not -12.0 <= float(formant) <= 12.0:
+        raise ValueError("formant: an interval within +-12 semitones expected")
+    if formant is not None and not 4 <= int(lifter) <= 64:
+        raise ValueError("lifter: 4 to 64 samples expected")
+
+
+class _FormantShiftRunner:
+    """StftRoundTrip.pitch_shift_formant from host arrays: x float32 [S][T], semitones [S] -> float32 [S][T]."""
+
+    def __init__(self, hop, device):
+        self.hop, self.device = int(hop), device
+
+    def run(self, x, semitones, formant, lifter):
+        import torch
+        from . import StftRoundTrip
+        dev = torch.device("cuda", self.device)
+        st = StftRoundTrip(x.shape[0], x.shape[1], 1024, self.hop, device=self.device)
+        try:
+            d_in = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
+            d_out = torch.empty_like(d_in)
+            st.pitch_shift_formant(d_in, d_out, semitones=np.asarray(semitones, np.float64).reshape(-1, 1) * np.ones((1, st.n_frames)),
+                                   formant_semitones=float(formant), lifter=int(lifter))
+            torch.cuda.synchronize(dev)
+            return d_out.cpu().numpy()
+        finally:
+            st.close()
+
+
+def pv_shift_formant(voices, shift, formant=0.0, lifter=32, N=1024, hop=256, device=0, stream=False, blocks_per_call=16, processor=None):
+    """pv_shift with the spectral envelope kept apart from the pitch: the pitch moves by `shift` semitones (one value or one per recording),
+    the formants by `formant` (0: they stay where they were), through a cepstral envelope with a lifter of `lifter` samples (4 .. 64).
+    Batch (default): the one-shot call StftRoundTrip.pitch_shift_formant on the recordings padded to a common length under the full
+    overlap of 1024-point frames; stream: block by block through PhaseVocoderStream.run(curve=..., formant_semitones=...), as pv_glide
+    runs.  Returns float32 [2][len] per recording.  `processor` (tests): an object with run(x, semitones, formant, lifter) (batch) or
+    latency and run(x, blocks_per_call, curve, formant_semitones, lifter) (stream) to use instead of the GPU."""
+    S = len(voices)
+    if S == 0:
+        raise ValueError("no recordings")
+    per = [float(v) for v in shift] if isinstance(shift, (list, tuple, np.ndarray)) else [float(shift)] * S
+    if len(per) != S:
+        raise ValueError("shift: one value per recording expected")
+    if not all(-12.0 <= v <= 12.0 for v in per):
+        raise ValueError("shift: intervals within +-12 semitones expected")
+    _check_formant(formant, lifter)
+    N, hop = int(N), int(hop)
+    lens = [int(np.asarray(v).shape[-1]) for v in voices]
+    p = processor
+    if stream and p is None:
+        from . import PhaseVocoderStream
+        p = PhaseVocoderStream(S, N, hop=hop, device=device)
+    T = max(lens) if stream else 1024 + -(-max(lens) // hop) * hop             # batch: every sample under the full overlap of frames
+    x = np.zeros((S, T), np.float32)
+    for s, v in enumerate(voices):
+        v = np.asarray(v, np.float32)
+        if v.ndim != 1:
+            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
+        x[s, :lens[s]] = v
+    if stream:
+        y = p.run(x, blocks_per_call=int(blocks_per_call), curve=np.array([per]), formant_semitones=float(formant), lifter=int(lifter))
+    else:
+        if p is None:
+            p = _FormantShiftRunner(hop, device)
+        y = p.run(x, per, float(formant), int(lifter))
     return [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
 
 
@@ -302,7 +373,7 @@ class _AutotuneRunner:
     def __init__(self, F, hop, device):
         self.F, self.hop, self.device = int(F), int(hop), device
 
-    def run(self, x, fs, keys):
+    def run(self, x, fs, keys, formant=None, lifter=32):
         import torch
         from . import StftRoundTrip
         dev = torch.device("cuda", self.device)
@@ -310,7 +381,7 @@ class _AutotuneRunner:
         try:
             d_in = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
             d_out = torch.empty_like(d_in)
-            period, ratio = st.autotune(d_in, d_out, float(fs), keys=[int(k) for k in keys])
+            period, ratio = st.autotune(d_in, d_out, float(fs), keys=[int(k) for k in keys], formant_semitones=formant, lifter=int(lifter))
             torch.cuda.synchronize(dev)
             return d_out.cpu().numpy(), period.cpu().numpy(), ratio.cpu().numpy()
         finally:
@@ -324,12 +395,14 @@ def tune_length(max_len, fs, F, hop):
     return max(F + -(-int(max_len) // hop) * hop, F + int(np.ceil(float(fs) / 100.0)))
 
 
-def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, with_track=False):
+def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, with_track=False, formant=None, lifter=32):
     """A batch of recordings through the pitch tracker and the one-shot phase vocoder (StftRoundTrip.autotune: one stream per recording):
     every frame is moved onto the nearest note of its recording's key.  key: Notes::key 0..12 (12 = chromatic), one value or one per
     recording.  The recordings are zero-padded to a common length (tune_length).  Returns float32 [2][len] per recording (the corrected
     signal on both channels); with_track: also period int32 [S][nF] and ratio float64 [S][nF] of the padded batch.  `processor` (tests): an
-    object with run(x, fs, keys) to use instead of the GPU."""
+    object with run(x, fs, keys) to use instead of the GPU.  formant (semitones; None: the correction above, unchanged): the correction
+    keeps the spectral envelope apart from the pitch (StftRoundTrip.autotune(formant_semitones=...); 1024-point frames) -- 0 leaves the
+    singer's formants where they were; lifter: the cepstral lifter, 4 .. 64 samples; run then also receives formant and lifter."""
     S = len(voices)
     if S == 0:
         raise ValueError("no recordings")
@@ -340,6 +413,9 @@ def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, w
         raise ValueError("key: 0..12 expected (12 = chromatic)")
     if not 8000.0 <= float(fs) <= 51200.0:
         raise ValueError("pvtune: sample rates from 8000 to 51200 Hz are served")
+    _check_formant(formant, lifter)
+    if formant is not None and int(F) != 1024:
+        raise ValueError("pvtune --formant: 1024-point frames expected (the formant kernels are not built for 2048)")
     lens = [int(np.asarray(v).shape[-1]) for v in voices]
     T = tune_length(max(lens), fs, F, hop)
     x = np.zeros((S, T), np.float32)
@@ -349,7 +425,8 @@ def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, w
             raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
         x[s, :lens[s]] = v
     p = processor if processor is not None else _AutotuneRunner(F, hop, device)
-    y, period, ratio = p.run(x, float(fs), keys)
+    kw = {} if formant is None else dict(formant=float(formant), lifter=int(lifter))
+    y, period, ratio = p.run(x, float(fs), keys, **kw)
     outs = [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
     return (outs, period, ratio) if with_track else outs
 
@@ -361,7 +438,7 @@ class _StreamTuneRunner:
     def __init__(self, N, hop, F, hold, glide, device, blocks_per_call=16):
         self.N, self.hop, self.F, self.hold, self.glide, self.device, self.k = int(N), int(hop), int(F), int(hold), float(glide), device, int(blocks_per_call)
 
-    def run(self, x, fs, keys):
+    def run(self, x, fs, keys, formant=None, lifter=32):
         import torch
         from . import PhaseVocoderStream, StreamingPitchTracker
         S, N = x.shape[0], self.N
@@ -372,7 +449,8 @@ class _StreamTuneRunner:
         try:
             d_in = torch.from_numpy(np.ascontiguousarray(x.reshape(S, nb, N).transpose(1, 0, 2), np.float32)).to(dev)
             d_out = torch.empty_like(d_in)
-            tables = [pv.autotune_device(trk, d_in[b:b + self.k], d_out[b:b + self.k], n_blocks=min(self.k, nb - b), keys=[int(k) for k in keys])
+            tables = [pv.autotune_device(trk, d_in[b:b + self.k], d_out[b:b + self.k], n_blocks=min(self.k, nb - b), keys=[int(k) for k in keys],
+                                         formant_semitones=formant, lifter=int(lifter))
                       for b in range(0, nb, self.k)]
             torch.cuda.synchronize(dev)
             y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(S, nb * N)
@@ -390,14 +468,15 @@ def stream_tune_length(max_len, N, hop):
     return -(-(int(max_len) + lat) // int(N)) * int(N), lat
 
 
-def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glide=1.0, device=0, processor=None, with_track=False):
+def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glide=1.0, device=0, processor=None, with_track=False, formant=None,
+                       lifter=32):
     """pv_autotune block by block, as a live caller would run it: the streaming tracker (StreamingPitchTracker, analysis length F) decides
     one ratio per block of N samples from the audio received so far, holds the last voiced ratio for `hold` unvoiced blocks and moves the
     fraction `glide` of the way to its target per block; the streaming phase vocoder (1024-point frames) shifts along that table.  The
     recordings are zero-padded to whole blocks that also hold the shifter's latency, which is taken off the front.  Returns float32
     [2][len] per recording; with_track: also period int32 [n_blocks][S] and ratio float64 [n_blocks][S] of the padded batch.  A decision
     costs the same at every N: N = 64 costs 16 times as much per second of audio as N = 1024.  `processor` (tests): an object with
-    run(x, fs, keys) to use instead of the GPU."""
+    run(x, fs, keys) to use instead of the GPU.  formant, lifter: as pv_autotune's (the shifter's frames are 1024 points whatever F)."""
     S = len(voices)
     if S == 0:
         raise ValueError("no recordings")
@@ -408,6 +487,7 @@ def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glid
         raise ValueError("key: 0..12 expected (12 = chromatic)")
     if not 8000.0 <= float(fs) <= 51200.0:
         raise ValueError("pvtune: sample rates from 8000 to 51200 Hz are served")
+    _check_formant(formant, lifter)
     if int(N) < 1 or int(F) not in (1024, 2048):
         raise ValueError("pvtune --stream: a block of at least one sample and a tracker frame of 1024 or 2048 expected")
     if not (0 <= int(hold) <= 1 << 20 and 0.0 < float(glide) <= 1.0):
@@ -421,7 +501,8 @@ def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glid
             raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
         x[s, :lens[s]] = v
     p = processor if processor is not None else _StreamTuneRunner(N, hop, F, hold, glide, device)
-    y, period, ratio = p.run(x, float(fs), keys)
+    kw = {} if formant is None else dict(formant=float(formant), lifter=int(lifter))
+    y, period, ratio = p.run(x, float(fs), keys, **kw)
     outs = [np.ascontiguousarray(np.stack([y[s, lat:lat + lens[s]]] * 2)) for s in range(S)]
     return (outs, period, ratio) if with_track else outs
 
@@ -451,7 +532,13 @@ def main(argv=None):
     ap.add_argument("--glide", default=None, metavar="A:B",
                     help="pvshift: a linear glide from A to B semitones over each recording, one value per block, instead of --shift; "
                          "pvtune --stream: one number in (0, 1], the fraction of the way to its target the ratio moves per block (default 1)")
-    ap.add_argument("--stream", action="store_true", help="pvtune: block by block through the streaming tracker and phase vocoder (--block, --hold, --glide)")
+    ap.add_argument("--stream", action="store_true", help="pvtune: block by block through the streaming tracker and phase vocoder (--block, --hold, --glide); "
+                                                          "pvshift --formant: block by block instead of the one-shot call")
+    ap.add_argument("--formant", type=float, nargs="?", const=0.0, default=None, metavar="ST",
+                    help="pvshift, pvtune: keep the spectral envelope apart from the pitch and move the formants by ST semitones "
+                         "(no value: 0, they stay where they were).  The value is optional, so put the flag BEHIND the input files or "
+                         "in front of another option: `--formant a.wav` would read a.wav as the interval")
+    ap.add_argument("--lifter", type=int, default=32, help="--formant: length of the cepstral lifter in samples, 4 to 64 (short: a smoother envelope)")
     ap.add_argument("--hold", type=int, default=0, help="pvtune --stream: unvoiced blocks over which the last voiced ratio is kept")
     ap.add_argument("--stretch", type=float, default=None, help="stretch: output duration / input duration, 0.25 to 4 (--shift: semitones on top)")
     ap.add_argument("--frame", type=int, default=1024, help="stretch, pvtune: frame length (1024 or 2048)")
@@ -469,6 +556,9 @@ def main(argv=None):
             argv[i:i + 2] = ["--glide=" + argv[i + 1]]
             break
     a = ap.parse_args(argv)
+    if a.formant is not None and a.flow not in ("pvshift", "pvtune"):
+        raise SystemExit("--formant: pvshift and pvtune take it")
+    fkw = {} if a.formant is None else dict(formant=a.formant, lifter=a.lifter)
 
     recs = [read_wav(f) for f in a.inputs]
     fs = recs[0][0]
@@ -491,10 +581,10 @@ def main(argv=None):
                 except ValueError:
                     raise SystemExit("pvtune --stream --glide: one number in (0, 1] expected")
                 outs, period, ratio = pv_autotune_stream(voices, fs, key=a.key, N=a.block, hop=a.hop, F=a.frame, hold=a.hold, glide=glide,
-                                                         device=a.device, with_track=True)
+                                                         device=a.device, with_track=True, **fkw)
                 period, ratio, step = period.T, ratio.T, a.block                    # a row per block, at the block's start
             else:
-                outs, period, ratio = pv_autotune(voices, fs, key=a.key, F=a.frame, hop=a.hop, device=a.device, with_track=True)
+                outs, period, ratio = pv_autotune(voices, fs, key=a.key, F=a.frame, hop=a.hop, device=a.device, with_track=True, **fkw)
                 step = a.hop
         except ValueError as e:
             raise SystemExit(str(e))
@@ -513,7 +603,15 @@ def main(argv=None):
                 g0, g1 = (float(v) for v in a.glide.split(":"))
             except ValueError:
                 raise SystemExit("--glide: A:B expected, two intervals in semitones")
-            outs = pv_glide(voices, g0, g1, N=a.block, hop=a.hop, device=a.device)
+            try:
+                outs = pv_glide(voices, g0, g1, N=a.block, hop=a.hop, device=a.device, **fkw)     # (a glide is streamed: one interval per block)
+            except ValueError as e:
+                raise SystemExit(str(e))
+        elif a.formant is not None:
+            try:
+                outs = pv_shift_formant(voices, a.shift, N=a.block, hop=a.hop, device=a.device, stream=a.stream, **fkw)
+            except ValueError as e:
+                raise SystemExit(str(e))
         else:
             outs = pv_shift(voices, a.shift, N=a.block, hop=a.hop, device=a.device)
         return _write_outputs(a, fs, outs)

@@ -167,6 +167,11 @@ def load_library():
         L.vp_pv_tracker_set_follow.argtypes = [vp, C.c_int, C.c_double]
         L.vp_pv_tracker_process_blocks_device.argtypes = [vp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.vp_pv_autotune_blocks_device.argtypes = [vp, vp, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "vp_stft_pitch_shift_formant"):      # (the formant entries; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_stft_pitch_shift_formant.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.vp_stft_autotune_formant.argtypes = [vp, fp, fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.vp_pv_process_blocks_formant_device.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.vp_pv_autotune_blocks_formant_device.argtypes = [vp, vp, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.vp_error_string.argtypes = [C.c_int]
     L.vp_error_string.restype = C.c_char_p
     L.vp_last_error.argtypes = [vp]
@@ -555,6 +560,26 @@ def _device_keys(owner, keys, dev):
     return owner._key_table
 
 
+FORMANT_LIFTER = 32                     # the cepstral lifter's default length in samples (VP_FORMANT_LIFTER_MIN .. _MAX = 4 .. 64)
+
+
+def _device_formants(owner, formant_semitones, d_formant, dev):
+    """The formant table of a formant call, or None (the library's NULL: ratio 1.0 everywhere): a device float64 tensor [S] of ratios as
+    it is; intervals (a scalar or S values, each |value| <= 12) go through semitones_to_ratios into one device table kept on `owner`
+    (owner._formant_table), rewritten on torch's current stream."""
+    import torch
+    if d_formant is not None:
+        assert d_formant.is_cuda and d_formant.dtype == torch.float64 and tuple(d_formant.shape) == (owner.S,) and d_formant.is_contiguous()
+        return d_formant
+    st = np.asarray(0.0 if formant_semitones is None else formant_semitones, dtype=np.float64)
+    assert st.shape in ((), (owner.S,)), st.shape
+    r = semitones_to_ratios(np.ascontiguousarray(np.broadcast_to(st, (owner.S,))))
+    if getattr(owner, "_formant_table", None) is None:
+        owner._formant_table = torch.empty((owner.S,), dtype=torch.float64, device=dev)
+    owner._formant_table.copy_(torch.from_numpy(r))
+    return owner._formant_table
+
+
 class StftRoundTrip:
     """Standalone batched STFT -> iSTFT (no reference counterpart; see include/vp_amd.h vp_stft_*)."""
 
@@ -635,6 +660,31 @@ class StftRoundTrip:
         if rc:
             raise VpError(rc, self.L.vp_error_string(rc).decode())
 
+    def pitch_shift_formant(self, d_in, d_out, semitones=None, stream=None, d_ratio=None, formant_semitones=0.0, lifter=FORMANT_LIFTER, d_formant=None):
+        """pitch_shift_curve with the spectral envelope kept apart from the pitch (vp_stft_pitch_shift_formant; 1024-point frames): the
+        formants stay where they were (formant_semitones = 0, the default) or move by an interval of their own, a scalar or [S] values,
+        |value| <= 12 (d_formant instead: a device float64 tensor [S] of ratios, used as it is).  `semitones`: a scalar, [S] (one interval
+        per stream; with S == n_frames a vector is a curve), [n_frames] or [S][n_frames]; d_ratio as in pitch_shift_curve -- the same
+        table-building path.  lifter: length of the cepstral lifter in samples, 4 .. 64 (short: a smoother envelope)."""
+        import torch
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
+        assert d_out.is_cuda and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
+        assert (semitones is None) != (d_ratio is None), "one of semitones and d_ratio"
+        if d_ratio is None:
+            st = np.asarray(semitones, dtype=np.float64)
+            if st.shape == (self.S,) and self.S != self.n_frames:
+                st = st[:, None]
+            assert st.shape in ((), (self.S, 1), (self.n_frames,), (self.S, self.n_frames)), st.shape
+            if not hasattr(self, "_curve_tables"):
+                self._curve_tables = {}
+            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(st, (self.S, self.n_frames)), d_in.device)
+        assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (self.S, self.n_frames) and d_ratio.is_contiguous()
+        d_formant = _device_formants(self, formant_semitones, d_formant, d_in.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        self._track_chk(self.L.vp_stft_pitch_shift_formant(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), d_formant.data_ptr(), int(lifter),
+                                                           C.c_void_p(stream)))
+
     def time_stretch(self, d_in, d_out, positions=None, stretch=None, semitones=0.0, stream=None, d_pos=None):
         """Time stretch (vp_stft_time_stretch): pitch_shift with frame f of stream s analysed at input sample positions[s][f] and written
         at output sample f hop, so duration and pitch are independent.  d_in is float32 [S][n_in] with any n_in >= frame_len, d_out
@@ -704,15 +754,23 @@ class StftRoundTrip:
                                                    period.data_ptr(), ratio.data_ptr(), C.c_void_p(stream)))
         return period, ratio
 
-    def autotune(self, d_in, d_out, sample_rate, keys=None, stream=None):
+    def autotune(self, d_in, d_out, sample_rate, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER):
         """Automatic pitch correction (vp_stft_autotune): track_pitch, then pitch_shift_curve along its ratios, on one stream; d_out has
-        the bits of those two calls.  Returns track_pitch's (period, ratio)."""
+        the bits of those two calls.  Returns track_pitch's (period, ratio).
+        formant_semitones (a scalar or [S]; None: the call above, unchanged): the correction runs through pitch_shift_formant instead
+        (vp_stft_autotune_formant) -- 0 keeps the formants where the singer had them."""
         import torch
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
         assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
         d_key, period, ratio = self._track_tables(keys, d_in.device)
         if stream is None:
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        if formant_semitones is not None:
+            d_formant = _device_formants(self, formant_semitones, None, d_in.device)
+            self._track_chk(self.L.vp_stft_autotune_formant(self.h, d_in.data_ptr(), d_out.data_ptr(), float(sample_rate),
+                                                            d_key.data_ptr() if d_key is not None else None, period.data_ptr(), ratio.data_ptr(),
+                                                            d_formant.data_ptr(), int(lifter), C.c_void_p(stream)))
+            return period, ratio
         self._track_chk(self.L.vp_stft_autotune(self.h, d_in.data_ptr(), d_out.data_ptr(), float(sample_rate),
                                                 d_key.data_ptr() if d_key is not None else None, period.data_ptr(), ratio.data_ptr(), C.c_void_p(stream)))
         return period, ratio
@@ -776,13 +834,18 @@ class PhaseVocoderStream:
         self._chk(self.L.vp_pv_process_block(self.h, x.ctypes.data, y.ctypes.data))
         return y
 
-    def process_device(self, d_in, d_out, n_blocks=1, stream=None, semitones_per_block=None, d_ratio=None):
+    def process_device(self, d_in, d_out, n_blocks=1, stream=None, semitones_per_block=None, d_ratio=None, formant_semitones=None, lifter=FORMANT_LIFTER,
+                       d_formant=None):
         """n_blocks blocks on the device: torch float32 [n_blocks][S][N] (or [S][N] for one block), enqueued on `stream`
         (default: the current torch stream) without synchronising.
         semitones_per_block: array-like [n_blocks] or [n_blocks][S], |value| <= 12 -- this call's frames take the interval of the block in
         which their last sample arrives (vp_pv_process_blocks_curve_device); set_semitones' interval is neither used nor changed.  The
         table is uploaded on torch's current stream into a device table kept per n_blocks.  d_ratio instead: a device float64 tensor
-        [n_blocks][S] of ratios, used as it is."""
+        [n_blocks][S] of ratios, used as it is.
+        formant_semitones (a scalar or [S], |value| <= 12; None: the calls above, unchanged) or d_formant (device float64 [S] of ratios):
+        the call keeps the spectral envelope apart from the pitch (vp_pv_process_blocks_formant_device) -- 0 leaves the formants where
+        they were; `lifter` is the cepstral lifter's length, 4 .. 64.  It is a curve call: without a table of its own it takes the
+        intervals set_semitones holds, for every block."""
         import torch
         shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
@@ -797,18 +860,31 @@ class PhaseVocoderStream:
                 self._curve_tables = {}
             st = np.broadcast_to(st.reshape(int(n_blocks), -1), (int(n_blocks), self.S))
             d_ratio = _upload_ratios(self._curve_tables, st, d_in.device)
+        formant = formant_semitones is not None or d_formant is not None
+        if formant and d_ratio is None:
+            if not hasattr(self, "_curve_tables"):
+                self._curve_tables = {}
+            held = np.array([self.semitones(s) for s in range(self.S)])
+            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(held, (int(n_blocks), self.S)), d_in.device)
         if d_ratio is not None:
             assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (int(n_blocks), self.S) and d_ratio.is_contiguous()
+            if formant:
+                d_formant = _device_formants(self, formant_semitones, d_formant, d_in.device)
+                self._chk(self.L.vp_pv_process_blocks_formant_device(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), d_formant.data_ptr(),
+                                                                     int(lifter), int(n_blocks), C.c_void_p(stream)))
+                return
             self._chk(self.L.vp_pv_process_blocks_curve_device(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), int(n_blocks),
                                                                C.c_void_p(stream)))
             return
         self._chk(self.L.vp_pv_process_blocks_device(self.h, d_in.data_ptr(), d_out.data_ptr(), int(n_blocks), C.c_void_p(stream)))
 
-    def autotune_device(self, tracker, d_in, d_out, n_blocks=1, keys=None, stream=None):
+    def autotune_device(self, tracker, d_in, d_out, n_blocks=1, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER):
         """Automatic pitch correction block by block (vp_pv_autotune_blocks_device): `tracker` (a StreamingPitchTracker of the same
         streams, block size and device) decides one ratio per block and stream from the audio received so far, this stream shifts along
         that table, both on `stream`; d_out has the bits of tracker.process_device followed by process_device(d_ratio=...).  Returns the
-        tracker's (period, ratio), device tensors [n_blocks][S].  reset() does not reach the tracker: reset both."""
+        tracker's (period, ratio), device tensors [n_blocks][S].  reset() does not reach the tracker: reset both.
+        formant_semitones (a scalar or [S]; None: the call above, unchanged): the shift runs through the formant call instead
+        (vp_pv_autotune_blocks_formant_device)."""
         import torch
         shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
@@ -816,18 +892,25 @@ class PhaseVocoderStream:
         d_key, period, ratio = tracker._tables(keys, int(n_blocks), d_in.device)
         if stream is None:
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        if formant_semitones is not None:
+            d_formant = _device_formants(self, formant_semitones, None, d_in.device)
+            self._chk(self.L.vp_pv_autotune_blocks_formant_device(self.h, tracker.h, d_in.data_ptr(), d_out.data_ptr(),
+                                                                  d_key.data_ptr() if d_key is not None else None, period.data_ptr(), ratio.data_ptr(),
+                                                                  d_formant.data_ptr(), int(lifter), int(n_blocks), C.c_void_p(stream)))
+            return period, ratio
         self._chk(self.L.vp_pv_autotune_blocks_device(self.h, tracker.h, d_in.data_ptr(), d_out.data_ptr(), d_key.data_ptr() if d_key is not None else None,
                                                       period.data_ptr(), ratio.data_ptr(), int(n_blocks), C.c_void_p(stream)))
         return period, ratio
 
-    def run(self, x, blocks_per_call=8, curve=None, autotune=None, keys=None):
+    def run(self, x, blocks_per_call=8, curve=None, autotune=None, keys=None, formant_semitones=None, lifter=FORMANT_LIFTER):
         """Whole signals float [S][T] -> output aligned with the input, [S][T]: the input padded with `latency` zeros (and up to
         whole blocks), streamed through the device entry point `blocks_per_call` blocks at a time, the first `latency` samples
         dropped.  Continues from the handle's state (reset() first for a fresh start).
         curve: semitones per block, array-like [n] or [n][S] with n >= 1; block b takes row min(b, n - 1) (the padding keeps the last
         row), through process_device(semitones_per_block=...).
         autotune: a StreamingPitchTracker instead -- every call goes through autotune_device(autotune, ..., keys=keys), and the result is
-        (output, period, ratio) with the tracker's tables as numpy arrays [n_blocks][S] (the padding blocks included)."""
+        (output, period, ratio) with the tracker's tables as numpy arrays [n_blocks][S] (the padding blocks included).
+        formant_semitones (a scalar or [S]; None: as above, unchanged): every call is a formant call (process_device / autotune_device)."""
         assert curve is None or autotune is None, "one of curve and autotune"
         import torch
         x = np.asarray(x, dtype=np.float32)
@@ -847,11 +930,13 @@ class PhaseVocoderStream:
         while b < nb:
             k = min(int(blocks_per_call), nb - b)
             if autotune is not None:
-                tables.append(self.autotune_device(autotune, d_in[b:b + k], d_out[b:b + k], n_blocks=k, keys=keys))
+                tables.append(self.autotune_device(autotune, d_in[b:b + k], d_out[b:b + k], n_blocks=k, keys=keys, formant_semitones=formant_semitones,
+                                                   lifter=lifter))
             elif curve is None:
-                self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k)
+                self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k, formant_semitones=formant_semitones, lifter=lifter)
             else:
-                self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k, semitones_per_block=curve[b:b + k])
+                self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k, semitones_per_block=curve[b:b + k], formant_semitones=formant_semitones,
+                                    lifter=lifter)
             b += k
         torch.cuda.synchronize(dev)
         y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, nb * N)
