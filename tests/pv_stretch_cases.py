@@ -11,6 +11,10 @@ nF = 19 and 5.
 Bound of the pointwise comparisons: pv_cases.bound's derivation (double transforms and stage, float32 output frames and a float32
 overlap-add of O = F / hop terms), in which nothing depends on the positions:
     |y - ref| <= 4 O 2^-24 max(1, max |ref|)       at every sample.
+
+The matrix above advances by hop / 4 .. 2 hop: neither clamp of the advance is ever taken.  EDGE_CASES (tests/test_gpu_pv_stretch_edges.py)
+are 48 cases of SIX streams whose tables reach both clamps of the advance, both clamps of the position and every alignment of a frame's
+address: edge_positions() says which row reaches what.  The bound is the same.
 """
 from collections import namedtuple
 
@@ -128,3 +132,78 @@ def big_reference(form="radians", variant=None):
         _REF[key] = {s: SR.stretch_roundtrip(x[s], pos[s], BIG_T, BIG_F, BIG_HOP, 1.0, form, "hop" if variant == "hop" else "delta")
                      for s in BIG_CHECKED}
     return _REF[key]
+
+
+# ---- the advance clamps and the table edges: 48 cases of six streams ---------------------------------------------------------------------
+EDGE_STREAMS = 6
+EDGE_ROWS = ("freeze", "reverse", "crawl", "leap", "ends", "skew")
+EDGE_SHAPES = ((19, 3), (6, 2), (2, 0))                                    # (nF, extra)
+EDGE_SEMITONES = (0.0, 7.0)
+EDGE_CASES = [StretchCase(F, hop, nF, extra, v) for F in (1024, 2048) for hop in HOPS[F] for nF, extra in EDGE_SHAPES for v in EDGE_SEMITONES]
+assert len(EDGE_CASES) == 48
+INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def _cycled(first, incs, nF):
+    return np.concatenate([[first], first + np.cumsum([incs[i % len(incs)] for i in range(nF - 1)], dtype=np.int64)]).astype(np.int64)
+
+
+def _leap(c):
+    return _cycled(0, (c.F, c.F + 1, c.F - 1, 2 * c.F + 3), c.nF)
+
+
+def edge_in_length(c):
+    """F + max(leap) + 1, raised to the next value = 3 (mod 4): the six row starts s n_in sit at residues 0, 3, 2, 1, 0, 3."""
+    n = c.F + int(_leap(c).max()) + 1
+    return n + (3 - n) % 4
+
+
+def edge_positions(c, n_in=None):
+    """int64 [EDGE_STREAMS][nF] (the wrapper makes them int32), with qm = n_in - F:
+      0 freeze   3 hop + 1 at every frame                            raw step 0 -> D = 1; the phase difference is exactly 0
+      1 reverse  (nF - 1 - f) hop + 2                                negative steps -> D = 1
+      2 crawl    0, then increments cycling 1, 2, 3                  D = 1, 2, 3 unclamped; F / D up to F
+      3 leap     0, then increments cycling F, F + 1, F - 1, 2 F + 3 D = F exactly, clamped from F + 1 and from 2 F + 3, and F - 1
+      4 ends     cycling -1, qm + 1, qm, -2^31, 2^31 - 1, 0, qm - 1, 1   both clamps of q, steps of +-qm and 0 between them
+      5 skew     1 + f (hop + 1)                                     frame addresses walk every residue mod 4"""
+    n_in = edge_in_length(c) if n_in is None else n_in
+    qm = n_in - c.F
+    f = np.arange(c.nF, dtype=np.int64)
+    ends = np.array([-1, qm + 1, qm, INT_MIN, INT_MAX, 0, qm - 1, 1], np.int64)
+    return np.stack([np.full(c.nF, 3 * c.hop + 1, np.int64), (c.nF - 1 - f) * c.hop + 2, _cycled(0, (1, 2, 3), c.nF), _leap(c), ends[f % 8],
+                     1 + f * (c.hop + 1)])
+
+
+def edge_rows(x5):
+    """Stream s of an edge case takes row s % 5 of a five-stream signal."""
+    return np.ascontiguousarray(x5[[s % 5 for s in range(EDGE_STREAMS)]])
+
+
+def edge_input(c, n_in=None):
+    return edge_rows(pv_cases.mixed_streams(edge_in_length(c) if n_in is None else n_in, seed=c.hop + 7))
+
+
+def edge_reference(c, form="radians", advance="delta", n_in=None, rows=range(EDGE_STREAMS)):
+    """{stream: [T] float64} of the streams in rows, each computed once per case, form, advance (a mutant of pv_stretch_reference.ADVANCES)
+    and input length (None: the case's; the smallest-input tests give their own, and the tables are then built against it).  Callers do
+    not write to them."""
+    x = pos = None
+    out = {}
+    for s in rows:
+        key = ("edge", c, form, advance, n_in, s)
+        if key not in _REF:
+            if x is None:
+                x, pos = edge_input(c, n_in), edge_positions(c, n_in)
+            r = SR.stretch_roundtrip(x[s], pos[s], out_length(c), c.F, c.hop, pv_cases.ratio_of(c.semitones), form, advance)
+            r.setflags(write=False)
+            _REF[key] = r
+        out[s] = _REF[key]
+    return out
+
+
+# ---- the smallest inputs: n_in = F (qm = 0: every table is freeze at 0) and n_in = F + 1 (positions 0 and 1 only), the case's own tables --
+SMALL_CASES = [(StretchCase(F, 256, 6, 2, v), F + more) for F in (1024, 2048) for more in (0, 1) for v in EDGE_SEMITONES]
+
+
+def small_id(cn):
+    return f"{case_id(cn[0])}-n_in{cn[1]}"

@@ -18,7 +18,9 @@ Bins 0 and F / 2 are real, their phases exactly 0 or half a turn on both sides, 
 is a half-integer or the bin's sign flips; with k (2 pi D / F) in the radians form, or with the nominal term reduced mod 1, the tie
 breaks differently in the two forms (measured: up to 4e-3 apart).
 
-advance="hop" is the MUTANT the teeth test needs: a stage that unwraps with hop instead of D_f.
+advance="hop" is the MUTANT the teeth test needs: a stage that unwraps with hop instead of D_f.  Four more MUTANTS, the plausible wrong
+kernels at the clamps (tests/pv_stretch_cases.py's edge tables reach them): "nohigh" D_f = max(step, 1), no upper clamp; "abs" D_f =
+clamp(|step|, 1, F); "lowhop" a step below 1 becomes hop; "qmax-1" q clamped to n_in - F - 1.  The default "delta" is the definition.
 """
 import numpy as np
 
@@ -29,11 +31,24 @@ def clamp_positions(pos, n_in, F):
     return np.clip(np.asarray(pos, np.int64), 0, n_in - F)
 
 
-def advances(q, hop, F):
-    """D_f of the clamped positions q."""
+ADVANCES = ("delta", "hop", "nohigh", "abs", "lowhop", "qmax-1")
+
+
+def advances(q, hop, F, advance="delta"):
+    """D_f of the clamped positions q; advance: "delta" (the definition) or a mutant's."""
     d = np.empty(len(q), np.int64)
     d[:1] = hop
-    d[1:] = np.clip(np.diff(q), 1, F)
+    step = np.diff(q)
+    if advance == "hop":
+        d[1:] = hop
+    elif advance == "nohigh":
+        d[1:] = np.maximum(step, 1)
+    elif advance == "abs":
+        d[1:] = np.clip(np.abs(step), 1, F)
+    elif advance == "lowhop":
+        d[1:] = np.minimum(np.where(step < 1, hop, step), F)
+    else:
+        d[1:] = np.clip(step, 1, F)
     return d
 
 
@@ -64,9 +79,9 @@ def stretch_roundtrip(x, pos, T, F=1024, hop=256, ratio=1.0, form="radians", adv
     x = np.asarray(x, np.float64)
     n_in = len(x)
     nF = (T - F) // hop + 1
-    assert n_in >= F and len(pos) == nF and form in ("radians", "turns") and advance in ("delta", "hop")
-    q = clamp_positions(pos, n_in, F)
-    D = advances(q, hop, F) if advance == "delta" else np.full(nF, hop, np.int64)
+    assert n_in >= F and len(pos) == nF and form in ("radians", "turns") and advance in ADVANCES
+    q = clamp_positions(pos, n_in - 1, F) if advance == "qmax-1" else clamp_positions(pos, n_in, F)
+    D = advances(q, hop, F, advance)
     w = window(F)
     scale = 1.0 / np.sum(w[::hop] ** 2)
     nb, O = F // 2 + 1, F // hop

@@ -1,8 +1,9 @@
 """CPU-side checks of the phase-vocoder time stretch (vp_stft_time_stretch): the reference of frames analysed at given positions is well
 conditioned on every case the GPU test compares against it (the gate), a table that is one frame off or a stage that unwraps with hop
 instead of the frame's advance cannot hide inside the bound (teeth), the table f hop is the fixed-grid definition, the clamps,
-vp_stretch_positions against its formula, the symbols and their argument checks, and the offline stretch's plumbing.  The kernels are
-checked on the GPU (tests/test_gpu_pv_stretch.py)."""
+vp_stretch_positions against its formula, the symbols and their argument checks, and the offline stretch's plumbing; and on the edge
+tables (both clamps of the advance and of the position) the same gate, with teeth for every plausible wrong clamp.  The kernels are
+checked on the GPU (tests/test_gpu_pv_stretch.py, tests/test_gpu_pv_stretch_edges.py)."""
 import ctypes as C
 import math
 import os
@@ -102,6 +103,87 @@ def test_gate_and_teeth_of_the_streams_checked_in_the_large_batch():
         bnd = 4.0 * (SC.BIG_F // SC.BIG_HOP) * 2.0 ** -24 * m
         assert np.abs(ref[s] - turns[s]).max() <= SC.GATE_TOL * m, s
         assert np.abs(ref[s] - roll[s]).max() > SC.TEETH * bnd and np.abs(ref[s] - hopw[s]).max() > SC.TEETH * bnd, s
+
+
+# ---- the edge tables: both clamps of the advance, both clamps of the position ------------------------------------------------------------
+def test_the_edge_tables_reach_what_they_name():
+    assert len(set(SC.EDGE_CASES)) == 48 and {(c.F, c.hop) for c in SC.EDGE_CASES} == {(F, h) for F in (1024, 2048) for h in SC.HOPS[F]}
+    assert {(c.nF, c.extra) for c in SC.EDGE_CASES} == {(19, 3), (6, 2), (2, 0)} and {c.semitones for c in SC.EDGE_CASES} == {0.0, 7.0}
+    for c in SC.EDGE_CASES:
+        F, hop, nF = c.F, c.hop, c.nF
+        n_in, pos, x = SC.edge_in_length(c), SC.edge_positions(c), SC.edge_input(c)
+        qm = n_in - F
+        assert pos.shape == (6, nF) and x.shape == (6, n_in) and x.dtype == np.float32 and np.array_equal(x[5], x[0])
+        assert n_in % 4 == 3 and n_in - 4 < F + pos[3].max() + 1 <= n_in and {s * n_in % 4 for s in range(6)} == {0, 1, 2, 3}
+        assert (SC.out_length(c) - F) // hop + 1 == nF and np.all(pos >= SC.INT_MIN) and np.all(pos <= SC.INT_MAX)
+        q = [SR.clamp_positions(p, n_in, F) for p in pos]
+        D = [SR.advances(v, hop, F) for v in q]
+        raw = [np.diff(p) for p in pos]
+        assert np.all(raw[0] == 0) and np.all(D[0][1:] == 1)                               # freeze
+        assert np.all(raw[1] == -hop) and np.all(D[1][1:] == 1) and np.array_equal(q[1], pos[1])            # reverse
+        assert np.array_equal(D[2][1:], ([1, 2, 3] * 6)[:nF - 1]) and np.array_equal(q[2], pos[2])          # crawl
+        assert np.array_equal(raw[3], ([F, F + 1, F - 1, 2 * F + 3] * 5)[:nF - 1]) and np.array_equal(q[3], pos[3])       # leap
+        assert np.array_equal(D[3][1:], ([F, F, F - 1, F] * 5)[:nF - 1])
+        assert np.array_equal(q[4], ([0, qm, qm, 0, qm, 0, qm - 1, 1] * 3)[:nF]) and qm > F                  # ends
+        assert np.array_equal(D[4][1:], ([F, 1, 1, F, 1, F, 1, 1, F, 1, 1, F, 1, F, 1, 1, F, 1])[:nF - 1])
+        assert np.array_equal(q[5], pos[5]) and np.all(D[5][1:] == hop + 1)                 # skew
+        assert nF < 6 or {int(v) % 4 for v in q[5]} == {0, 1, 2, 3}
+    c = SC.StretchCase(1024, 256, 19, 3, 0.0)                                             # the mutants are what they say
+    q = SR.clamp_positions(SC.edge_positions(c)[4], SC.edge_in_length(c), 1024)
+    qm = SC.edge_in_length(c) - 1024
+    assert list(SR.advances(q, 256, 1024, "nohigh")[1:4]) == [qm, 1, 1] and list(SR.advances(q, 256, 1024, "abs")[1:5]) == [1024, 1, 1024, 1024]
+    assert list(SR.advances(q, 256, 1024, "lowhop")[1:4]) == [1024, 256, 256] and np.all(SR.advances(q, 256, 1024, "hop") == 256)
+
+
+def _mutants_of(row, c):
+    """The mutants that must show on a row of an edge case."""
+    m = [] if (row == "freeze" and c.semitones == 0.0) else ["hop"]
+    if (row == "leap" and c.nF >= 6) or row == "ends":
+        m.append("nohigh")
+    if row == "reverse" or (row == "ends" and c.nF >= 6):
+        m += ["abs", "lowhop"]
+    if row == "freeze" and c.semitones == 7.0:
+        m.append("lowhop")
+    if row == "ends":
+        m.append("qmax-1")
+    return m
+
+
+@pytest.mark.parametrize("c", SC.EDGE_CASES, ids=SC.case_id)
+def test_edge_gate_and_teeth(c):
+    """On every stream of an edge case.  Gate: the two statements of the reference agree.  Teeth: each mutant of the advance or of the
+    position's clamp moves the reference by more than TEETH x the bound of the GPU comparison on the rows that reach its clamp.  freeze at 0
+    semitones: a repeated frame's deviation is -(k D) / F; at ratio 1 any D that divides hop gives whole turns per hop, so the pure stretch
+    cannot see this clamp -- the definition and the "hop" mutant agree within the gate, which is asserted instead."""
+    ref, turns = SC.edge_reference(c), SC.edge_reference(c, "turns")
+    for s, row in enumerate(SC.EDGE_ROWS):
+        m = max(1.0, np.abs(ref[s]).max())
+        gate, bnd = np.abs(ref[s] - turns[s]).max(), SC.bound(c, ref[s])
+        msg = f"STRETCHEDGE {SC.case_id(c)} {row}: gate {gate:.3g} (tol {SC.GATE_TOL * m:.3g})"
+        assert np.all(np.isfinite(ref[s])) and np.abs(ref[s]).max() > 0.01 and gate <= SC.GATE_TOL * m, (row, gate)
+        for mutant in _mutants_of(row, c):
+            t = np.abs(ref[s] - SC.edge_reference(c, advance=mutant, rows=[s])[s]).max() / bnd
+            msg += f"  {mutant}/bound {t:.3g}"
+            assert t > SC.TEETH, (row, mutant, t)
+        if row == "freeze" and c.semitones == 0.0:
+            t = np.abs(ref[s] - SC.edge_reference(c, advance="hop", rows=[s])[s]).max()
+            msg += f"  hop (unseen at ratio 1) {t:.3g}"
+            assert t <= SC.GATE_TOL * m, (row, "hop", t)
+        print(msg)
+
+
+@pytest.mark.parametrize("cn", SC.SMALL_CASES, ids=SC.small_id)
+def test_gate_of_the_smallest_inputs(cn):
+    """n_in = F and F + 1: the edge tables collapse onto positions 0 and 0 / 1; the two statements of the reference agree there too."""
+    c, n_in = cn
+    q = SR.clamp_positions(SC.edge_positions(c, n_in), n_in, c.F)
+    assert q.min() == 0 and q.max() == n_in - c.F and (n_in > c.F or np.all(q == 0))
+    ref, turns = SC.edge_reference(c, n_in=n_in), SC.edge_reference(c, "turns", n_in=n_in)
+    for s, row in enumerate(SC.EDGE_ROWS):
+        m = max(1.0, np.abs(ref[s]).max())
+        gate = np.abs(ref[s] - turns[s]).max()
+        print(f"STRETCHEDGE {SC.small_id(cn)} {row}: gate {gate:.3g} (tol {SC.GATE_TOL * m:.3g})")
+        assert np.all(np.isfinite(ref[s])) and np.abs(ref[s]).max() > 0.01 and gate <= SC.GATE_TOL * m, (row, gate)
 
 
 @pytest.mark.parametrize("F,hop", [(1024, 256), (1024, 64), (2048, 512)])
