@@ -18,6 +18,9 @@ phi = 1 leaves the envelope where it was (formant preservation), phi = 2^(st / 1
 pitch: delta is exactly 0 and the output is frame_loop's, bit for bit.  Bins 0 and F / 2 take the gain like every other bin and then keep
 their real parts.  Two forms, as every phase-vocoder case module has them: phases in radians (pv_stream_reference.PvStreamRef._frame's
 arithmetic) and in turns (pv_cases._turns_frame's).
+
+WRONG names what a plausible wrong kernel would compute in the envelope stage, one deviation each; every function below takes one of the
+names as an optional `wrong` (None: the definition above).  tests/test_pv_formant_edges_cpu.py asserts how far each is from the definition.
 """
 import numpy as np
 
@@ -28,6 +31,16 @@ import stft_reference as R
 LN16 = float(np.log(16.0))
 FLOOR = 1e-12
 LIFTER_DEFAULT = 32
+WRONG = ("clamp-ln8",        # the clamp at +-ln 8
+         "clamp-db",         # ... at +-ln 10^(24 / 20) = 2.763 (ln 16 = 2.7726 is 24.08 dB)
+         "clamp-nolow",      # no lower clamp
+         "clamp-nohigh",     # no upper clamp
+         "top511",           # the interpolation's source position clipped at nb - 2 instead of nb - 1
+         "interp-t0",        # the interpolation weight dropped: le[i0]
+         "interp-nearest",   # the nearer of the two envelope values
+         "floor-1e-11", "floor-1e-13",
+         "floor-none",       # log(m^2) (1e-300 keeps the logarithm of an exact zero finite)
+         "floor-on-m")       # log(m + 1e-6), the floor on the magnitude
 
 
 def clamp_ratio(r):
@@ -45,9 +58,15 @@ def lifter_window(F, nc, half=True):
     return lw
 
 
-def envelope(m, F, nc, half=True):
+def log_magnitude(m, wrong=None):
+    if wrong == "floor-on-m":
+        return np.log(m + 1e-6)
+    return 0.5 * np.log(m * m + {"floor-1e-11": 1e-11, "floor-1e-13": 1e-13, "floor-none": 1e-300}.get(wrong, FLOOR))
+
+
+def envelope(m, F, nc, half=True, wrong=None):
     """The smoothed log envelope of the magnitudes m [nb], by two transforms."""
-    L = 0.5 * np.log(m * m + FLOOR)
+    L = log_magnitude(m, wrong)
     c = np.fft.irfft(L, F) * lifter_window(F, nc, half)
     return np.fft.rfft(c).real
 
@@ -63,37 +82,65 @@ def envelope_direct(m, F, nc):
     return le
 
 
-def envelope_at(le, rho):
+def envelope_at(le, rho, wrong=None):
     nb = len(le)
-    src = np.clip(np.arange(nb) * (1.0 / rho), 0.0, nb - 1.0)
+    src = np.clip(np.arange(nb) * (1.0 / rho), 0.0, nb - (2.0 if wrong == "top511" else 1.0))
     i0 = np.minimum(np.floor(src).astype(np.int64), nb - 2)
     t = src - i0
+    if wrong == "interp-t0":
+        t = 0.0 * t
+    elif wrong == "interp-nearest":
+        t = np.floor(t + 0.5)
     return le[i0] + t * (le[i0 + 1] - le[i0])
 
 
-def log_gain(m, F, ratio, phi, nc, half=True):
+def raw_log_gain(m, F, ratio, phi, nc, half=True, wrong=None):
+    """at(phi) - at(r) before the clamp [nb]."""
+    le = envelope(m, F, nc, half, wrong)
+    return envelope_at(le, phi, wrong) - envelope_at(le, ratio, wrong)
+
+
+def clamp_limits(wrong=None):
+    c = {"clamp-ln8": float(np.log(8.0)), "clamp-db": float(np.log(10.0 ** (24.0 / 20.0)))}.get(wrong, LN16)
+    return (-np.inf if wrong == "clamp-nolow" else -c), (np.inf if wrong == "clamp-nohigh" else c)
+
+
+def log_gain(m, F, ratio, phi, nc, half=True, wrong=None):
     """(delta [nb], number of bins at the clamp)."""
-    le = envelope(m, F, nc, half)
-    raw = envelope_at(le, phi) - envelope_at(le, ratio)
-    return np.clip(raw, -LN16, LN16), int(np.count_nonzero(np.abs(raw) >= LN16))
+    raw = raw_log_gain(m, F, ratio, phi, nc, half, wrong)
+    return np.clip(raw, *clamp_limits(wrong)), int(np.count_nonzero(np.abs(raw) >= LN16))
 
 
 class FormantRef(P.PvStreamRef):
     """PvStreamRef with the formant correction in _frame (phases in radians).  phi, nc: the stream's; the pitch ratio is the frame's.
-    phi = "pitch": the formant ratio of every frame is that frame's pitch ratio (the plain pitch shift)."""
+    phi = "pitch": the formant ratio of every frame is that frame's pitch ratio (the plain pitch shift).  set_formant switches phi and
+    nc between calls (a handle's formant, curve and plain calls)."""
 
-    def __init__(self, N, hop=256, F=1024, ratio=1.0, phi=1.0, nc=LIFTER_DEFAULT, half=True):
+    def __init__(self, N, hop=256, F=1024, ratio=1.0, phi=1.0, nc=LIFTER_DEFAULT, half=True, wrong=None):
         super().__init__(N, hop, F, ratio)
-        self.phi, self.nc, self.half = (None if isinstance(phi, str) else float(clamp_ratio(phi))), int(nc), half
-        assert self.phi is not None or phi == "pitch", phi
+        self.half, self.wrong = half, wrong
+        self.set_formant(phi, nc)
         self.clamped = 0                                         # (frame, bin) pairs at the +-ln 16 clamp
+        self.clamped_hi = self.clamped_lo = 0                    # ... on either side
         self.pairs = 0
 
+    def set_formant(self, phi, nc=None):
+        self.phi = None if isinstance(phi, str) else float(clamp_ratio(phi))
+        assert self.phi is not None or phi == "pitch", phi
+        if nc is not None:
+            self.nc = int(nc)
+
     def _gain(self, m, ratio):
-        d, n = log_gain(m, self.F, ratio, ratio if self.phi is None else self.phi, self.nc, self.half)
-        self.clamped += n
+        raw = raw_log_gain(m, self.F, ratio, ratio if self.phi is None else self.phi, self.nc, self.half, self.wrong)
+        self.clamped += int(np.count_nonzero(np.abs(raw) >= LN16))
+        self.clamped_hi += int(np.count_nonzero(raw >= LN16))
+        self.clamped_lo += int(np.count_nonzero(raw <= -LN16))
         self.pairs += len(m)
-        return np.exp(d)
+        return np.exp(np.clip(raw, *clamp_limits(self.wrong)))
+
+    def add_stats(self, stats):
+        for k in ("clamped", "clamped_hi", "clamped_lo", "pairs"):
+            stats[k] = stats.get(k, 0) + getattr(self, k)
 
     def _frame(self, seg, f, ratio):
         ratio = float(clamp_ratio(ratio))
@@ -141,11 +188,11 @@ class FormantTurns(FormantRef):
         return np.fft.irfft(Y, self.F) * self.w
 
 
-def frame_loop(x, F, hop, ratio, phi=1.0, nc=LIFTER_DEFAULT, form="radians", half=True, stats=None):
+def frame_loop(x, F, hop, ratio, phi=1.0, nc=LIFTER_DEFAULT, form="radians", half=True, stats=None, wrong=None):
     """One stream, one-shot: x float [T], ratio [nFrames] -> float64 [T] (pv_curve_cases.frame_loop with the correction).
     stats: a dict that receives the clamp counts."""
     cls = FormantRef if form == "radians" else FormantTurns
-    r = cls(F, hop, F, phi=phi, nc=nc, half=half)               # (the block size plays no part in _frame)
+    r = cls(F, hop, F, phi=phi, nc=nc, half=half, wrong=wrong)  # (the block size plays no part in _frame)
     x = np.asarray(x, np.float64)
     nF = (len(x) - F) // hop + 1
     assert len(ratio) == nF
@@ -153,8 +200,7 @@ def frame_loop(x, F, hop, ratio, phi=1.0, nc=LIFTER_DEFAULT, form="radians", hal
     for f in range(nF):
         y[f * hop:f * hop + F] += r._frame(x[f * hop:f * hop + F], f, float(ratio[f]))
     if stats is not None:
-        stats["clamped"] = stats.get("clamped", 0) + r.clamped
-        stats["pairs"] = stats.get("pairs", 0) + r.pairs
+        r.add_stats(stats)
     return y * r.scale
 
 
@@ -165,6 +211,5 @@ def by_block(x, N, hop, ratio, phi=1.0, nc=LIFTER_DEFAULT, form="radians", stats
     r = cls(N, hop, phi=phi, nc=nc)
     y = np.concatenate([r.process(x[b * N:(b + 1) * N], float(ratio[b])) for b in range(len(ratio))])
     if stats is not None:
-        stats["clamped"] = stats.get("clamped", 0) + r.clamped
-        stats["pairs"] = stats.get("pairs", 0) + r.pairs
+        r.add_stats(stats)
     return y
