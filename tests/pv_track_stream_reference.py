@@ -18,14 +18,24 @@ ends at n_b = (b + 1) N samples.
 How blocks are grouped into process() calls does not enter: the tables are a function of the blocks received.  Float32-denormal input
 samples are outside the domain, as for the batch tracker.
 
-MUTANTS are seeded faults of this definition (tests/test_pv_track_stream_reference_cpu.py requires each to differ from it on a named case)."""
+MUTANTS are seeded faults of this definition (tests/test_pv_track_stream_reference_cpu.py requires each to differ from it on a named case).
+GATHER_MUTANTS are faults of how the device collects a window from the call's slab and the stream's ring, stated on this definition's sample
+indices (tests/test_pv_track_edges_cpu.py requires each to differ on a named case of tests/pv_track_edge_cases.py).  With c0 the stream's
+sample count when the call began, window sample p is the stream's sample i = n_b - W + p: from the ring when i < c0, else sample j = i - c0 of
+the call's slab.
+  ring_phase   a sample from the ring is read one slot late: i + 1, and behind the ring's newest sample its oldest, c0 - W (0.0 where the
+               ring has not been written yet);
+  carry_gt     the lanes step 64 samples at a time with the offset in its block carried as (q64, r64) = (64 / N, 64 % N); the carry taken
+               at `off > N` instead of `off >= N` leaves a sample that starts a block (j % N == 0, p >= 64, r64 > 0) in the block before
+               it at its last offset: sample i - 1, and for j == 0 the ring's slot of i, which holds i - W."""
 import numpy as np
 
 import pv_track_reference as R
 
 INT_MAX = 2 ** 31 - 1
 HOLD_MAX = 1 << 20
-MUTANTS = ("zero_prefill", "window_at_block_start", "age_ge_hold", "glide_formula_at_one", "key_ignored")
+GATHER_MUTANTS = ("ring_phase", "carry_gt")
+MUTANTS = ("zero_prefill", "window_at_block_start", "age_ge_hold", "glide_formula_at_one", "key_ignored") + GATHER_MUTANTS
 
 
 def window_len(fs, F):
@@ -73,10 +83,13 @@ class StreamTracker:
     def reset(self, stream=-1):
         if stream < 0:
             self.hist = [np.zeros(0, np.float32) for _ in range(self.S)]      # the stream's last samples (W + N of them at most)
+            self.all = [np.zeros(0, np.float32) for _ in range(self.S)]       # ... and all of them, for the gather faults
+            self.call0 = [0] * self.S                                         # the stream's count when the current call began
             self.count = [0] * self.S
             self.state = [(1.0, 0, 1.0)] * self.S
         else:
             self.hist[stream], self.count[stream], self.state[stream] = np.zeros(0, np.float32), 0, (1.0, 0, 1.0)
+            self.all[stream], self.call0[stream] = np.zeros(0, np.float32), 0
 
     def _raw(self, s, key):
         """(period, raw ratio) of the block that just ended on stream s."""
@@ -89,11 +102,25 @@ class StreamTracker:
             if self.mutant != "zero_prefill":
                 return 0, 1.0
             w = np.concatenate([np.zeros(W - n, np.float32), h])
+        elif self.mutant in GATHER_MUTANTS:
+            w = self._gather_fault(s)
         else:
             w = h[len(h) - W:]
         p, r = R.track(w[None, :], self.fs, self.F, self.F, [key], mutant="key_ignored" if self.mutant == "key_ignored" else None)
         assert p.shape == (1, 1)
         return int(p[0, 0]), float(r[0, 0])
+
+    def _gather_fault(self, s):
+        W, N, n, c0, x = self.W, self.N, self.count[s], self.call0[s], self.all[s]
+        at = lambda i: x[i] if i >= 0 else np.float32(0.0)                         # noqa: E731
+        w = x[n - W:n].copy()
+        for p in range(W):
+            i = n - W + p
+            if self.mutant == "ring_phase" and i < c0:
+                w[p] = at(i + 1 if i + 1 < c0 else c0 - W)
+            if self.mutant == "carry_gt" and p >= 64 and 64 % N and i >= c0 and (i - c0) % N == 0:
+                w[p] = at(i - 1 if i > c0 else i - W)
+        return w
 
     def process(self, blocks, keys=None):
         """blocks float32 [n][S][N] -> (period int32 [n][S], followed ratio float64 [n][S]); self.raw is the raw ratio table of the call."""
@@ -105,10 +132,13 @@ class StreamTracker:
             keys = [int(keys)] * self.S
         assert len(keys) == self.S
         n = blocks.shape[0]
+        self.call0 = list(self.count)
         period, ratio, self.raw = np.zeros((n, self.S), np.int32), np.ones((n, self.S), np.float64), np.ones((n, self.S), np.float64)
         for b in range(n):
             for s in range(self.S):
                 self.hist[s] = np.concatenate([self.hist[s], blocks[b, s]])[-(self.W + self.N):]
+                if self.mutant in GATHER_MUTANTS:
+                    self.all[s] = np.concatenate([self.all[s], blocks[b, s]])
                 self.count[s] += self.N
                 period[b, s], self.raw[b, s] = self._raw(s, keys[s])
                 self.state[s], ratio[b, s] = follow_step(self.state[s], period[b, s], self.raw[b, s], self.hold, self.glide, self.mutant)
