@@ -351,6 +351,26 @@ int vp_stft_pitch_shift(vp_stft *p, const float *d_in, float *d_out, double semi
  * Used as r = fmin(fmax(r, 0.5), 2.0), so a NaN becomes 0.5.
  * VP_ERR_INVALID_ARG for null pointers, VP_ERR_HIP when the device refused the kernels' LDS size at create. */
 int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream);
+/* vp_stft_pitch_shift_curve with PEAK LOCKING (kernel vp_k_stft_pv_lock; Laroche & Dolson 1999, identity locking with integer offsets).
+ * The plain stage moves every bin on its own and runs one phase accumulator per synthesis bin, which tears a sinusoid's main lobe apart
+ * and loses the phase relation of its bins ("phasiness": a +7 semitone tone comes out 9 dB low).  Here every frame's spectral peaks are
+ * found, each bin belongs to its nearest peak, and a peak's whole region is translated by one integer offset and rotated by one
+ * accumulated angle.  The definition is tests/pv_lock_reference.py.  Per stream pprev[k] = theta[k] = 0; per frame, with r the frame's
+ * ratio clamped as in vp_stft_pitch_shift_curve, O = frame_len / hop, phases in turns:
+ *   m, p magnitude and phase of the analysis bins k <= 512;  d = p - pprev - k / O, d -= rint(d);  nu = k + d O;  pprev = p;
+ *   k is a peak iff m[k] > 0, m[k] > m[k-1], m[k-2] and m[k] >= m[k+1], m[k+2] (neighbours outside 0 .. 512 do not count);
+ *   own[k] is the nearest peak, the lower one on equal distance;
+ *   per peak P: t = theta[P] + (nu[P] (r - 1)) / O, th[P] = t - rint(t);  P' = floor(P r + 0.5), peaks with P' > 512 are not synthesised;
+ *   synthesis bin kk belongs to the nearest P' (the lower on equal distance), its source is k = kk - (P' - P):
+ *     Y[kk] = X[k] exp(2 pi i th[P]) if 0 <= k <= 512 and own[k] == P, else 0;  bins 0 and 512 keep their real parts;
+ *   theta[k] = th[own[k]] for every k.  A frame without peaks (all zeros) gives Y = 0 and leaves theta.
+ * A region is translated whole: at r > 1 the gaps stay empty, at r < 1 neighbouring regions are cut where they meet, not added.  At
+ * r = 1 the stage is the identity.  1024-point frames, every hop, always double, one workgroup per stream, no allocation.
+ * Out of scope: 2048-point frames; formant correction on top of locking; locking in the time stretch; fractional-bin interpolation of
+ * the offset (the integer offset is why a tone at -12 semitones loses level); adding overlapping regions; several voices per call.
+ * VP_ERR_INVALID_ARG (null handle, input, output or ratio table) and VP_ERR_GEOMETRY (a 2048-point handle) are reported before the
+ * device is touched and vp_stft_last_error says which; VP_ERR_HIP as vp_stft_pitch_shift. */
+int vp_stft_pitch_shift_locked(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream);
 /* vp_stft_pitch_shift_curve with the spectral envelope kept apart from the pitch (kernel vp_k_stft_pv_formant): the formants stay where
  * they were, or move by a ratio of their own, while the pitch follows d_ratio.  The definition is tests/pv_formant_reference.py.  Per
  * frame, with m the analysis magnitudes, r the frame's pitch ratio and phi the stream's formant ratio (both clamped to [0.5, 2] as in
@@ -470,6 +490,14 @@ int vp_pv_process_blocks_device(vp_pv *p, const float *d_in, float *d_out, int n
  * used nor changed by this call: it is stored as usual and holds again from the next plain call on.  The table is read when the kernel
  * runs: keep it unchanged until then.  No allocation. */
 int vp_pv_process_blocks_curve_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream);
+/* vp_pv_process_blocks_curve_device with vp_stft_pitch_shift_locked's stage (kernel vp_k_pv_stream_lock): d_ratio device double
+ * [n_blocks][S], a frame takes the ratio of the block in which its last sample arrives.  The stream's record is unchanged: theta lives in
+ * the array that holds the plain calls' synthesis accumulator and pprev in the array of the previous frame's phases.  Latency, call
+ * bookkeeping, pending interval changes and resets are the curve call's; a reset stream starts from zeros.  The output, less the latency,
+ * is bit-identical to vp_stft_pitch_shift_locked on the concatenated input with the table expanded per frame.  Locked, curve, plain and
+ * formant calls may follow each other on one handle: they share the two arrays, so after a change of kind the output is defined and
+ * finite but carries a phase jump -- a caller who minds that resets the stream (vp_pv_reset) at the change.  No allocation. */
+int vp_pv_process_blocks_locked_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream);
 /* vp_pv_process_blocks_curve_device with vp_stft_pitch_shift_formant's correction (kernel vp_k_pv_stream_formant): d_formant device
  * double [S] or NULL = 1.0, lifter as there (VP_ERR_INVALID_ARG outside 4 .. 64, before the device is touched).  The stream's state
  * record, latency and call bookkeeping are the curve call's, so formant, curve and plain calls mix freely on one handle; pending resets

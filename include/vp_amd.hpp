@@ -413,6 +413,13 @@ public:
     {
         check(vp_pv_process_blocks_curve_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksCurve");
     }
+    // processBlocksCurve with peak locking (vp_pv_process_blocks_locked_device): a spectral peak's whole region of bins moves by one
+    // integer offset and turns by one accumulated angle.  The kinds of call share the stream's state: after a change of kind the output
+    // is finite but carries a phase jump -- reset() the stream at the change to avoid it
+    void processBlocksLocked(const float *dIn, float *dOut, const double *dRatio, int nBlocks, void *hipStream = nullptr)
+    {
+        check(vp_pv_process_blocks_locked_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksLocked");
+    }
     // automatic correction: the tracker's call, then processBlocksCurve along its table (dRatio: result and scratch, required; dPeriod
     // may be null), on one stream.  The tracker must have this shifter's streams, block size and device.  reset() does not reach it.
     void autotuneBlocks(StreamingPitchTracker &tracker, const float *dIn, float *dOut, const int *dKey, int *dPeriod, double *dRatio, int nBlocks,

@@ -6,6 +6,7 @@
     [VP_AMD_LIB=...] python tools/pv_bench.py --stretch [--reps 7] [--out profiles/pv_stretch_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --track [--reps 7] [--out profiles/pv_track_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --track-stream [--reps 7] [--out profiles/pv_track_stream_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --locked [--reps 7] [--out profiles/pv_lock_bench.txt]
 
 --curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
 "steps" curve, fixed, ...): 256 streams x 65 536 samples at 1024 points / hop 256 and 2048 points / hop 512 (vp_stft_pitch_shift against
@@ -29,6 +30,11 @@ batch tracker, alternating in one process: 256 streams at 44.1 kHz, 1024 points,
 tracker takes 16 blocks of 1024 per call and, as its own line, one block per call.  Then the streaming autotune
 (vp_pv_autotune_blocks_device) against the tracker call and the curve call that make it up.  Every repetition is a window of about a tenth of a second of calls.  Printed: decisions/s per leg and autotune's
 time per call against the sum of its parts'.
+
+--locked: the peak-locked builds (vp_stft_pitch_shift_locked, vp_pv_process_blocks_locked_device) beside the curve kernels they were
+copied from, alternating in one process on the SAME "steps" table: one-shot, 256 streams x 65 536 samples, 1024 points / hop 256, on noise
+and on voiced signals (the stage's mask searches depend on how far apart the peaks are); then streaming, 16 blocks of 1024 per call.  The
+locked kernel's mean over the curve kernel's from the same run is the comparison; the kernels' resource listings follow.
 """
 import argparse
 import os
@@ -120,6 +126,34 @@ def curve_legs(reps, emit):
             "curve, steps": lambda: ps.process_device(xb, yb, n_blocks=K, d_ratio=steps)}
     report(f"streaming, {S} streams, {K} blocks of {N} per call, hop = {hop}", alternate(legs, reps, 300), S * K * N // hop, "plain +7 (parent kernel)", emit)
     ps.close()
+
+
+def locked_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import PhaseVocoderStream, StftRoundTrip, semitones_to_ratios
+    S, T, F, hop, fs = 256, 65536, 1024, 256, 44100.0
+    rng = np.random.default_rng(9)
+    st = StftRoundTrip(S, T, F, hop)
+    nF = st.n_frames
+    steps = torch.from_numpy(semitones_to_ratios(rng.uniform(-12.0, 12.0, (S, nF)))).cuda()
+    base = "curve, steps (parent kernel)"
+    for what, x in (("noise", torch.randn(S, T, device="cuda", dtype=torch.float32) * 0.1), ("voiced signals", torch.from_numpy(voiced_rows(S, T, fs)).cuda())):
+        y = torch.empty_like(x)
+        legs = {base: lambda x=x, y=y: st.pitch_shift_curve(x, y, d_ratio=steps),
+                "locked, steps": lambda x=x, y=y: st.pitch_shift_locked(x, y, d_ratio=steps)}
+        report(f"one-shot, {S} streams x {T} samples of {what}, F = {F}, hop = {hop}", alternate(legs, reps, 100), S * nF, base, emit)
+    st.close()
+    N, K = 1024, 16
+    a, b = PhaseVocoderStream(S, N, hop=hop), PhaseVocoderStream(S, N, hop=hop)
+    xb = torch.randn(K, S, N, device="cuda", dtype=torch.float32) * 0.1
+    yb = torch.empty_like(xb)
+    steps = torch.from_numpy(semitones_to_ratios(rng.uniform(-12.0, 12.0, (K, S)))).cuda()
+    legs = {base: lambda: a.process_device(xb, yb, n_blocks=K, d_ratio=steps),
+            "locked, steps": lambda: b.process_device(xb, yb, n_blocks=K, d_ratio=steps, locked=True)}
+    report(f"streaming, {S} streams, {K} blocks of {N} per call of noise, hop = {hop}", alternate(legs, reps, 300), S * K * N // hop, base, emit)
+    a.close()
+    b.close()
 
 
 def stretch_legs(reps, emit):
@@ -268,10 +302,11 @@ def main():
     ap.add_argument("--stretch", action="store_true", help="the time-stretch legs instead of the fixed intervals")
     ap.add_argument("--track", action="store_true", help="the pitch-tracker legs instead of the fixed intervals")
     ap.add_argument("--track-stream", action="store_true", help="the streaming-tracker legs instead of the fixed intervals")
+    ap.add_argument("--locked", action="store_true", help="the peak-locked legs instead of the fixed intervals")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="--curve / --stretch / --track: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve and not a.stretch and not a.track and not a.track_stream:
+    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked:
         return fixed_intervals()
     lines = []
 
@@ -289,6 +324,9 @@ def main():
     if a.track_stream:
         track_stream_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_yin_track", "vp_k_yin_track_stream", "vp_k_track_follow", "vp_k_track_reset", "vp_k_pv_stream_curve"))
+    if a.locked:
+        locked_legs(max(5, a.reps), emit)
+        resource_listing(emit, ("vp_k_stft_pv_curve", "vp_k_stft_pv_lock", "vp_k_pv_stream_curve", "vp_k_pv_stream_lock"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -1881,7 +1881,7 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     // THAT call; the plain and single-precision round trips (<= 64 KB) are served regardless.  The sticky HIP error is cleared so
     // that a later hipGetLastError() behind a launch does not report this one.
     p->pvOk = vp_stft_prepare_device() == hipSuccess && vp_stft_curve_prepare_device() == hipSuccess && vp_stft_stretch_prepare_device() == hipSuccess
-        && vp_stft_formant_prepare_device() == hipSuccess;
+        && vp_stft_formant_prepare_device() == hipSuccess && vp_stft_lock_prepare_device() == hipSuccess;
     if (!p->pvOk) (void)hipGetLastError();
     p->device = device; p->F = frame_len; p->hop = hop; p->S = n_streams; p->T = n_samples;
     p->nFrames = (n_samples - frame_len) / hop + 1;
@@ -1960,9 +1960,9 @@ extern "C" int vp_stft_get_precision(const vp_stft *p) { return p ? (p->f32 ? VP
 
 // (d_ratio: the phase-vocoder stage reads its ratio per frame from this table, `ratio` is unused then; d_pos: it reads frame f at input
 // sample d_pos[s][f] of rows of n_in samples -- the time stretch; lifter > 0: the ratio-curve build with the formant correction, d_formant
-// [S] or null)
+// [S] or null; locked: the ratio-curve build with peak locking)
 static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag, hipStream_t st, bool pv, double ratio, const double *d_ratio = nullptr,
-                      const int *d_pos = nullptr, int n_in = 0, const double *d_formant = nullptr, int lifter = 0)
+                      const int *d_pos = nullptr, int n_in = 0, const double *d_formant = nullptr, int lifter = 0, bool locked = false)
 {
     VpStftArgs a;
     memset(&a, 0, sizeof a);
@@ -1988,6 +1988,7 @@ static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
     a.roundsPerRun = (a.nRounds + runs - 1) / runs;
     const int nRuns = (a.nRounds + a.roundsPerRun - 1) / a.roundsPerRun;
     if (d_ratio && lifter > 0) return vp_stft_launch_formant(a, d_ratio, d_formant, lifter, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
+    if (d_ratio && locked) return vp_stft_launch_lock(a, d_ratio, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     if (d_ratio) return vp_stft_launch_curve(a, d_ratio, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     if (d_pos) return vp_stft_launch_stretch(a, d_pos, n_in, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     return vp_stft_launch(a, p->S, nRuns, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
@@ -2017,6 +2018,18 @@ extern "C" int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d
     if (!p->pvOk) return VP_ERR_HIP;                           // (as vp_stft_pitch_shift)
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio);
+}
+
+// the pitch shift along a ratio curve with PEAK LOCKING (vp_k_stft_pv_lock; 1024-point frames): the arguments of vp_stft_pitch_shift_curve,
+// checked before the device is touched
+extern "C" int vp_stft_pitch_shift_locked(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream)
+{
+    if (!p) return VP_ERR_INVALID_ARG;
+    if (!d_in || !d_out || !d_ratio) { p->lastError = "locked: null input, output or ratio table"; return VP_ERR_INVALID_ARG; }
+    if (p->F != 1024) { p->lastError = "locked: 2048-point frames are not built (the peak-locked stage exists for 1024-point frames only)"; return VP_ERR_GEOMETRY; }
+    if (!p->pvOk) { p->lastError = "locked: the device refused the phase-vocoder kernels' LDS size at create"; return VP_ERR_HIP; }   // (as vp_stft_pitch_shift)
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio, nullptr, 0, nullptr, 0, true);
 }
 
 // every argument of a formant call that the curve call does not have, checked before the device is touched
@@ -2177,7 +2190,8 @@ extern "C" int vp_pv_create(int device, int n_streams, int block_size, int frame
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VP_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    if (vp_pv_prepare_device() != hipSuccess || vp_pv_curve_prepare_device() != hipSuccess || vp_pv_formant_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
+    if (vp_pv_prepare_device() != hipSuccess || vp_pv_curve_prepare_device() != hipSuccess || vp_pv_formant_prepare_device() != hipSuccess
+        || vp_pv_lock_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
     vp_pv *p = new vp_pv();
     p->device = device; p->S = n_streams; p->N = block_size; p->F = frame_len; p->hop = hop;
     int g = block_size, b = hop;
@@ -2255,9 +2269,9 @@ extern "C" int vp_pv_reset(vp_pv *p, int stream)
 // the pending changes travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update launches in front of it): ordered on
 // the caller's stream, no host memory the device reads later, no allocation
 // (d_ratio: one ratio per block and stream for this call, [n_blocks][S]; the pending changes travel and are stored as in any call;
-// lifter > 0: the curve call with the formant correction, d_formant [S] or null)
+// lifter > 0: the curve call with the formant correction, d_formant [S] or null; locked: the curve call with peak locking)
 static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipStream_t st, const double *d_ratio = nullptr, const double *d_formant = nullptr,
-                  int lifter = 0)
+                  int lifter = 0, bool locked = false)
 {
     p->upd.clear();
     if (p->allRatio > 0.0 || p->allReset) p->upd.push_back(VpPvUpdate{-1, p->allReset ? 1 : 0, p->allRatio});
@@ -2276,7 +2290,8 @@ static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipSt
     }
     a.in = d_in; a.out = d_out; a.nBlocks = n_blocks; a.nUpd = (int)(p->upd.size() - i);
     for (int k = 0; k < a.nUpd; k++) a.upd[k] = p->upd[i + k];
-    if ((d_ratio && lifter > 0 ? vp_pv_launch_formant(a, d_ratio, d_formant, lifter, st) : d_ratio ? vp_pv_launch_curve(a, d_ratio, st) : vp_pv_launch(a, st)) != hipSuccess)
+    if ((d_ratio && locked ? vp_pv_launch_lock(a, d_ratio, st) : d_ratio && lifter > 0 ? vp_pv_launch_formant(a, d_ratio, d_formant, lifter, st)
+         : d_ratio ? vp_pv_launch_curve(a, d_ratio, st) : vp_pv_launch(a, st)) != hipSuccess)
         return VP_ERR_HIP;
     p->allRatio = 0.0; p->allReset = false;
     std::fill(p->ratioPend.begin(), p->ratioPend.end(), 0.0);
@@ -2296,6 +2311,14 @@ extern "C" int vp_pv_process_blocks_curve_device(vp_pv *p, const float *d_in, fl
     if (!p || !d_in || !d_out || !d_ratio || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio);
+}
+
+// the curve call with peak locking (vp_k_pv_stream_lock): the record's two arrays hold the previous frame's phases and theta
+extern "C" int vp_pv_process_blocks_locked_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream)
+{
+    if (!p || !d_in || !d_out || !d_ratio || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio, nullptr, 0, true);
 }
 
 // the curve call with the cepstral formant correction (vp_k_pv_stream_formant): d_formant [S] or NULL (1.0), lifter in samples

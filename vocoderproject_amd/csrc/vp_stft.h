@@ -47,6 +47,11 @@ hipError_t vp_stft_stretch_prepare_device();
 // vp_stft_launch_curve, d_formant [nStreams] formant ratios or nullptr (1), nc the lifter length in samples (4 .. 64); a.F == 1024
 hipError_t vp_stft_launch_formant(const VpStftArgs &a, const double *d_ratio, const double *d_formant, int nc, int nStreams, hipStream_t st);
 hipError_t vp_stft_formant_prepare_device();
+// the 1024-point ratio-curve build with peak locking (vp_k_stft_pv_lock; csrc/vp_stft_lock.inc): d_ratio as in vp_stft_launch_curve;
+// a.F == 1024.  Its dynamic LDS at this hop: the curve build's plus the masks, owners and map of the locked stage
+hipError_t vp_stft_launch_lock(const VpStftArgs &a, const double *d_ratio, int nStreams, hipStream_t st);
+hipError_t vp_stft_lock_prepare_device();
+size_t vp_stft_lock_lds_bytes(int hop);
 
 // ---- streaming phase vocoder (vp_pv_*): one workgroup per stream and call, state in HBM between calls -----------------------------
 #define VP_PV_MAX_UPDATES 16            // interval changes / resets carried in a process call's arguments
@@ -87,3 +92,7 @@ hipError_t vp_pv_curve_prepare_device();
 // ... and with the cepstral formant correction (vp_k_pv_stream_formant): d_formant [a.S] or nullptr (1), nc the lifter length (4 .. 64)
 hipError_t vp_pv_launch_formant(const VpPvArgs &a, const double *d_ratio, const double *d_formant, int nc, hipStream_t st);
 hipError_t vp_pv_formant_prepare_device();
+// the curve call with peak locking (vp_k_pv_stream_lock): theta in the record's accumulator array, the record unchanged
+hipError_t vp_pv_launch_lock(const VpPvArgs &a, const double *d_ratio, hipStream_t st);
+hipError_t vp_pv_lock_prepare_device();
+size_t vp_pv_lock_lds_bytes();

@@ -1113,5 +1113,8 @@ hipError_t vp_pv_launch(const VpPvArgs &a, hipStream_t st)
 // ---- the phase-vocoder kernels with frames analysed at caller-given positions: time stretch (vp_stft_time_stretch) ----
 #include "vp_stft_stretch.inc"
 
+// ---- the ratio-curve kernels with peak locking (vp_stft_pitch_shift_locked, vp_pv_process_blocks_locked_device) ----
+#include "vp_stft_lock.inc"
+
 // ---- the ratio-curve kernels with the cepstral formant correction (vp_stft_pitch_shift_formant, vp_pv_process_blocks_formant_device) ----
 #include "vp_stft_formant.inc"

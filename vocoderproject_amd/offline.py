@@ -212,19 +212,21 @@ def glide_curve(lens, start, end, N, n_blocks):
     return c
 
 
-def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, processor=None, formant=None, lifter=32):
+def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, processor=None, formant=None, lifter=32, locked=False):
     """pv_shift with a glide: every recording's interval moves linearly from `start` to `end` semitones over its length, one value per
     block, through the streaming phase vocoder's ratio-curve call (PhaseVocoderStream.run(curve=...): several blocks per call, each
     with its own interval).  Returns float32 [2][len] per recording.  `processor` (tests): an object with latency and
     run(x, blocks_per_call, curve) to use instead of a new PhaseVocoderStream.  formant (semitones; None: the call above, unchanged): the
     formant-preserving call instead -- the spectral envelope moves by `formant` semitones (0: it stays) whatever the pitch does, with a
-    cepstral lifter of `lifter` samples; run then also receives formant_semitones and lifter."""
+    cepstral lifter of `lifter` samples; run then also receives formant_semitones and lifter.  locked: the peak-locked call instead
+    (run then also receives locked=True); not together with formant."""
     S = len(voices)
     if S == 0:
         raise ValueError("no recordings")
     if not (-12.0 <= float(start) <= 12.0 and -12.0 <= float(end) <= 12.0):
         raise ValueError("glide: intervals within +-12 semitones expected")
     _check_formant(formant, lifter)
+    _check_locked(locked, formant)
     p = processor
     if p is None:
         from . import PhaseVocoderStream
@@ -239,7 +241,43 @@ def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, 
         x[s, :lens[s]] = v
     curve = glide_curve(lens, start, end, N, -(-(T + int(p.latency)) // int(N)))
     kw = {} if formant is None else dict(formant_semitones=float(formant), lifter=int(lifter))
+    if locked:
+        kw["locked"] = True
     y = p.run(x, blocks_per_call=int(blocks_per_call), curve=curve, **kw)     # aligned with the input: the latency is off
+    return [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
+
+
+def _check_locked(locked, formant, F=1024):
+    if locked and formant is not None:
+        raise ValueError("--locked and --formant exclude each other: formant correction on top of peak locking is not built")
+    if locked and int(F) != 1024:
+        raise ValueError("--locked: 1024-point frames expected (the peak-locked kernels are not built for 2048)")
+
+
+def pv_shift_locked(voices, shift, N=1024, hop=256, device=0, blocks_per_call=16, processor=None):
+    """pv_shift through the PEAK-LOCKED call: every recording by its own fixed interval (one value or one per recording), streamed block
+    by block through PhaseVocoderStream.run(curve=..., locked=True) -- a constant curve.  Returns float32 [2][len] per recording.
+    `processor` (tests): an object with latency and run(x, blocks_per_call, curve, locked) to use instead of a new PhaseVocoderStream."""
+    S = len(voices)
+    if S == 0:
+        raise ValueError("no recordings")
+    per = [float(v) for v in shift] if isinstance(shift, (list, tuple, np.ndarray)) else [float(shift)] * S
+    if len(per) != S:
+        raise ValueError("shift: one value per recording expected")
+    if not all(-12.0 <= v <= 12.0 for v in per):
+        raise ValueError("shift: intervals within +-12 semitones expected")
+    p = processor
+    if p is None:
+        from . import PhaseVocoderStream
+        p = PhaseVocoderStream(S, int(N), hop=int(hop), device=device)
+    lens = [int(np.asarray(v).shape[-1]) for v in voices]
+    x = np.zeros((S, max(lens)), np.float32)
+    for s, v in enumerate(voices):
+        v = np.asarray(v, np.float32)
+        if v.ndim != 1:
+            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
+        x[s, :lens[s]] = v
+    y = p.run(x, blocks_per_call=int(blocks_per_call), curve=np.array([per]), locked=True)
     return [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
 
 
@@ -373,7 +411,7 @@ class _AutotuneRunner:
     def __init__(self, F, hop, device):
         self.F, self.hop, self.device = int(F), int(hop), device
 
-    def run(self, x, fs, keys, formant=None, lifter=32):
+    def run(self, x, fs, keys, formant=None, lifter=32, locked=False):
         import torch
         from . import StftRoundTrip
         dev = torch.device("cuda", self.device)
@@ -381,7 +419,8 @@ class _AutotuneRunner:
         try:
             d_in = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
             d_out = torch.empty_like(d_in)
-            period, ratio = st.autotune(d_in, d_out, float(fs), keys=[int(k) for k in keys], formant_semitones=formant, lifter=int(lifter))
+            lk = {"locked": True} if locked else {}
+            period, ratio = st.autotune(d_in, d_out, float(fs), keys=[int(k) for k in keys], formant_semitones=formant, lifter=int(lifter), **lk)
             torch.cuda.synchronize(dev)
             return d_out.cpu().numpy(), period.cpu().numpy(), ratio.cpu().numpy()
         finally:
@@ -395,14 +434,16 @@ def tune_length(max_len, fs, F, hop):
     return max(F + -(-int(max_len) // hop) * hop, F + int(np.ceil(float(fs) / 100.0)))
 
 
-def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, with_track=False, formant=None, lifter=32):
+def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, with_track=False, formant=None, lifter=32, locked=False):
     """A batch of recordings through the pitch tracker and the one-shot phase vocoder (StftRoundTrip.autotune: one stream per recording):
     every frame is moved onto the nearest note of its recording's key.  key: Notes::key 0..12 (12 = chromatic), one value or one per
     recording.  The recordings are zero-padded to a common length (tune_length).  Returns float32 [2][len] per recording (the corrected
     signal on both channels); with_track: also period int32 [S][nF] and ratio float64 [S][nF] of the padded batch.  `processor` (tests): an
     object with run(x, fs, keys) to use instead of the GPU.  formant (semitones; None: the correction above, unchanged): the correction
     keeps the spectral envelope apart from the pitch (StftRoundTrip.autotune(formant_semitones=...); 1024-point frames) -- 0 leaves the
-    singer's formants where they were; lifter: the cepstral lifter, 4 .. 64 samples; run then also receives formant and lifter."""
+    singer's formants where they were; lifter: the cepstral lifter, 4 .. 64 samples; run then also receives formant and lifter.
+    locked: the correction runs through the peak-locked call (StftRoundTrip.autotune(locked=True); 1024-point frames, not together with
+    formant); run then also receives locked=True."""
     S = len(voices)
     if S == 0:
         raise ValueError("no recordings")
@@ -416,6 +457,7 @@ def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, w
     _check_formant(formant, lifter)
     if formant is not None and int(F) != 1024:
         raise ValueError("pvtune --formant: 1024-point frames expected (the formant kernels are not built for 2048)")
+    _check_locked(locked, formant, F)
     lens = [int(np.asarray(v).shape[-1]) for v in voices]
     T = tune_length(max(lens), fs, F, hop)
     x = np.zeros((S, T), np.float32)
@@ -426,6 +468,8 @@ def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, w
         x[s, :lens[s]] = v
     p = processor if processor is not None else _AutotuneRunner(F, hop, device)
     kw = {} if formant is None else dict(formant=float(formant), lifter=int(lifter))
+    if locked:
+        kw["locked"] = True
     y, period, ratio = p.run(x, float(fs), keys, **kw)
     outs = [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
     return (outs, period, ratio) if with_track else outs
@@ -438,9 +482,10 @@ class _StreamTuneRunner:
     def __init__(self, N, hop, F, hold, glide, device, blocks_per_call=16):
         self.N, self.hop, self.F, self.hold, self.glide, self.device, self.k = int(N), int(hop), int(F), int(hold), float(glide), device, int(blocks_per_call)
 
-    def run(self, x, fs, keys, formant=None, lifter=32):
+    def run(self, x, fs, keys, formant=None, lifter=32, locked=False):
         import torch
         from . import PhaseVocoderStream, StreamingPitchTracker
+        lk = {"locked": True} if locked else {}
         S, N = x.shape[0], self.N
         nb = x.shape[1] // N
         dev = torch.device("cuda", self.device)
@@ -450,7 +495,7 @@ class _StreamTuneRunner:
             d_in = torch.from_numpy(np.ascontiguousarray(x.reshape(S, nb, N).transpose(1, 0, 2), np.float32)).to(dev)
             d_out = torch.empty_like(d_in)
             tables = [pv.autotune_device(trk, d_in[b:b + self.k], d_out[b:b + self.k], n_blocks=min(self.k, nb - b), keys=[int(k) for k in keys],
-                                         formant_semitones=formant, lifter=int(lifter))
+                                         formant_semitones=formant, lifter=int(lifter), **lk)
                       for b in range(0, nb, self.k)]
             torch.cuda.synchronize(dev)
             y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(S, nb * N)
@@ -469,14 +514,15 @@ def stream_tune_length(max_len, N, hop):
 
 
 def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glide=1.0, device=0, processor=None, with_track=False, formant=None,
-                       lifter=32):
+                       lifter=32, locked=False):
     """pv_autotune block by block, as a live caller would run it: the streaming tracker (StreamingPitchTracker, analysis length F) decides
     one ratio per block of N samples from the audio received so far, holds the last voiced ratio for `hold` unvoiced blocks and moves the
     fraction `glide` of the way to its target per block; the streaming phase vocoder (1024-point frames) shifts along that table.  The
     recordings are zero-padded to whole blocks that also hold the shifter's latency, which is taken off the front.  Returns float32
     [2][len] per recording; with_track: also period int32 [n_blocks][S] and ratio float64 [n_blocks][S] of the padded batch.  A decision
     costs the same at every N: N = 64 costs 16 times as much per second of audio as N = 1024.  `processor` (tests): an object with
-    run(x, fs, keys) to use instead of the GPU.  formant, lifter: as pv_autotune's (the shifter's frames are 1024 points whatever F)."""
+    run(x, fs, keys) to use instead of the GPU.  formant, lifter, locked: as pv_autotune's (the shifter's frames are 1024 points whatever
+    F)."""
     S = len(voices)
     if S == 0:
         raise ValueError("no recordings")
@@ -488,6 +534,7 @@ def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glid
     if not 8000.0 <= float(fs) <= 51200.0:
         raise ValueError("pvtune: sample rates from 8000 to 51200 Hz are served")
     _check_formant(formant, lifter)
+    _check_locked(locked, formant)
     if int(N) < 1 or int(F) not in (1024, 2048):
         raise ValueError("pvtune --stream: a block of at least one sample and a tracker frame of 1024 or 2048 expected")
     if not (0 <= int(hold) <= 1 << 20 and 0.0 < float(glide) <= 1.0):
@@ -502,6 +549,8 @@ def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glid
         x[s, :lens[s]] = v
     p = processor if processor is not None else _StreamTuneRunner(N, hop, F, hold, glide, device)
     kw = {} if formant is None else dict(formant=float(formant), lifter=int(lifter))
+    if locked:
+        kw["locked"] = True
     y, period, ratio = p.run(x, float(fs), keys, **kw)
     outs = [np.ascontiguousarray(np.stack([y[s, lat:lat + lens[s]]] * 2)) for s in range(S)]
     return (outs, period, ratio) if with_track else outs
@@ -538,6 +587,9 @@ def main(argv=None):
                     help="pvshift, pvtune: keep the spectral envelope apart from the pitch and move the formants by ST semitones "
                          "(no value: 0, they stay where they were).  The value is optional, so put the flag BEHIND the input files or "
                          "in front of another option: `--formant a.wav` would read a.wav as the interval")
+    ap.add_argument("--locked", action="store_true",
+                    help="pvshift (--shift or --glide), pvtune [--stream]: the peak-locked phase vocoder -- a spectral peak's whole region moves "
+                         "and turns as one, so tones keep their level (1024-point frames; not together with --formant)")
     ap.add_argument("--lifter", type=int, default=32, help="--formant: length of the cepstral lifter in samples, 4 to 64 (short: a smoother envelope)")
     ap.add_argument("--hold", type=int, default=0, help="pvtune --stream: unvoiced blocks over which the last voiced ratio is kept")
     ap.add_argument("--stretch", type=float, default=None, help="stretch: output duration / input duration, 0.25 to 4 (--shift: semitones on top)")
@@ -558,7 +610,13 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.formant is not None and a.flow not in ("pvshift", "pvtune"):
         raise SystemExit("--formant: pvshift and pvtune take it")
+    if a.locked and a.flow not in ("pvshift", "pvtune"):
+        raise SystemExit("--locked: pvshift and pvtune take it")
+    if a.locked and a.formant is not None:
+        raise SystemExit("--locked and --formant exclude each other: formant correction on top of peak locking is not built")
     fkw = {} if a.formant is None else dict(formant=a.formant, lifter=a.lifter)
+    if a.locked:
+        fkw["locked"] = True
 
     recs = [read_wav(f) for f in a.inputs]
     fs = recs[0][0]
@@ -605,6 +663,11 @@ def main(argv=None):
                 raise SystemExit("--glide: A:B expected, two intervals in semitones")
             try:
                 outs = pv_glide(voices, g0, g1, N=a.block, hop=a.hop, device=a.device, **fkw)     # (a glide is streamed: one interval per block)
+            except ValueError as e:
+                raise SystemExit(str(e))
+        elif a.locked:
+            try:
+                outs = pv_shift_locked(voices, a.shift, N=a.block, hop=a.hop, device=a.device)
             except ValueError as e:
                 raise SystemExit(str(e))
         elif a.formant is not None:

@@ -135,6 +135,9 @@ def load_library():
         L.vp_stft_pitch_shift_curve.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p]
         L.vp_semitones_to_ratios.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
         L.vp_pv_process_blocks_curve_device.argtypes = [vp, fp, fp, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "vp_stft_pitch_shift_locked"):       # (the peak-locked entries; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_stft_pitch_shift_locked.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p]
+        L.vp_pv_process_blocks_locked_device.argtypes = [vp, fp, fp, C.c_void_p, C.c_int, C.c_void_p]
     if hasattr(L, "vp_stft_time_stretch"):             # (the time stretch; absent from older libraries loaded through VP_AMD_LIB)
         L.vp_stft_time_stretch.argtypes = [vp, fp, C.c_int, C.c_void_p, fp, C.c_double, C.c_void_p]
         L.vp_stretch_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]
@@ -660,6 +663,26 @@ class StftRoundTrip:
         if rc:
             raise VpError(rc, self.L.vp_error_string(rc).decode())
 
+    def pitch_shift_locked(self, d_in, d_out, semitones=None, stream=None, d_ratio=None):
+        """pitch_shift_curve with peak locking (vp_stft_pitch_shift_locked; 1024-point frames): every frame's spectral peaks are found and a
+        peak's whole region of bins moves by one integer offset and turns by one accumulated angle, so a sinusoid's main lobe stays one
+        windowed sinusoid (the definition is tests/pv_lock_reference.py).  `semitones`, `d_ratio` and `stream` as in pitch_shift_curve --
+        the same table-building path.  A 2048-point handle raises VpError (VP_ERR_GEOMETRY)."""
+        import torch
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
+        assert d_out.is_cuda and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
+        assert (semitones is None) != (d_ratio is None), "one of semitones and d_ratio"
+        if d_ratio is None:
+            st = np.asarray(semitones, dtype=np.float64)
+            assert st.shape in ((self.n_frames,), (self.S, self.n_frames)), st.shape
+            if not hasattr(self, "_curve_tables"):
+                self._curve_tables = {}
+            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(st, (self.S, self.n_frames)), d_in.device)
+        assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (self.S, self.n_frames) and d_ratio.is_contiguous()
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        self._track_chk(self.L.vp_stft_pitch_shift_locked(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), C.c_void_p(stream)))
+
     def pitch_shift_formant(self, d_in, d_out, semitones=None, stream=None, d_ratio=None, formant_semitones=0.0, lifter=FORMANT_LIFTER, d_formant=None):
         """pitch_shift_curve with the spectral envelope kept apart from the pitch (vp_stft_pitch_shift_formant; 1024-point frames): the
         formants stay where they were (formant_semitones = 0, the default) or move by an interval of their own, a scalar or [S] values,
@@ -754,14 +777,22 @@ class StftRoundTrip:
                                                    period.data_ptr(), ratio.data_ptr(), C.c_void_p(stream)))
         return period, ratio
 
-    def autotune(self, d_in, d_out, sample_rate, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER):
+    def autotune(self, d_in, d_out, sample_rate, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False):
         """Automatic pitch correction (vp_stft_autotune): track_pitch, then pitch_shift_curve along its ratios, on one stream; d_out has
         the bits of those two calls.  Returns track_pitch's (period, ratio).
         formant_semitones (a scalar or [S]; None: the call above, unchanged): the correction runs through pitch_shift_formant instead
-        (vp_stft_autotune_formant) -- 0 keeps the formants where the singer had them."""
+        (vp_stft_autotune_formant) -- 0 keeps the formants where the singer had them.
+        locked=True: track_pitch followed by pitch_shift_locked along its ratios, on the same stream (not together with
+        formant_semitones: ValueError before any launch)."""
         import torch
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
         assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
+        if locked:
+            if formant_semitones is not None:
+                raise ValueError("locked and formant_semitones exclude each other: formant correction on top of locking is not built")
+            period, ratio = self.track_pitch(d_in, sample_rate, keys=keys, stream=stream)
+            self.pitch_shift_locked(d_in, d_out, stream=stream, d_ratio=ratio)
+            return period, ratio
         d_key, period, ratio = self._track_tables(keys, d_in.device)
         if stream is None:
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
@@ -835,7 +866,7 @@ class PhaseVocoderStream:
         return y
 
     def process_device(self, d_in, d_out, n_blocks=1, stream=None, semitones_per_block=None, d_ratio=None, formant_semitones=None, lifter=FORMANT_LIFTER,
-                       d_formant=None):
+                       d_formant=None, locked=False):
         """n_blocks blocks on the device: torch float32 [n_blocks][S][N] (or [S][N] for one block), enqueued on `stream`
         (default: the current torch stream) without synchronising.
         semitones_per_block: array-like [n_blocks] or [n_blocks][S], |value| <= 12 -- this call's frames take the interval of the block in
@@ -845,8 +876,14 @@ class PhaseVocoderStream:
         formant_semitones (a scalar or [S], |value| <= 12; None: the calls above, unchanged) or d_formant (device float64 [S] of ratios):
         the call keeps the spectral envelope apart from the pitch (vp_pv_process_blocks_formant_device) -- 0 leaves the formants where
         they were; `lifter` is the cepstral lifter's length, 4 .. 64.  It is a curve call: without a table of its own it takes the
-        intervals set_semitones holds, for every block."""
+        intervals set_semitones holds, for every block.
+        locked=True: the curve call with peak locking (vp_pv_process_blocks_locked_device); without a table of its own it takes the
+        intervals set_semitones holds, like a formant call.  Not together with formant_semitones / d_formant: ValueError before any
+        launch.  The kinds of call share the stream's state: after a change of kind the output is finite but carries a phase jump
+        (reset() the stream at the change to avoid it)."""
         import torch
+        if locked and (formant_semitones is not None or d_formant is not None):
+            raise ValueError("locked and formant_semitones exclude each other: formant correction on top of locking is not built")
         shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
         assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == shape and d_out.is_contiguous()
@@ -861,13 +898,17 @@ class PhaseVocoderStream:
             st = np.broadcast_to(st.reshape(int(n_blocks), -1), (int(n_blocks), self.S))
             d_ratio = _upload_ratios(self._curve_tables, st, d_in.device)
         formant = formant_semitones is not None or d_formant is not None
-        if formant and d_ratio is None:
+        if (formant or locked) and d_ratio is None:
             if not hasattr(self, "_curve_tables"):
                 self._curve_tables = {}
             held = np.array([self.semitones(s) for s in range(self.S)])
             d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(held, (int(n_blocks), self.S)), d_in.device)
         if d_ratio is not None:
             assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (int(n_blocks), self.S) and d_ratio.is_contiguous()
+            if locked:
+                self._chk(self.L.vp_pv_process_blocks_locked_device(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), int(n_blocks),
+                                                                    C.c_void_p(stream)))
+                return
             if formant:
                 d_formant = _device_formants(self, formant_semitones, d_formant, d_in.device)
                 self._chk(self.L.vp_pv_process_blocks_formant_device(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), d_formant.data_ptr(),
@@ -878,14 +919,22 @@ class PhaseVocoderStream:
             return
         self._chk(self.L.vp_pv_process_blocks_device(self.h, d_in.data_ptr(), d_out.data_ptr(), int(n_blocks), C.c_void_p(stream)))
 
-    def autotune_device(self, tracker, d_in, d_out, n_blocks=1, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER):
+    def autotune_device(self, tracker, d_in, d_out, n_blocks=1, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False):
         """Automatic pitch correction block by block (vp_pv_autotune_blocks_device): `tracker` (a StreamingPitchTracker of the same
         streams, block size and device) decides one ratio per block and stream from the audio received so far, this stream shifts along
         that table, both on `stream`; d_out has the bits of tracker.process_device followed by process_device(d_ratio=...).  Returns the
         tracker's (period, ratio), device tensors [n_blocks][S].  reset() does not reach the tracker: reset both.
         formant_semitones (a scalar or [S]; None: the call above, unchanged): the shift runs through the formant call instead
-        (vp_pv_autotune_blocks_formant_device)."""
+        (vp_pv_autotune_blocks_formant_device).
+        locked=True: tracker.process_device followed by process_device(d_ratio=..., locked=True) on the same stream (not together with
+        formant_semitones: ValueError before any launch)."""
         import torch
+        if locked:
+            if formant_semitones is not None:
+                raise ValueError("locked and formant_semitones exclude each other: formant correction on top of locking is not built")
+            period, ratio = tracker.process_device(d_in, n_blocks=n_blocks, keys=keys, stream=stream)
+            self.process_device(d_in, d_out, n_blocks=n_blocks, stream=stream, d_ratio=ratio, locked=True)
+            return period, ratio
         shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
         assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == shape and d_out.is_contiguous()
@@ -902,7 +951,7 @@ class PhaseVocoderStream:
                                                       period.data_ptr(), ratio.data_ptr(), int(n_blocks), C.c_void_p(stream)))
         return period, ratio
 
-    def run(self, x, blocks_per_call=8, curve=None, autotune=None, keys=None, formant_semitones=None, lifter=FORMANT_LIFTER):
+    def run(self, x, blocks_per_call=8, curve=None, autotune=None, keys=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False):
         """Whole signals float [S][T] -> output aligned with the input, [S][T]: the input padded with `latency` zeros (and up to
         whole blocks), streamed through the device entry point `blocks_per_call` blocks at a time, the first `latency` samples
         dropped.  Continues from the handle's state (reset() first for a fresh start).
@@ -910,8 +959,12 @@ class PhaseVocoderStream:
         row), through process_device(semitones_per_block=...).
         autotune: a StreamingPitchTracker instead -- every call goes through autotune_device(autotune, ..., keys=keys), and the result is
         (output, period, ratio) with the tracker's tables as numpy arrays [n_blocks][S] (the padding blocks included).
-        formant_semitones (a scalar or [S]; None: as above, unchanged): every call is a formant call (process_device / autotune_device)."""
+        formant_semitones (a scalar or [S]; None: as above, unchanged): every call is a formant call (process_device / autotune_device).
+        locked=True: every call is a peak-locked call (process_device / autotune_device with locked=True; not with formant_semitones)."""
         assert curve is None or autotune is None, "one of curve and autotune"
+        if locked and formant_semitones is not None:
+            raise ValueError("locked and formant_semitones exclude each other: formant correction on top of locking is not built")
+        lk = {"locked": True} if locked else {}                     # (without the flag: exactly the calls made before it existed)
         import torch
         x = np.asarray(x, dtype=np.float32)
         assert x.ndim == 2 and x.shape[0] == self.S, x.shape
@@ -931,12 +984,12 @@ class PhaseVocoderStream:
             k = min(int(blocks_per_call), nb - b)
             if autotune is not None:
                 tables.append(self.autotune_device(autotune, d_in[b:b + k], d_out[b:b + k], n_blocks=k, keys=keys, formant_semitones=formant_semitones,
-                                                   lifter=lifter))
+                                                   lifter=lifter, **lk))
             elif curve is None:
-                self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k, formant_semitones=formant_semitones, lifter=lifter)
+                self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k, formant_semitones=formant_semitones, lifter=lifter, **lk)
             else:
                 self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k, semitones_per_block=curve[b:b + k], formant_semitones=formant_semitones,
-                                    lifter=lifter)
+                                    lifter=lifter, **lk)
             b += k
         torch.cuda.synchronize(dev)
         y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, nb * N)
