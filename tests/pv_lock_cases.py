@@ -1,5 +1,7 @@
 """The peak-locked test matrix (vp_stft_pitch_shift_locked, vp_pv_process_blocks_locked_device): signals, curves and cases that
 tests/test_pv_lock_reference_cpu.py (gate, identity, teeth, quality) and tests/test_gpu_pv_lock.py (kernels against NumPy) iterate.
+tests/pv_lock_edge_cases.py (the edge cases, with tests/test_pv_lock_edges_cpu.py and tests/test_gpu_pv_lock_edges.py) takes the bound,
+the gate tolerance, the teeth, the lengths and the streaming call pattern from here, and the CPU file pins what this matrix reaches.
 Test infrastructure only.  The definition is tests/pv_lock_reference.py; the bound of every pointwise GPU comparison is pv_cases.bound's,
 
     |y - ref| <= 4 O 2^-24 max(1, max |ref|)       at every sample,

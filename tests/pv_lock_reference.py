@@ -18,7 +18,9 @@ with the ratio r clamped to [0.5, 2] (fmax first: a NaN is 0.5), phases in TURNS
 
 locked_roundtrip is that statement (turns, rfft).  locked_roundtrip_b states the same stage a second way -- phases and angles kept in
 radians, the full complex fft, explicit loops for peaks, ownership and the gather -- as the check of the first.  `mutant` names a
-deliberately wrong variant of the first form (the tests' teeth): noprop, tieup, ratio, floor, noown, late, strict.
+deliberately wrong variant of the first form (the tests' teeth): noprop, tieup, ratio, floor, noown, late, strict, and the EDGE_MUTANTS
+that only frames without a peak, frames that lose every peak past N and sparse masks can tell from the definition.  `trace` collects the
+stage's intermediates per frame (lock_stage); with trace=None nothing changes (tests/test_pv_lock_edges_cpu.py asserts the bits).
 
 The unwrap of the second form divides its radians by 2 pi and wraps in turns, like the first.  Bins 0 and N of a real frame are real:
 their phases are exactly 0 or half a turn (pi / 2 pi is exactly 0.5 in binary), so when such a bin is a peak and changes sign between two
@@ -33,6 +35,13 @@ import pv_stream_reference as P
 from stft_reference import TWO_PI, window
 
 MUTANTS = ("noprop", "tieup", "ratio", "floor", "noown", "late", "strict")
+# wrong variants at the EDGES of the stage (tests/pv_lock_edge_cases.py names the case that sees each):
+#   silent_theta  a frame without peaks zeroes theta            silent_prev  a frame without peaks leaves pprev
+#   gone_theta    a frame whose peaks all leave past N does not advance theta
+#   drop_n        a peak with P' == N is dropped                top_lost     a peak at bin N is not a peak
+#   no_lower      bins below the lowest peak (below the lowest shifted peak) have no owner: zero output, theta 0
+#   near_only     a bin more than 64 bins from both of its neighbours takes the upper one
+EDGE_MUTANTS = ("silent_theta", "silent_prev", "gone_theta", "drop_n", "no_lower", "near_only", "top_lost")
 
 
 def clamp_ratio(r):
@@ -40,8 +49,8 @@ def clamp_ratio(r):
     return np.fmin(np.fmax(np.where(np.isnan(r), 0.5, r), 0.5), 2.0)
 
 
-def nearest(idx, n, tie_up=False):
-    """Owner of each of n bins among the sorted, non-empty idx; ties to the lower (tie_up: to the upper)."""
+def nearest(idx, n, tie_up=False, near_only=False):
+    """Owner of each of n bins among the sorted, non-empty idx; ties to the lower (tie_up: to the upper; near_only: the edge mutant)."""
     idx = np.asarray(idx, np.int64)
     k = np.arange(n)
     j = np.searchsorted(idx, k, side="right") - 1                 # last idx <= k, or -1
@@ -49,7 +58,10 @@ def nearest(idx, n, tie_up=False):
     hi = idx[np.clip(j + 1, 0, len(idx) - 1)]
     dlo = np.where(j >= 0, k - lo, n + 1)
     dhi = np.where(j + 1 < len(idx), hi - k, n + 1)
-    return np.where((dhi < dlo) if not tie_up else (dhi <= dlo), hi, lo)
+    up = (dhi < dlo) if not tie_up else (dhi <= dlo)
+    if near_only:
+        up = up | ((dlo > 64) & (dhi > 64) & (j >= 0) & (j + 1 < len(idx)))
+    return np.where(up, hi, lo)
 
 
 def frame_ratios(ratio, nF):
@@ -69,8 +81,10 @@ class LockState:
         self.theta = np.zeros(nb)
 
 
-def lock_stage(X, r, st, O, mutant=None):
-    """One frame of the stage: X complex [nb], r the clamped ratio; st is updated; returns Y."""
+def lock_stage(X, r, st, O, mutant=None, trace=None):
+    """One frame of the stage: X complex [nb], r the clamped ratio; st is updated; returns Y.  `trace`: a list that receives one dict of
+    the definition's intermediates per frame (P, own, Ps, Pa, owns: int arrays, owns None where no shifted peak is left; r; silent: no
+    peak; gone: peaks, all shifted past N; tie: the peaks among bins 0 and N whose unwrap sat exactly on the half turn, a tuple)."""
     nb = len(X)
     N = nb - 1
     k = np.arange(nb)
@@ -79,51 +93,73 @@ def lock_stage(X, r, st, O, mutant=None):
     d = p - st.pprev - k / O
     d -= np.rint(d)
     nu = k + d * O
-    st.pprev = p
     mp = np.concatenate(([-1.0, -1.0], m, [-1.0, -1.0]))
     c = mp[2:-2]
     if mutant == "strict":
         pk = (c > 0) & (c > mp[1:-3]) & (c > mp[0:-4]) & (c > mp[3:-1]) & (c > mp[4:])
     else:
         pk = (c > 0) & (c > mp[1:-3]) & (c > mp[0:-4]) & (c >= mp[3:-1]) & (c >= mp[4:])
+    if mutant == "top_lost":
+        pk[N] = False
     P = np.nonzero(pk)[0]
+    if not (mutant == "silent_prev" and len(P) == 0):
+        st.pprev = p
     Y = np.zeros(nb, complex)
     if len(P) == 0:
+        if mutant == "silent_theta":
+            st.theta = np.zeros(nb)
+        if trace is not None:
+            e = np.zeros(0, np.int64)
+            trace.append(dict(P=e, own=None, Ps=e, Pa=e, owns=None, r=float(r), silent=True, gone=False, tie=()))
         return Y
     tie = mutant == "tieup"
-    own = nearest(P, nb, tie)
+    near = mutant == "near_only"
+    own = nearest(P, nb, tie, near)
     t = st.theta[P] + nu[P] * ((r if mutant == "ratio" else r - 1.0)) / O
     newth = np.zeros(nb)
     newth[P] = t - np.rint(t)
     Pp = np.floor(P * r + (0.0 if mutant == "floor" else 0.5)).astype(np.int64)
-    keep = Pp <= N
+    keep = (Pp < N) if mutant == "drop_n" else (Pp <= N)
     Ps, Pa = Pp[keep], P[keep]
     if mutant == "floor" and len(Ps):                             # (floor(P r) need not be distinct: the last one stays)
         Ps, first = np.unique(Ps[::-1], return_index=True)
         Pa = Pa[::-1][first]
+    owns = None
     if len(Ps):
         src = np.zeros(nb, np.int64)
         src[Ps] = Pa
-        owns = nearest(Ps, nb, tie)
+        owns = nearest(Ps, nb, tie, near)
         pa = src[owns]
         kk = k - (owns - pa)
         kc = np.clip(kk, 0, N)
         ok = (kk >= 0) & (kk <= N)
         if mutant != "noown":
             ok &= own[kc] == pa
+        if mutant == "no_lower":
+            ok &= (k >= Ps[0]) & (kk >= P[0])
         Y = np.where(ok, X[kc] * np.exp(2j * np.pi * newth[pa]), 0)
-    if mutant == "noprop":
+    if trace is not None:
+        ends = [e for e in (0, N) if pk[e]]
+        trace.append(dict(P=P, own=own, Ps=Ps, Pa=Pa, owns=owns, r=float(r), silent=False, gone=len(Ps) == 0,
+                          tie=tuple(e for e in ends if abs(d[e]) == 0.5)))
+    if mutant == "gone_theta" and len(Ps) == 0:
+        pass
+    elif mutant == "noprop":
         st.theta = st.theta.copy()
         st.theta[P] = newth[P]
     else:
         st.theta = newth[own]
+        if mutant == "no_lower":
+            st.theta = np.where(k >= P[0], st.theta, 0.0)
     Y[0] = Y[0].real
     Y[-1] = Y[-1].real
     return Y
 
 
-def locked_roundtrip(x, ratio, F=1024, hop=256, mutant=None):
-    """x: float array [T]; ratio: scalar or [nFrames] -> float64 [T]."""
+def locked_roundtrip(x, ratio, F=1024, hop=256, mutant=None, trace=None, perturb=None):
+    """x: float array [T]; ratio: scalar or [nFrames] -> float64 [T].  `trace`: lock_stage's.  `perturb` (eps, seed): the conditioning
+    probe -- every frame's spectrum is moved by eps times its largest magnitude (seeded complex noise; real at bins 0 and N) before the
+    stage."""
     x = np.asarray(x, np.float64)
     T = len(x)
     w = window(F)
@@ -134,10 +170,15 @@ def locked_roundtrip(x, ratio, F=1024, hop=256, mutant=None):
     if mutant == "late":
         r = np.roll(r, 1)
     st = LockState(F // 2 + 1)
+    rng = np.random.default_rng([perturb[1], 41]) if perturb is not None else None
     y = np.zeros(T)
     for f in range(nF):
         X = np.fft.rfft(x[f * hop:f * hop + F] * w)
-        Y = lock_stage(X, r[f], st, O, mutant)
+        if perturb is not None:
+            e = rng.standard_normal(len(X)) + 1j * rng.standard_normal(len(X))
+            e[0], e[-1] = e[0].real, e[-1].real                   # (bins 0 and N of a real frame are real by construction)
+            X = X + perturb[0] * np.abs(X).max() * e
+        Y = lock_stage(X, r[f], st, O, mutant, trace)
         y[f * hop:f * hop + F] += np.fft.irfft(Y, F) * w
     return y * scale
 
@@ -231,18 +272,22 @@ class LockStreamRef(P.PvStreamRef):
     F - gcd(N, hop), reset) with the locked stage: process(x, ratio) one block at a time is vp_pv_process_blocks_locked_device driven
     block by block -- every frame of the call takes the call's ratio."""
 
+    def __init__(self, N, hop=256, F=1024, ratio=1.0, trace=None, mutant=None):
+        self.trace, self.mutant = trace, mutant
+        super().__init__(N, hop, F, ratio)
+
     def reset(self):
         super().reset()
         self.lock = LockState(self.F // 2 + 1)
 
     def _frame(self, seg, f, ratio):
-        Y = lock_stage(np.fft.rfft(seg * self.w), float(clamp_ratio(ratio)), self.lock, self.F // self.hop)
+        Y = lock_stage(np.fft.rfft(seg * self.w), float(clamp_ratio(ratio)), self.lock, self.F // self.hop, self.mutant, self.trace)
         return np.fft.irfft(Y, self.F) * self.w
 
 
-def by_block(x, N, hop, block_ratio):
+def by_block(x, N, hop, block_ratio, trace=None):
     """x [T] (T a multiple of N) streamed block by block, block b with block_ratio[b] -> the streaming call's output [T] (float64)."""
-    r = LockStreamRef(N, hop)
+    r = LockStreamRef(N, hop, trace=trace)
     return np.concatenate([r.process(x[b * N:(b + 1) * N], block_ratio[b]) for b in range(len(x) // N)])
 
 
