@@ -366,8 +366,9 @@ int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d_out, const
  *   theta[k] = th[own[k]] for every k.  A frame without peaks (all zeros) gives Y = 0 and leaves theta.
  * A region is translated whole: at r > 1 the gaps stay empty, at r < 1 neighbouring regions are cut where they meet, not added.  At
  * r = 1 the stage is the identity.  1024-point frames, every hop, always double, one workgroup per stream, no allocation.
- * Out of scope: 2048-point frames; formant correction on top of locking; locking in the time stretch; fractional-bin interpolation of
- * the offset (the integer offset is why a tone at -12 semitones loses level); adding overlapping regions; several voices per call.
+ * Out of scope: 2048-point frames; formant correction on top of locking; fractional-bin interpolation of the offset (the integer offset
+ * is why a tone at -12 semitones loses level); adding overlapping regions; several voices per call.  Locking in the time stretch is
+ * vp_stft_time_stretch_locked.
  * VP_ERR_INVALID_ARG (null handle, input, output or ratio table) and VP_ERR_GEOMETRY (a 2048-point handle) are reported before the
  * device is touched and vp_stft_last_error says which; VP_ERR_HIP as vp_stft_pitch_shift. */
 int vp_stft_pitch_shift_locked(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream);
@@ -404,6 +405,21 @@ int vp_semitones_to_ratios(const double *semitones, double *ratios, long n);
  * VP_ERR_INVALID_ARG for null pointers, n_in < frame_len or |semitones| > 12 (checked before the device is touched), VP_ERR_HIP when the
  * device refused the kernels' LDS size at create. */
 int vp_stft_time_stretch(vp_stft *p, const float *d_in, int n_in, const int *d_pos, float *d_out, double semitones, void *hip_stream);
+/* The time stretch with PEAK LOCKING (kernel vp_k_stft_pv_stretch_lock): vp_stft_time_stretch's framing -- positions q_f, advances D_f,
+ * frame f overlap-added at output sample f hop -- with vp_stft_pitch_shift_locked's stage and its per-frame, per-stream ratio table
+ * (clamped to [0.5, 2], a NaN is 0.5).  The definition is tests/pv_stretch_lock_reference.py: the locked stage with two changes, phases in
+ * turns:
+ *   unwrap    d = p - pprev - (k D_f) / frame_len, d -= rint(d);  nu = k + d (frame_len / D_f);
+ *   rotation  per peak P: t = theta[P] + nu[P] ((r hop - D_f) / frame_len), th[P] = t - rint(t) -- the analysis phase of a partial advances
+ *             nu D / frame_len turns per frame, the synthesis must advance r nu hop / frame_len.
+ * Peaks, ownership, the shift P' = floor(P r + 0.5), the gather, the propagation of theta, silent frames and the real bins 0 and 512 are
+ * unchanged.  The table d_pos[s][f] = f hop with n_in = T gives vp_stft_pitch_shift_locked's bits.  1024-point frames, every hop, always
+ * double, one workgroup per stream, no allocation.  Out of scope: a streaming form, 2048-point frames, formant correction.
+ * d_in: device float [n_streams][n_in]; d_pos: device int [n_streams][vp_stft_num_frames(p)]; d_out: device float [n_streams][T];
+ * d_ratio: device double [n_streams][vp_stft_num_frames(p)].  Both tables are read when the kernel runs.
+ * VP_ERR_INVALID_ARG (a null handle or pointer, n_in < frame_len) and VP_ERR_GEOMETRY (a 2048-point handle) are reported before the
+ * device is touched and vp_stft_last_error says which; VP_ERR_HIP as vp_stft_pitch_shift. */
+int vp_stft_time_stretch_locked(vp_stft *p, const float *d_in, int n_in, const int *d_pos, float *d_out, const double *d_ratio, void *hip_stream);
 /* A constant stretch's table: pos[f] = min(floor(f hop / stretch), n_in - frame_len), f < n_frames; stretch = output duration / input
  * duration in [0.25, 4].  VP_ERR_INVALID_ARG outside that range, for a stretch that is not finite, n_in < frame_len or hop <= 0; nothing
  * is written then.  Host array; no device is touched. */

@@ -1,0 +1,235 @@
+"""CPU-side checks of the peak-locked time stretch's definition (tests/pv_stretch_lock_reference.py) and of the items the GPU tests compare
+on (tests/pv_stretch_lock_cases.py): the gate (two statements of the reference agree on every item), the conditioning probe (every item
+compared pointwise on the GPU passes gate and probe; the demoted ones are named, few, and at hop 512 only), the fixed-grid table gives the
+locked pitch shift's bits, ratio 1 on that table is the round trip, the teeth (named mutants are far away on a gated item chosen to see
+them), the quality the stage exists for (a stretched tone's envelope ripples less than under the plain stretch, at the right frequency),
+that the entry point is declared and exported and refuses null arguments without a device, and the offline flow's plumbing against
+stubs.  profiles/pv_stretch_lock_quality.txt is tools/pv_stretch_lock_quality.py's print of the quality table.  Run with -s for the
+PVSTRETCHLOCK lines.
+
+Measured on the 528 gate and edge items: the two forms differ by at most 3.4e-12 (tone-tone, stretch 4, +7, hop 512); 17 items move by
+1 % of their GPU bound or more under the probe (up to 0.61 of it), all at hop 512 -- pv_stretch_lock_cases.DEMOTED.  Quality, ripple
+locked / plain at hop 256: 227.3 Hz 0.06 (x0.5), 0.12 (x1.5), 0.002 (x0.25), 0.05 (x2 +7), 0.07 (x0.5 -5); 1000.7 Hz 0.01, 0.02, 0.0002,
+0.07, 0.007."""
+import ctypes as C
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import pv_lock_cases as LC  # noqa: E402
+import pv_lock_reference as LR  # noqa: E402
+import pv_stretch_cases as SC  # noqa: E402
+import pv_stretch_lock_cases as K  # noqa: E402
+import pv_stretch_lock_reference as SLR  # noqa: E402
+import stft_reference  # noqa: E402
+
+F = K.F
+SYMBOL = "vp_stft_time_stretch_locked"
+
+
+def _gate_probe_properties(it):
+    y = K.reference(it)
+    gate, moved = K.gate_and_probe(it)
+    print(f"PVSTRETCHLOCK {it.name}: gate {gate:.3g} moved {moved:.3g} of the bound, max |ref| {np.abs(y).max():.3g}")
+    assert np.all(np.isfinite(y)) and np.abs(y).max() <= K.ceiling(it) + 1e-9, it.name
+    return gate, moved
+
+
+def _assert_pointwise(it):
+    gate, moved = _gate_probe_properties(it)
+    if K.pointwise(it):
+        assert gate <= K.GATE_TOL, (it.name, gate)
+        assert moved < K.CONDITION_SHARE, (it.name, moved)
+    else:
+        assert moved >= K.CONDITION_SHARE or gate > K.GATE_TOL, (it.name, "is demoted but passes gate and probe")
+
+
+# ---- the gate and the conditioning probe ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c", K.GATE_CASES, ids=K.gate_id)
+def test_gate_items_pass_the_gate_and_the_probe(c):
+    it = K.gate_item(c)
+    assert np.abs(K.reference(it)).max() > 1e-3
+    _assert_pointwise(it)
+
+
+@pytest.mark.parametrize("c", K.EDGE_CASES, ids=SC.case_id)
+def test_edge_items_pass_the_gate_and_the_probe(c):
+    for it in K.edge_case_items(c):
+        _assert_pointwise(it)
+
+
+@pytest.mark.parametrize("c", K.GPU_CASES, ids=K.gpu_id)
+def test_gpu_items_pass_the_gate_and_the_probe(c):
+    for it in K.gpu_items(c):
+        assert K.pointwise(it)
+        _assert_pointwise(it)
+
+
+def test_small_and_big_items_pass_the_gate_and_the_probe():
+    for it in [it for c, n_in in K.SMALL_CASES for it in K.edge_case_items(c, n_in)] + K.big_items():
+        assert K.pointwise(it)
+        _assert_pointwise(it)
+
+
+def test_the_demoted_items_are_named_few_and_at_hop_512_only():
+    named = [K.gate_item(c) for c in K.GATE_CASES] + [K.edge_item(e) for e in K.EDGE_ROWS]
+    names = [it.name for it in named]
+    assert len(names) == len(set(names)) == 528
+    assert set(K.DEMOTED) <= set(names) and len(K.DEMOTED) == len(set(K.DEMOTED))
+    assert len(K.DEMOTED) <= 0.05 * len(names), len(K.DEMOTED)
+    assert all(it.hop == 512 for it in named if it.name in K.DEMOTED)
+
+
+def test_the_edge_tables_reach_both_clamps_and_odd_advances():
+    """The tie the definition names: an odd advance puts bin N's nominal term on a half-integer."""
+    import pv_stretch_reference as SR
+    seen = set()
+    for c in K.EDGE_CASES:
+        for it in K.edge_case_items(c):
+            q = SR.clamp_positions(it.pos, len(it.x), F)
+            D = SR.advances(q, it.hop, F)
+            raw = np.diff(q)
+            seen |= {"low"} if np.any(raw < 1) else set()
+            seen |= {"high"} if np.any(raw > F) else set()
+            seen |= {"odd"} if np.any(D[1:] % 2 == 1) else set()
+            seen |= {"qlow"} if np.any(np.asarray(it.pos) < 0) else set()
+            seen |= {"qhigh"} if np.any(np.asarray(it.pos) > len(it.x) - F) else set()
+            seen |= {"unaligned"} if np.any(q % 2 == 1) else set()
+    assert seen == {"low", "high", "odd", "qlow", "qhigh", "unaligned"}, seen
+
+
+# ---- the fixed grid -----------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("hop", K.HOPS)
+def test_the_grid_table_gives_the_locked_pitch_shift_bit_for_bit(hop):
+    rng = np.random.default_rng([hop, 61])
+    for sig in ("noise", "voice+noise", "silence-noise"):
+        nF = 11
+        T = LC.length(nF, hop, 5)
+        x = LC.SIGNALS[sig](T, hop)
+        r = LC.ratio_of(rng.uniform(-13.0, 13.0, nF))
+        y = SLR.stretch_locked_roundtrip(x, np.arange(nF) * hop, T, r, F, hop)
+        assert np.abs(y).max() > 1e-3
+        assert np.array_equal(y, LR.locked_roundtrip(x, r, F, hop)), sig
+
+
+@pytest.mark.parametrize("hop", K.HOPS)
+def test_ratio_one_on_the_grid_table_is_the_round_trip(hop):
+    nF = 9
+    T = LC.length(nF, hop, 5)
+    for sig in ("voice+noise", "noise"):
+        x = LC.SIGNALS[sig](T, 1)
+        ref = stft_reference.stft_roundtrip(x, F, hop)
+        for y in (SLR.stretch_locked_roundtrip(x, np.arange(nF) * hop, T, 1.0, F, hop), SLR.stretch_locked_roundtrip_b(x, np.arange(nF) * hop, T, 1.0, F, hop)):
+            assert np.abs(y - ref).max() <= K.bound(hop, ref), sig
+
+
+def test_a_curve_outside_the_clamp_equals_the_clamped_one():
+    it = K.gate_item(K.GateCase("voice", 0.8, "steps", 256, K.GATE_NF))
+    r = LC.curve("outside", K.GATE_NF)
+    a = SLR.stretch_locked_roundtrip(it.x, it.pos, it.T, r, F, 256)
+    assert np.array_equal(a, SLR.stretch_locked_roundtrip(it.x, it.pos, it.T, np.clip(np.nan_to_num(r, nan=0.5), 0.5, 2.0), F, 256))
+
+
+# ---- teeth ----------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mutant", SLR.MUTANTS)
+def test_every_mutant_is_far_from_the_reference_on_a_gated_item(mutant):
+    it = K.teeth_item(mutant)
+    assert K.pointwise(it)
+    gate, moved = K.gate_and_probe(it)
+    assert gate <= K.GATE_TOL and moved < K.CONDITION_SHARE
+    ref = K.reference(it)
+    dist = np.abs(ref - K.reference(it, "a", mutant)).max() / K.bound(it.hop, ref)
+    print(f"PVSTRETCHLOCK mutant {mutant} on {it.name}: {dist:.3g} GPU bounds from the reference")
+    assert dist >= K.TEETH, dist
+
+
+# ---- quality ----------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("freq", K.QUALITY_TONES)
+def test_a_stretched_tone_ripples_less_than_under_the_plain_stretch(freq):
+    for a, v in K.QUALITY_PAIRS:
+        x, pos, T = K.quality_setup(freq, a)
+        r = K.ratio_of(v)
+        rp, ap = LC.ripple(SLR.plain_stretch(x, pos, T, r, F, K.QUALITY_HOP))
+        yl = SLR.stretch_locked_roundtrip(x, pos, T, r, F, K.QUALITY_HOP)
+        rl, al = LC.ripple(yl)
+        fpk = K.peak_frequency(yl)
+        print(f"PVSTRETCHLOCK quality {freq} Hz x{a:g} {v:+g} st: ripple plain {rp:.4f} locked {rl:.4f} (ratio {rl / rp:.3f}), level plain {ap:.3f} locked {al:.3f}, "
+              f"peak {fpk:.2f} Hz")
+        assert rl < rp, (freq, a, v, rl, rp)
+        assert abs(fpk - freq * r) <= 1.0, (freq, a, v, fpk)
+
+
+# ---- the entry point ------------------------------------------------------------------------------------------------------------------------------------
+def test_the_symbol_is_declared_and_exported_and_null_arguments_fail_without_a_device():
+    from vocoderproject_amd import build
+    lib = C.CDLL(build.build())
+    txt = open(os.path.join(ROOT, "include", "vp_amd.h")).read()
+    assert hasattr(lib, SYMBOL) and SYMBOL + "(vp_stft *p, const float *d_in, int n_in, const int *d_pos, float *d_out, const double *d_ratio, void *hip_stream);" in txt
+    assert "locking in the time stretch;" not in txt                                     # no longer listed as out of scope of the locked call
+    assert lib.vp_abi_version() == 3
+    one = C.c_void_p(8)                                                                  # (a non-null pointer that is never followed)
+    fn = getattr(lib, SYMBOL)
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    assert fn(None, one, 4096, one, one, one, None) == -1
+    assert "vp_stft_stretch_lock.inc" in build.DEPS
+    # the call path builds its arguments on the stack: nothing is allocated
+    src = open(os.path.join(ROOT, "vocoderproject_amd", "csrc", "vp_capi.hip")).read()
+    body = src[src.index('extern "C" int ' + SYMBOL):]
+    body = body[:body.index("\n}\n")]
+    assert "hipMalloc" not in body and "new " not in body and "2048-point frames are not built" in body
+    assert body.index("VP_ERR_GEOMETRY") < body.index("hipSetDevice")                   # refused before the device is touched
+    from vocoderproject_amd import StftRoundTrip
+    assert callable(StftRoundTrip.time_stretch_locked)
+    py = open(os.path.join(ROOT, "vocoderproject_amd", "processor.py")).read()
+    assert re.search(r'if hasattr\(L, "vp_stft_time_stretch_locked"\):[^\n]*\n\s+L\.vp_stft_time_stretch_locked\.argtypes', py)
+
+
+# ---- the offline flow ---------------------------------------------------------------------------------------------------------------------------------------
+class _Echo:
+    """The offline flow's processor that only keeps what the flow hands it."""
+
+    def run(self, x, pos, T, semitones, **kw):
+        self.seen = (x.copy(), pos.copy(), T, semitones, kw)
+        return np.zeros((x.shape[0], T), np.float32)
+
+
+def test_offline_stretch_hands_locked_through_and_leaves_the_plain_call_as_it_was():
+    from vocoderproject_amd import offline
+    v = [np.arange(1, 5001, dtype=np.float32) / 8192, np.linspace(-1, 1, 1700).astype(np.float32)]
+    p, q = _Echo(), _Echo()
+    out = offline.pv_stretch(v, [1.5, 0.5], shift=3.0, processor=p, locked=True)
+    ref = offline.pv_stretch(v, [1.5, 0.5], shift=3.0, processor=q)
+    assert [o.shape for o in out] == [o.shape for o in ref] == [(2, 7500), (2, 850)]
+    assert p.seen[4] == {"locked": True} and q.seen[4] == {}                             # without the flag: run(x, pos, T, semitones), nothing more
+    assert np.array_equal(p.seen[0], q.seen[0]) and np.array_equal(p.seen[1], q.seen[1]) and p.seen[2:4] == q.seen[2:4]
+    with pytest.raises(ValueError):
+        offline.pv_stretch(v, 1.5, F=2048, processor=p, locked=True)
+    offline.pv_stretch(v, 1.5, F=2048, hop=512, processor=p)                             # (the plain stretch keeps its 2048-point frames)
+
+
+def test_offline_command_line_takes_locked_for_a_stretch(tmp_path, monkeypatch):
+    from vocoderproject_amd import offline
+    f = str(tmp_path / "a.wav")
+    offline.write_wav(f, 44100, np.linspace(-0.5, 0.5, 1000))
+    seen = {}
+
+    def fake(voices, stretch, **kw):
+        seen.update(n=[len(v) for v in voices], stretch=stretch, kw=kw)
+        return [np.zeros((2, int(np.ceil(len(v) * stretch))), np.float32) for v in voices]
+    monkeypatch.setattr(offline, "pv_stretch", fake)
+    out = str(tmp_path / "o")
+    assert offline.main(["stretch", f, "--stretch", "1.5", "--shift", "3", "--hop", "128", "--locked", "--out-dir", out]) == 0
+    assert seen["kw"] == dict(shift=3.0, F=1024, hop=128, device=0, locked=True) and seen["stretch"] == 1.5
+    assert offline.main(["stretch", f, "--stretch", "1.5", "--shift", "3", "--hop", "128", "--out-dir", out]) == 0
+    assert seen["kw"] == dict(shift=3.0, F=1024, hop=128, device=0)                      # the call as it was
+    monkeypatch.undo()
+    with pytest.raises(SystemExit):                                                      # refused before any processor exists
+        offline.main(["stretch", f, "--stretch", "1.5", "--locked", "--frame", "2048", "--out-dir", out])
+    with pytest.raises(SystemExit):
+        offline.main(["pitch", f, "--locked", "--out-dir", out])

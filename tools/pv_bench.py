@@ -7,6 +7,7 @@
     [VP_AMD_LIB=...] python tools/pv_bench.py --track [--reps 7] [--out profiles/pv_track_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --track-stream [--reps 7] [--out profiles/pv_track_stream_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --locked [--reps 7] [--out profiles/pv_lock_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --stretch-locked [--reps 7] [--out profiles/pv_stretch_lock_bench.txt]
 
 --curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
 "steps" curve, fixed, ...): 256 streams x 65 536 samples at 1024 points / hop 256 and 2048 points / hop 512 (vp_stft_pitch_shift against
@@ -35,6 +36,12 @@ time per call against the sum of its parts'.
 copied from, alternating in one process on the SAME "steps" table: one-shot, 256 streams x 65 536 samples, 1024 points / hop 256, on noise
 and on voiced signals (the stage's mask searches depend on how far apart the peaks are); then streaming, 16 blocks of 1024 per call.  The
 locked kernel's mean over the curve kernel's from the same run is the comparison; the kernels' resource listings follow.
+
+--stretch-locked: the locked time stretch (vp_stft_time_stretch_locked) beside both of its parents, alternating in one process: 256
+streams, 65 536 output samples, 1024 points / hop 256, on noise and on voiced signals, every call at +7 semitones.  The locked pitch shift
+(vp_k_stft_pv_lock) and the new kernel at the identity table f hop on the same input: the ratio is the cost of the positions alone.  Then
+the plain time stretch (vp_k_stft_pv_stretch) and the new kernel at stretch 0.5 and 2, each pair on the same input and table.  The kernels'
+resource listings follow.
 """
 import argparse
 import os
@@ -154,6 +161,38 @@ def locked_legs(reps, emit):
     report(f"streaming, {S} streams, {K} blocks of {N} per call of noise, hop = {hop}", alternate(legs, reps, 300), S * K * N // hop, base, emit)
     a.close()
     b.close()
+
+
+def stretch_locked_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import StftRoundTrip, semitones_to_ratios, stretch_positions
+    S, T, F, hop, fs = 256, 65536, 1024, 256, 44100.0
+    st = StftRoundTrip(S, T, F, hop)
+    nF = st.n_frames
+    y = torch.empty(S, T, device="cuda", dtype=torch.float32)
+    ratio = torch.from_numpy(np.full((S, nF), semitones_to_ratios([7.0])[0])).cuda()
+    parent = "locked +7 (parent kernel)"
+    n_max = int(T / 0.5) + F
+    for what, rows in (("noise", torch.randn(S, n_max, device="cuda", dtype=torch.float32) * 0.1), ("voiced signals", torch.from_numpy(voiced_rows(S, n_max, fs)).cuda())):
+        legs = {}
+        for a in (1.0, 0.5, 2.0):
+            n_in = T if a == 1.0 else int(T / a) + F                        # (stretch 1: the parent's input, row for row)
+            x = rows[:, :n_in].contiguous()
+            pos = torch.from_numpy(np.tile(stretch_positions(nF, hop, a, n_in, F), (S, 1))).cuda()
+            if a == 1.0:
+                assert np.array_equal(pos[0].cpu().numpy(), np.arange(nF) * hop)
+                legs[parent] = lambda x=x: st.pitch_shift_locked(x, y, d_ratio=ratio)
+                legs["stretch locked 1, +7 (identity table)"] = lambda x=x, pos=pos: st.time_stretch_locked(x, y, d_pos=pos, d_ratio=ratio)
+            else:
+                legs[f"plain stretch {a:g}, +7"] = lambda x=x, pos=pos: st.time_stretch(x, y, d_pos=pos, semitones=7.0)
+                legs[f"stretch locked {a:g}, +7"] = lambda x=x, pos=pos: st.time_stretch_locked(x, y, d_pos=pos, d_ratio=ratio)
+        times = alternate(legs, reps, 100)
+        report(f"locked time stretch, {S} streams x {T} output samples of {what}, F = {F}, hop = {hop}", times, S * nF, parent, emit)
+        mean = {k: sum(v) / len(v) for k, v in times.items()}
+        for a in (0.5, 2.0):
+            emit(f"  stretch locked {a:g} = {mean[f'plain stretch {a:g}, +7'] / mean[f'stretch locked {a:g}, +7']:.3f} x plain stretch {a:g} (frames/s, the same run)")
+    st.close()
 
 
 def stretch_legs(reps, emit):
@@ -303,10 +342,11 @@ def main():
     ap.add_argument("--track", action="store_true", help="the pitch-tracker legs instead of the fixed intervals")
     ap.add_argument("--track-stream", action="store_true", help="the streaming-tracker legs instead of the fixed intervals")
     ap.add_argument("--locked", action="store_true", help="the peak-locked legs instead of the fixed intervals")
+    ap.add_argument("--stretch-locked", action="store_true", help="the locked time-stretch legs instead of the fixed intervals")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="--curve / --stretch / --track: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked:
+    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.stretch_locked:
         return fixed_intervals()
     lines = []
 
@@ -327,6 +367,9 @@ def main():
     if a.locked:
         locked_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_stft_pv_curve", "vp_k_stft_pv_lock", "vp_k_pv_stream_curve", "vp_k_pv_stream_lock"))
+    if a.stretch_locked:
+        stretch_locked_legs(max(5, a.reps), emit)
+        resource_listing(emit, ("vp_k_stft_pv_lock", "vp_k_stft_pv_stretch", "vp_k_stft_pv_stretch_lock"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -1881,7 +1881,7 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     // THAT call; the plain and single-precision round trips (<= 64 KB) are served regardless.  The sticky HIP error is cleared so
     // that a later hipGetLastError() behind a launch does not report this one.
     p->pvOk = vp_stft_prepare_device() == hipSuccess && vp_stft_curve_prepare_device() == hipSuccess && vp_stft_stretch_prepare_device() == hipSuccess
-        && vp_stft_formant_prepare_device() == hipSuccess && vp_stft_lock_prepare_device() == hipSuccess;
+        && vp_stft_formant_prepare_device() == hipSuccess && vp_stft_lock_prepare_device() == hipSuccess && vp_stft_stretch_lock_prepare_device() == hipSuccess;
     if (!p->pvOk) (void)hipGetLastError();
     p->device = device; p->F = frame_len; p->hop = hop; p->S = n_streams; p->T = n_samples;
     p->nFrames = (n_samples - frame_len) / hop + 1;
@@ -1960,7 +1960,7 @@ extern "C" int vp_stft_get_precision(const vp_stft *p) { return p ? (p->f32 ? VP
 
 // (d_ratio: the phase-vocoder stage reads its ratio per frame from this table, `ratio` is unused then; d_pos: it reads frame f at input
 // sample d_pos[s][f] of rows of n_in samples -- the time stretch; lifter > 0: the ratio-curve build with the formant correction, d_formant
-// [S] or null; locked: the ratio-curve build with peak locking)
+// [S] or null; locked: the ratio-curve build with peak locking; d_ratio, d_pos and locked together: the locked time stretch)
 static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag, hipStream_t st, bool pv, double ratio, const double *d_ratio = nullptr,
                       const int *d_pos = nullptr, int n_in = 0, const double *d_formant = nullptr, int lifter = 0, bool locked = false)
 {
@@ -1988,6 +1988,7 @@ static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
     a.roundsPerRun = (a.nRounds + runs - 1) / runs;
     const int nRuns = (a.nRounds + a.roundsPerRun - 1) / a.roundsPerRun;
     if (d_ratio && lifter > 0) return vp_stft_launch_formant(a, d_ratio, d_formant, lifter, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
+    if (d_ratio && d_pos && locked) return vp_stft_launch_stretch_lock(a, d_ratio, d_pos, n_in, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     if (d_ratio && locked) return vp_stft_launch_lock(a, d_ratio, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     if (d_ratio) return vp_stft_launch_curve(a, d_ratio, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
     if (d_pos) return vp_stft_launch_stretch(a, d_pos, n_in, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
@@ -2065,6 +2066,19 @@ extern "C" int vp_stft_time_stretch(vp_stft *p, const float *d_in, int n_in, con
     if (!p->pvOk) return VP_ERR_HIP;                           // (as vp_stft_pitch_shift)
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, std::pow(2.0, semitones / 12.0), nullptr, d_pos, n_in);
+}
+
+// the time stretch with PEAK LOCKING (vp_k_stft_pv_stretch_lock; 1024-point frames): vp_stft_time_stretch's input, table and output with
+// vp_stft_pitch_shift_locked's ratio table, checked before the device is touched
+extern "C" int vp_stft_time_stretch_locked(vp_stft *p, const float *d_in, int n_in, const int *d_pos, float *d_out, const double *d_ratio, void *hip_stream)
+{
+    if (!p) return VP_ERR_INVALID_ARG;
+    if (!d_in || !d_pos || !d_out || !d_ratio) { p->lastError = "stretch locked: null input, position table, output or ratio table"; return VP_ERR_INVALID_ARG; }
+    if (n_in < p->F) { p->lastError = "stretch locked: the input row is shorter than one frame"; return VP_ERR_INVALID_ARG; }
+    if (p->F != 1024) { p->lastError = "stretch locked: 2048-point frames are not built (the peak-locked stage exists for 1024-point frames only)"; return VP_ERR_GEOMETRY; }
+    if (!p->pvOk) { p->lastError = "stretch locked: the device refused the phase-vocoder kernels' LDS size at create"; return VP_ERR_HIP; }   // (as vp_stft_pitch_shift)
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio, d_pos, n_in, nullptr, 0, true);
 }
 
 extern "C" int vp_stretch_positions(int *pos, int n_frames, int hop, double stretch, int n_in, int frame_len)

@@ -52,6 +52,10 @@ hipError_t vp_stft_formant_prepare_device();
 hipError_t vp_stft_launch_lock(const VpStftArgs &a, const double *d_ratio, int nStreams, hipStream_t st);
 hipError_t vp_stft_lock_prepare_device();
 size_t vp_stft_lock_lds_bytes(int hop);
+// the peak-locked build with frames at given positions (vp_k_stft_pv_stretch_lock; csrc/vp_stft_stretch_lock.inc): d_ratio as in
+// vp_stft_launch_lock, d_pos and nIn as in vp_stft_launch_stretch; a.F == 1024.  Its dynamic LDS is vp_stft_lock_lds_bytes(a.hop)
+hipError_t vp_stft_launch_stretch_lock(const VpStftArgs &a, const double *d_ratio, const int *d_pos, int nIn, int nStreams, hipStream_t st);
+hipError_t vp_stft_stretch_lock_prepare_device();
 
 // ---- streaming phase vocoder (vp_pv_*): one workgroup per stream and call, state in HBM between calls -----------------------------
 #define VP_PV_MAX_UPDATES 16            // interval changes / resets carried in a process call's arguments

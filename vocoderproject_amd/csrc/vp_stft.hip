@@ -1116,5 +1116,8 @@ hipError_t vp_pv_launch(const VpPvArgs &a, hipStream_t st)
 // ---- the ratio-curve kernels with peak locking (vp_stft_pitch_shift_locked, vp_pv_process_blocks_locked_device) ----
 #include "vp_stft_lock.inc"
 
+// ---- the peak-locked kernel with frames analysed at caller-given positions: the locked time stretch (vp_stft_time_stretch_locked) ----
+#include "vp_stft_stretch_lock.inc"
+
 // ---- the ratio-curve kernels with the cepstral formant correction (vp_stft_pitch_shift_formant, vp_pv_process_blocks_formant_device) ----
 #include "vp_stft_formant.inc"

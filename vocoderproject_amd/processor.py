@@ -141,6 +141,8 @@ def load_library():
     if hasattr(L, "vp_stft_time_stretch"):             # (the time stretch; absent from older libraries loaded through VP_AMD_LIB)
         L.vp_stft_time_stretch.argtypes = [vp, fp, C.c_int, C.c_void_p, fp, C.c_double, C.c_void_p]
         L.vp_stretch_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]
+    if hasattr(L, "vp_stft_time_stretch_locked"):      # (the locked time stretch; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_stft_time_stretch_locked.argtypes = [vp, fp, C.c_int, C.c_void_p, fp, C.c_void_p, C.c_void_p]
     if hasattr(L, "vp_stft_track_pitch"):              # (the pitch tracker; absent from older libraries loaded through VP_AMD_LIB)
         L.vp_track_tau_max.argtypes = [C.c_double]
         L.vp_stft_track_pitch.argtypes = [vp, fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -708,6 +710,25 @@ class StftRoundTrip:
         self._track_chk(self.L.vp_stft_pitch_shift_formant(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), d_formant.data_ptr(), int(lifter),
                                                            C.c_void_p(stream)))
 
+    def _position_table(self, positions, stretch, n_in, dev):
+        """The position table of a time-stretch call from host data -- `stretch` through stretch_positions, `positions` broadcast and
+        clipped to int32 -- in the device table the handle keeps per shape (self._stretch_tables), rewritten on torch's current stream."""
+        import torch
+        if stretch is not None:
+            a = np.broadcast_to(np.asarray(stretch, dtype=np.float64).reshape(-1), (self.S,))
+            pos = np.stack([stretch_positions(self.n_frames, self.hop, v, n_in, self.F) for v in a])
+        else:
+            pos = np.asarray(positions)
+            assert pos.dtype.kind in "iu" and pos.shape in ((self.n_frames,), (self.S, self.n_frames)), (pos.dtype, pos.shape)
+            pos = np.clip(np.broadcast_to(pos, (self.S, self.n_frames)), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
+        if not hasattr(self, "_stretch_tables"):
+            self._stretch_tables = {}
+        tab = self._stretch_tables.get(pos.shape)
+        if tab is None:
+            tab = self._stretch_tables[pos.shape] = torch.empty(pos.shape, dtype=torch.int32, device=dev)
+        tab.copy_(torch.from_numpy(np.ascontiguousarray(pos)))
+        return tab
+
     def time_stretch(self, d_in, d_out, positions=None, stretch=None, semitones=0.0, stream=None, d_pos=None):
         """Time stretch (vp_stft_time_stretch): pitch_shift with frame f of stream s analysed at input sample positions[s][f] and written
         at output sample f hop, so duration and pitch are independent.  d_in is float32 [S][n_in] with any n_in >= frame_len, d_out
@@ -726,26 +747,43 @@ class StftRoundTrip:
         assert n_in >= self.F, n_in
         assert (positions is not None) + (stretch is not None) + (d_pos is not None) == 1, "one of positions, stretch and d_pos"
         if d_pos is None:
-            if stretch is not None:
-                a = np.broadcast_to(np.asarray(stretch, dtype=np.float64).reshape(-1), (self.S,))
-                pos = np.stack([stretch_positions(self.n_frames, self.hop, v, n_in, self.F) for v in a])
-            else:
-                pos = np.asarray(positions)
-                assert pos.dtype.kind in "iu" and pos.shape in ((self.n_frames,), (self.S, self.n_frames)), (pos.dtype, pos.shape)
-                pos = np.clip(np.broadcast_to(pos, (self.S, self.n_frames)), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
-            if not hasattr(self, "_stretch_tables"):
-                self._stretch_tables = {}
-            tab = self._stretch_tables.get(pos.shape)
-            if tab is None:
-                tab = self._stretch_tables[pos.shape] = torch.empty(pos.shape, dtype=torch.int32, device=d_in.device)
-            tab.copy_(torch.from_numpy(np.ascontiguousarray(pos)))
-            d_pos = tab
+            d_pos = self._position_table(positions, stretch, n_in, d_in.device)
         assert d_pos.is_cuda and d_pos.dtype == torch.int32 and tuple(d_pos.shape) == (self.S, self.n_frames) and d_pos.is_contiguous()
         if stream is None:
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
         rc = self.L.vp_stft_time_stretch(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), float(semitones), C.c_void_p(stream))
         if rc:
             raise VpError(rc, self.L.vp_error_string(rc).decode())
+
+    def time_stretch_locked(self, d_in, d_out, positions=None, stretch=None, semitones=None, stream=None, d_pos=None, d_ratio=None):
+        """time_stretch with peak locking (vp_stft_time_stretch_locked; 1024-point frames): the frames are analysed at the table's positions
+        as in time_stretch, and the stage between the transforms is pitch_shift_locked's with the frame's own analysis advance -- a
+        sinusoid's main lobe stays one windowed sinusoid under any stretch, with or without a pitch shift on top (the definition is
+        tests/pv_stretch_lock_reference.py).  positions, stretch and d_pos as in time_stretch, from the same per-handle tables.  The pitch
+        is per frame and per stream: `semitones` a scalar, [n_frames] (every stream follows the curve) or [S][n_frames], each |value| <= 12,
+        None = no shift; d_ratio instead: a device float64 tensor [S][n_frames] of ratios, used as it is (the kernel clamps to [0.5, 2]).
+        A 2048-point handle raises VpError (VP_ERR_GEOMETRY)."""
+        import torch
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and d_in.dim() == 2 and d_in.shape[0] == self.S and d_in.is_contiguous()
+        assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
+        n_in = int(d_in.shape[1])
+        assert n_in >= self.F, n_in
+        assert (positions is not None) + (stretch is not None) + (d_pos is not None) == 1, "one of positions, stretch and d_pos"
+        assert semitones is None or d_ratio is None, "at most one of semitones and d_ratio"
+        if d_pos is None:
+            d_pos = self._position_table(positions, stretch, n_in, d_in.device)
+        assert d_pos.is_cuda and d_pos.dtype == torch.int32 and tuple(d_pos.shape) == (self.S, self.n_frames) and d_pos.is_contiguous()
+        if d_ratio is None:
+            st = np.asarray(0.0 if semitones is None else semitones, dtype=np.float64)
+            assert st.shape in ((), (self.n_frames,), (self.S, self.n_frames)), st.shape
+            if not hasattr(self, "_curve_tables"):
+                self._curve_tables = {}
+            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(st, (self.S, self.n_frames)), d_in.device)
+        assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (self.S, self.n_frames) and d_ratio.is_contiguous()
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        self._track_chk(self.L.vp_stft_time_stretch_locked(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(),
+                                                           C.c_void_p(stream)))
 
     def _track_tables(self, keys, dev):
         """(d_key or None, period, ratio): the call's key table and outputs.  The key table is kept per handle (one device int32 [S],
