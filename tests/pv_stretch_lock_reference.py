@@ -28,6 +28,16 @@ rint's rule (half to even) in both forms and in the kernel -- a rule, not a roun
   nod     the rotation is left at nu (r - 1) / O: the D term forgotten
   late    the ratio table one frame late
   nohigh  D_f = max(q_f - q_(f-1), 1): no upper clamp at F
+and the EDGE_MUTANTS, which only frames without a peak, the exact tie of the unwrap and a peak shifted onto bin N can tell from the
+definition (tests/pv_stretch_lock_edge_cases.py names the case that sees each):
+  silent_theta      a frame without peaks zeroes theta          silent_prev  a frame without peaks leaves pprev
+  tie_away          the unwrap rounds a half away from zero (C's round) instead of to even (rint)
+  drop_n            a peak with P' == N is dropped
+  hop_after_silent  the frame behind a frame without peaks takes hop as its advance
+
+`trace` collects the stage's intermediates per frame: pv_lock_reference.lock_stage's keys (P, own, Ps, Pa, owns, r, silent, gone, tie)
+and the frame's q and D; `tie` holds the peaks whose unwrap d sat exactly on +-1/2 (every bin, not only 0 and N).  With trace=None nothing
+changes (tests/test_pv_stretch_lock_edges_cpu.py asserts the bits on the 384 gate cases).
 """
 import numpy as np
 
@@ -36,11 +46,12 @@ import pv_stretch_reference as SR
 from stft_reference import TWO_PI, window
 
 MUTANTS = ("hop", "nod", "late", "nohigh")
+EDGE_MUTANTS = ("silent_theta", "silent_prev", "tie_away", "drop_n", "hop_after_silent")
 
 
-def stretch_lock_stage(X, r, D, st, F, hop, mutant=None):
+def stretch_lock_stage(X, r, D, st, F, hop, mutant=None, trace=None):
     """One frame of the stage: X complex [nb], r the clamped ratio, D the frame's analysis advance; st (LR.LockState) is updated;
-    returns Y."""
+    returns Y.  `trace`: a list that receives one dict per frame (the module's note; the caller adds q)."""
     nb = len(X)
     N = nb - 1
     O = F // hop
@@ -49,15 +60,21 @@ def stretch_lock_stage(X, r, D, st, F, hop, mutant=None):
     p = np.arctan2(X.imag, X.real) / TWO_PI
     Du = hop if mutant == "hop" else D
     d = p - st.pprev - (k * Du) / F
-    d -= np.rint(d)
+    d -= np.sign(d) * np.floor(np.abs(d) + 0.5) if mutant == "tie_away" else np.rint(d)
     nu = k + d * (F / Du)
     mp = np.concatenate(([-1.0, -1.0], m, [-1.0, -1.0]))
     c = mp[2:-2]
     pk = (c > 0) & (c > mp[1:-3]) & (c > mp[0:-4]) & (c >= mp[3:-1]) & (c >= mp[4:])
     P = np.nonzero(pk)[0]
-    st.pprev = p
+    if not (mutant == "silent_prev" and len(P) == 0):
+        st.pprev = p
     Y = np.zeros(nb, complex)
     if len(P) == 0:
+        if mutant == "silent_theta":
+            st.theta = np.zeros(nb)
+        if trace is not None:
+            e = np.zeros(0, np.int64)
+            trace.append(dict(P=e, own=None, Ps=e, Pa=e, owns=None, r=float(r), silent=True, gone=False, tie=(), D=int(D)))
         return Y
     own = LR.nearest(P, nb)
     if mutant == "nod":
@@ -67,8 +84,9 @@ def stretch_lock_stage(X, r, D, st, F, hop, mutant=None):
     newth = np.zeros(nb)
     newth[P] = t - np.rint(t)
     Pp = np.floor(P * r + 0.5).astype(np.int64)
-    keep = Pp <= N
+    keep = (Pp < N) if mutant == "drop_n" else (Pp <= N)
     Ps, Pa = Pp[keep], P[keep]
+    owns = None
     if len(Ps):
         src = np.zeros(nb, np.int64)
         src[Ps] = Pa
@@ -78,6 +96,9 @@ def stretch_lock_stage(X, r, D, st, F, hop, mutant=None):
         kc = np.clip(kk, 0, N)
         ok = (kk >= 0) & (kk <= N) & (own[kc] == pa)
         Y = np.where(ok, X[kc] * np.exp(2j * np.pi * newth[pa]), 0)
+    if trace is not None:
+        trace.append(dict(P=P, own=own, Ps=Ps, Pa=Pa, owns=owns, r=float(r), silent=False, gone=len(Ps) == 0,
+                          tie=tuple(int(e) for e in P if abs(d[e]) == 0.5), D=int(D)))
     st.theta = newth[own]
     Y[0] = Y[0].real
     Y[-1] = Y[-1].real
@@ -92,11 +113,12 @@ def _frames(x, pos, T, F, hop, mutant=None):
     return nF, q, SR.advances(q, hop, F, "nohigh" if mutant == "nohigh" else "delta")
 
 
-def stretch_locked_roundtrip(x, pos, T, ratio=1.0, F=1024, hop=256, mutant=None, perturb=None):
+def stretch_locked_roundtrip(x, pos, T, ratio=1.0, F=1024, hop=256, mutant=None, perturb=None, trace=None):
     """x: float [n_in], pos: int [nF], ratio: a scalar or [nF] -> float64 [T].  `perturb` (eps, seed): the conditioning probe of
-    pv_lock_reference.locked_roundtrip -- every frame's spectrum is moved by eps times its largest magnitude before the stage."""
+    pv_lock_reference.locked_roundtrip -- every frame's spectrum is moved by eps times its largest magnitude before the stage.
+    `trace`: stretch_lock_stage's, with every frame's q."""
     x = np.asarray(x, np.float64)
-    assert mutant is None or mutant in MUTANTS, mutant
+    assert mutant is None or mutant in MUTANTS + EDGE_MUTANTS, mutant
     nF, q, D = _frames(x, pos, T, F, hop, mutant)
     w = window(F)
     scale = 1.0 / np.sum(w[::hop] ** 2)
@@ -106,13 +128,18 @@ def stretch_locked_roundtrip(x, pos, T, ratio=1.0, F=1024, hop=256, mutant=None,
     st = LR.LockState(F // 2 + 1)
     rng = np.random.default_rng([perturb[1], 41]) if perturb is not None else None
     y = np.zeros(T)
+    behind_silent = False
     for f in range(nF):
         X = np.fft.rfft(x[q[f]:q[f] + F] * w)
         if perturb is not None:
             e = rng.standard_normal(len(X)) + 1j * rng.standard_normal(len(X))
             e[0], e[-1] = e[0].real, e[-1].real                   # (bins 0 and N of a real frame are real by construction)
             X = X + perturb[0] * np.abs(X).max() * e
-        Y = stretch_lock_stage(X, r[f], int(D[f]), st, F, hop, mutant)
+        Df = hop if mutant == "hop_after_silent" and behind_silent else int(D[f])
+        Y = stretch_lock_stage(X, r[f], Df, st, F, hop, mutant, trace)
+        if trace is not None:
+            trace[-1]["q"] = int(q[f])
+        behind_silent = not np.any(X)                             # (a spectrum with a non-zero bin has a peak: its largest, leftmost)
         y[f * hop:f * hop + F] += np.fft.irfft(Y, F) * w
     return y * scale
 
