@@ -91,6 +91,10 @@ def main():
         for r in (0, 1):
             print(f"  producer {r}, first Start's segment   " + " | ".join(f"{nm}: {ev(13 + r, k):.1f}" for k, nm in enumerate(finep)))
         print("  recursion, instance taken up at   " + " | ".join(f"{ev(15, k):.1f}" for k in range(7) if v[typ * 128 + 15 * 8 + k]))
+        # (the split FAST recursion: the parked segment -- the one the block's last Start opens -- has its first block's first pass
+        # parked by a producer / its first instance's walk begins on the recursion wavefront)
+        if v[typ * 128 + 13 * 8 + 7] or v[typ * 128 + 14 * 8 + 7]:
+            print(f"  split recursion, parked segment   block parked: {ev(13, 7):.1f} | walk started: {ev(14, 7):.1f}")
 
 
 if __name__ == "__main__":

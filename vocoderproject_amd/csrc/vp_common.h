@@ -183,6 +183,8 @@ struct VpWsSched {
     int startStep[WS_MAXS], startPar[WS_MAXS], startNeed[WS_MAXS];                 // startNeed: instances that must have been added to the
                                                                                     // output before the start's parity buffers are free
     int segA[WS_MAXS + 1], segB[WS_MAXS + 1];                                       // first and last instance of each segment
+    int segPark[WS_MAXS + 1];                                                       // FAST, orders <= 16: the segment's producers park the recursion's
+                                                                                    // first pass behind their gather trips (see ws_build_sched)
 };
 VP_HD static inline bool ws_build_sched(const VpGeom &g, int nChunk0, int nSteps, VpWsSched &sc)
 {
@@ -210,6 +212,18 @@ VP_HD static inline bool ws_build_sched(const VpGeom &g, int nChunk0, int nSteps
         nCh += 1;
     }
     sc.nInst = nI; sc.nStart = nS; sc.nSeg = nG;
+    // Which segments park the FAST recursion's first pass on the producers: those whose recursions are the block's TAIL -- the
+    // segment the block's last Start opens (no Start opens one behind it).  The first frame of a two-Start block and the frame in
+    // flight at entry stay as they were: their recursions end long before the tail's input exists, and their trips stand in front
+    // of the next Start's residual.  The parked segments are a suffix of the block's segments (ws_recursion relies on it).
+    // (-DWS_PARK_EVERY: every segment, the other rule that was measured)
+    for (int q = 0; q <= WS_MAXS; q++) {
+#ifdef WS_PARK_EVERY
+        sc.segPark[q] = (q < nG) ? 1 : 0;
+#else
+        sc.segPark[q] = (nS > 0 && q == nG - 1) ? 1 : 0;
+#endif
+    }
     return nI > 0;
 }
 

@@ -1102,6 +1102,70 @@ __device__ __forceinline__ void iir_block_wave_regs(const lds_f64 *x, lds_f64 *y
     }
 }
 
+// The two passes of iir_block_wave_regs as routines of their own (whole 64-sample blocks), so that the wave-specialised kernel's
+// producers can park pass 1 block by block behind their gather trips and the recursion wavefront is left with the walk: the same
+// terms into the same accumulators, joined in the same places -- the output is iir_block_wave_regs' bit for bit (which stays the
+// definition: the phase kernels call it).
+// Pass 1 of ONE block: the 48 terms of samples b + 16 .. b + 63, parked in y[b + lane].  One full wavefront.
+__device__ __forceinline__ void iir_block_park(const lds_f64 *x, lds_f64 *y, int b, const lds_f64 *hpad)
+{
+    const int lane = vp_tid() & 63, m = lane & 15;
+    double H[64];
+#pragma unroll
+    for (int j = 16; j < 48; j++) H[j] = hpad[WAVE + lane - j];               // h[lane - j], 0 for j > lane
+    const double X1 = x[b + 16 + m], X2 = x[b + 32 + m], X3 = x[b + 48 + m];
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
+    VP_BI_ROW(X1, 1)
+    // (the caller runs this between two gather trips, with the trips' state in registers: the last sixteen taps are requested only now,
+    // into the first row's registers -- 64 registers of taps at the peak instead of 96 -- and arrive while the second row is summed)
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int j = 48; j < 64; j++) H[j] = hpad[WAVE + lane - j];
+    VP_BI_ROW(X2, 2)
+    VP_BI_ROW(X3, 3)
+    y[b + lane] = (acc0 + acc1) + (acc2 + acc3);
+}
+// Pass 2's registers: taps 0..15 and the 16 history coefficients.  They are the FRAME's, so the caller may request them ahead of
+// the chunk (and keep them from chunk to chunk of one frame).
+struct IirWalkRegs { double H[16], A[16]; };
+__device__ __forceinline__ void iir_block_walk_load(IirWalkRegs &R, const lds_f64 *aL, int order_, const lds_f64 *hpad)
+{
+    const int lane = vp_tid() & 63, m = lane & 15;
+    const int order = __builtin_amdgcn_readfirstlane(order_);
+#pragma unroll
+    for (int j = 0; j < 16; j++) R.H[j] = hpad[WAVE + lane - j];
+#pragma unroll
+    for (int k = 1; k <= 16; k++) R.A[k - 1] = (m + k <= order) ? -aL[m + k] : 0.0;  // -a[m + k]
+}
+// Pass 2 over a chunk whose blocks are all parked in y[] (iir_block_park).  One full wavefront.
+__device__ __forceinline__ void iir_block_walk(const IirWalkRegs &R, const lds_f64 *x, lds_f64 *y, int n, int order_, bool haveHist0)
+{
+    const int lane = vp_tid() & 63, m = lane & 15;
+    const int order = __builtin_amdgcn_readfirstlane(order_);
+    double H[16], A[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) { H[j] = R.H[j]; A[j] = R.A[j]; }
+    double X0 = x[m];
+    for (int b = 0; b < n; b += WAVE) {
+        const bool hist = (b > 0) || haveHist0;
+        double Y3 = 0.0;
+        if (hist && 16 - m <= order) Y3 = y[b - 16 + m];
+        const double parked = y[b + lane];
+        double u0 = 0.0, u1 = 0.0;
+        VP_BI_T(u0, Y3, A[0], 15);  VP_BI_T(u1, Y3, A[1], 14);  VP_BI_T(u0, Y3, A[2], 13);  VP_BI_T(u1, Y3, A[3], 12);
+        VP_BI_T(u0, Y3, A[4], 11);  VP_BI_T(u1, Y3, A[5], 10);  VP_BI_T(u0, Y3, A[6], 9);   VP_BI_T(u1, Y3, A[7], 8);
+        VP_BI_T(u0, Y3, A[8], 7);   VP_BI_T(u1, Y3, A[9], 6);   VP_BI_T(u0, Y3, A[10], 5);  VP_BI_T(u1, Y3, A[11], 4);
+        VP_BI_T(u0, Y3, A[12], 3);  VP_BI_T(u1, Y3, A[13], 2);  VP_BI_T(u0, Y3, A[14], 1);  VP_BI_T(u1, Y3, A[15], 0);
+        X0 = X0 + (u0 + u1);
+        asm volatile("s_nop 1" : "+v"(X0));                                   // VALU write of X0 -> DPP read: 2 wait states
+        double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
+        VP_BI_ROW(X0, 0)
+        y[b + lane] = parked + ((acc0 + acc1) + (acc2 + acc3));
+        const int bn = b + WAVE;
+        if (bn < n) X0 = x[bn + m];
+    }
+}
+
 // The block form for orders 17..48 (whole 64-sample blocks, ONE full wavefront), with the recursion between the blocks
 // reduced to what really is serial.  By linearity a block's outputs are
 //     y[b + i] = z[b + i] + sum_{k=1..order} Hc[i][k] * y[b - k],        z = T(h) (g x)   (zero-state response),

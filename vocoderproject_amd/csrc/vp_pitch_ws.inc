@@ -170,8 +170,12 @@ __device__ __forceinline__ SegTab ws_seg_tab(lds_f64 *base)
 // by ONE wavefront (lane = pending mark).  Leaves the number of grains in *ngOut and advances st->stMarkIdx.
 // (st: the frame's tracker state, read only -- at a Start the background's published copy, which the group adopts meanwhile --;
 // stIdx: the group's own copy, whose chunk progress stMarkIdx this advances)
+// park: the segment's producers park the recursion's first pass behind their trips (VpWsSched::segPark) -- the pass then covers the
+// segment's chunks whole, from the first one's first sample, in trips aligned to the recursion's 64-sample blocks (chunks are
+// multiples of 64 samples here): every block of every instance is some trip's, so no instance is ever parked in part.  Lanes and
+// trips that no grain covers write back what they read.
 __device__ __forceinline__ void ws_psola_table_seg(const VpGeom &g, const VpDev &d, const lds_state *st, lds_state *stIdx, const SegTab &G, int kFirst, int kLast,
-                                                   int pSFirst, lds_ctl *ctl, int sg)
+                                                   int pSFirst, lds_ctl *ctl, int sg, bool park)
 {
     const int lane = vp_tid() & 63;
     const int T = (st->pitch > 1) ? st->period : st->prevVoicedPeriod;
@@ -218,10 +222,11 @@ __device__ __forceinline__ void ws_psola_table_seg(const VpGeom &g, const VpDev 
     lo = __builtin_amdgcn_readfirstlane(lo);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) hi = max(hi, __shfl_xor(hi, off, WAVE));
+    if (park) { lo = kFirst * g.C; hi = max(hi, (kLast + 1) * g.C); }
     if (lane == 0) {
         stIdx->stMarkIdx = smi0 + ng;
         ctl->gNg[sg] = ng; ctl->gLo[sg] = lo; ctl->gHi[sg] = hi;
-        ctl->gNT[sg] = (ng > 0 && hi > lo) ? (hi - lo + WAVE - 1) / WAVE : 0;
+        ctl->gNT[sg] = ((ng > 0 || park) && hi > lo) ? (hi - lo + WAVE - 1) / WAVE : 0;
     }
 }
 // the gather: 64 consecutive output samples per trip.  Lane q holds grain q's entry in registers; the grains that touch a trip's
@@ -233,8 +238,14 @@ __device__ __forceinline__ void ws_psola_table_seg(const VpGeom &g, const VpDev 
 // beyond it.  Whoever finishes an instance's last trip releases it to the recursion, in instance order (psDone).
 // (Background wavefronts that had finished their starts took trips too, in one experiment: no gain beside the lead's SIMD-mates and a
 // loss -- 4 % -- when the one that shares the recursion's SIMD joined in.  What bounds the pass is one trip's latency, not hands.)
+// hpPark (a parked segment, else null): the frame's padded impulse response.  A trip's 64 samples are FINAL when the trip stores
+// them -- every grain that covers a sample is added inside the trip that owns it, earlier segments' grains are in already, later
+// segments' grains start at or beyond their own chunks -- so the trip's owner runs the recursion's first pass on that block right
+// behind the store (iir_block_park into yFrame, which nobody reads there before the instance's recursion) -- for the blocks inside the
+// segment's own chunks: what a grain spills beyond the last chunk is not final yet.  The taps are requested per trip: 96 registers of
+// them do not fit beside the gather's state.  Parked instances are released with instMode 3.
 __device__ __forceinline__ void ws_psola_gather_seg(const VpGeom &g, const VpDev &d, const PitchLds &L, const SegTab &G, lds_ctl *ctl, int sg, int jA, int jB,
-                                                    int kFirst, bool first)
+                                                    int kFirst, bool first, const lds_f64 *hpPark = nullptr, int nChunk0 = 0)
 {
     const lds_state *st = L.st;
     const int lane = vp_tid() & 63;
@@ -257,7 +268,7 @@ __device__ __forceinline__ void ws_psola_gather_seg(const VpGeom &g, const VpDev
     auto release = [&](int j) {
         ws_wait_ge(&ctl->psDone, j, d);
         for (;;) {
-            if (lane == 0) ctl->instMode[j] = 2;
+            if (lane == 0) ctl->instMode[j] = hpPark ? 3 : 2;
             ws_signal(&ctl->psDone, j + 1);
             j++;
             if (j > jB || count(j - jA) != 0) break;
@@ -383,6 +394,12 @@ __device__ __forceinline__ void ws_psola_gather_seg(const VpGeom &g, const VpDev
             if (two && a2) accv += v2;
         }
         if (in) L.oE[i] = accv;
+        if (hpPark && b < (kFirst + jB - jA + 1) * g.C) {
+            iir_block_park((const lds_f64 *)L.oE, L.yF, b, hpPark);
+#ifdef VP_STAMPS
+            { const struct { int nChunk0; } c = {nChunk0}; if (m == 0) WS_EV(d, 13, 7); }   // (the parked segment's first block is parked)
+#endif
+        }
         WS_STAT(d, 0, 1); WS_STAT(d, 1, WS_CLK() - tTrip0);
         // done: the trip's instance counts it; its last one releases the instance
         int r = 0;
@@ -648,6 +665,9 @@ __device__ __forceinline__ void ws_producer(const VpGeom &g, const VpCall &c, co
         const int jA = sc.segA[sg], jB = sc.segB[sg];
         const int t = sc.instStep[jA], kFirst = sc.instK[jA], kLast = sc.instK[jB], p = sc.instPar[jA], si = sc.instStart[jA];
         const int pS = c.pStart + t * g.C;
+        // (FAST, orders up to 16 -- iir_block_wave_regs' path --: the segments the schedule names park the recursion's first pass)
+        const bool park = FAST && order <= 16 && sc.segPark[sg] != 0;
+        const lds_f64 *hpPark = park ? (const lds_f64 *)(sm + cv.hp + p * WS_HP(g)) : (const lds_f64 *)nullptr;
         WS_TR();
         L.xs = xsAll + t * g.C;
         L.oE = p ? frBase + 3 * g.F + 2048 : frBase;
@@ -686,7 +706,7 @@ __device__ __forceinline__ void ws_producer(const VpGeom &g, const VpCall &c, co
                 if (mode == 2) {
                     if (lane == 0) st->stMarkIdx = 0;                         // :238
                     wave_sync();
-                    ws_psola_table_seg(g, d, stPub, st, G, kFirst, kLast, pS, ctl, sg);
+                    ws_psola_table_seg(g, d, stPub, st, G, kFirst, kLast, pS, ctl, sg, park);
                 }
                 WS_TA(d, wq, 4);                                              // grain table
                 WS_FINEP(d, 2);
@@ -720,7 +740,7 @@ __device__ __forceinline__ void ws_producer(const VpGeom &g, const VpCall &c, co
             mode = (st->nAn != 0) ? 2 : 0;
             if (mode == 2) {
                 if (rank == 0) {
-                    ws_psola_table_seg(g, d, st, st, G, kFirst, kLast, pS, ctl, sg);
+                    ws_psola_table_seg(g, d, st, st, G, kFirst, kLast, pS, ctl, sg, park);
                     WS_TA(d, wq, 4);
                 } else {
                     // filterFIR(F-C, C, ...) :258-259 of the segment's chunks (what lies beyond: nothing there yet, :216) and, once per
@@ -744,7 +764,7 @@ __device__ __forceinline__ void ws_producer(const VpGeom &g, const VpCall &c, co
         if (mode == 2) {
             // the gather pass; the segment is over -- its tables, the residual and the quotient / Hann tables free for the next one's --
             // when its last instance is out
-            ws_psola_gather_seg(g, d, L, G, ctl, sg, jA, jB, kFirst, rank == 0);
+            ws_psola_gather_seg(g, d, L, G, ctl, sg, jA, jB, kFirst, rank == 0, hpPark, c.nChunk0);
             WS_FINEP(d, 4);
             WS_TA(d, wq, 5);                                                  // gather pass
             ws_wait_ge(&ctl->psDone, jB + 1, d);
@@ -819,7 +839,11 @@ __device__ __forceinline__ void ws_recursion(const VpGeom &g, const VpCall &c, c
             fill(fj, win);
         }
     };
-    for (int j = 0; j < nInst; j++) {
+    // FAST, orders up to 16: the instances of the segments whose producers park the routine's first pass (VpWsSched::segPark: a suffix
+    // of the block's segments) are the second loop's; everything else takes the one-piece routine as before
+    int jPark = nInst;
+    if (FAST && order <= 16) for (int sg = sc.nSeg - 1; sg >= 0 && sc.segPark[sg] != 0; sg--) jPark = sc.segA[sg];
+    for (int j = 0; j < jPark; j++) {
         const int p = sc.instPar[j];
         if (nIir > 1 && p != me) continue;
         WS_TR();
@@ -864,6 +888,34 @@ __device__ __forceinline__ void ws_recursion(const VpGeom &g, const VpCall &c, c
         else
             flush(j + 1, false);
         WS_TA(d, me, 4);                                                      // windowed add
+    }
+    if constexpr (FAST) {
+        // The parked instances: their blocks' first-pass sums lie in yFrame when the producers release them (instMode 3), so what is
+        // left on this chain is the walk.  Its 64 registers of taps and history coefficients are the FRAME's: a Cont instance has them
+        // before the wait -- kept from the chunk before, or requested while the producers are still at work (the frame in flight's
+        // lie in LDS since the prologue) -- instead of 80 LDS values requested behind it; a Start's are final only with its release.
+        IirWalkRegs R;
+        bool haveR = false;
+        for (int j = jPark; j < nInst; j++) {
+            const int p = sc.instPar[j];
+            WS_TR();
+            const int k = sc.instK[j], shift = k * g.C;
+            lds_f64 *oE = p ? frBase + 3 * g.F + 2048 : frBase, *yF = p ? frBase + 2 * g.F + 2048 : frBase + g.F;
+            const lds_f64 *aF = sm + cv.aF + p * WS_AF(g), *hpad = sm + cv.hp + p * WS_HP(g);
+            if (sc.instStart[j] >= 0) haveR = false;
+            else if (!haveR) { iir_block_walk_load(R, aF, order, hpad); haveR = true; }
+            ws_wait_ge(&ctl->psDone, j + 1, d);
+            WS_TA(d, me, 1);                                                  // waited for the producers
+            WS_FINER(d, j);
+            if (ctl->instMode[j] == 3) {
+                if (!haveR) { iir_block_walk_load(R, aF, order, hpad); haveR = true; }
+                if (j == jPark) WS_EV(d, 14, 7);                              // (diagnostic: the first parked instance's walk starts)
+                iir_block_walk(R, (const lds_f64 *)(oE + shift), yF + shift, g.C, order, shift > 0);
+            }
+            WS_TA(d, me, 2);                                                  // recursion
+            ws_signal(&ctl->iirDone, j + 1);
+            WS_TA(d, me, 4);
+        }
     }
     if (!FAST) { WS_TR(); flush(nInst, true); WS_TA(d, me, 3); }
     WS_EV(d, me, me == 0 ? 6 : 7);
