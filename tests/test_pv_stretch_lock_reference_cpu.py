@@ -180,8 +180,20 @@ def test_the_symbol_is_declared_and_exported_and_null_arguments_fail_without_a_d
     assert "vp_stft_stretch_lock.inc" in build.DEPS
     # the call path builds its arguments on the stack: nothing is allocated
     src = open(os.path.join(ROOT, "vocoderproject_amd", "csrc", "vp_capi.hip")).read()
-    body = src[src.index('extern "C" int ' + SYMBOL):]
-    body = body[:body.index("\n}\n")]
+    def expanded(at, seen):
+        # (the function that starts at `at`, each of the file's static functions it calls written out in front of the line that calls it,
+        # a call's arguments before the call: the text in the order it runs)
+        out = []
+        for line in src[at:src.index("\n}\n", at)].split("\n"):
+            for name in reversed(re.findall(r"\b(\w+)\(", line)):
+                m = re.search(r"^static [^\n;(]*\b%s\([^;{]*\)\n\{" % name, src, re.M)
+                if m and name not in seen:
+                    seen.add(name)
+                    out.append(expanded(m.start(), seen))
+            out.append(line)
+        return "\n".join(out)
+    body = expanded(src.index('extern "C" int ' + SYMBOL), set())
+    assert "stft_check(" in body and "vp_stft_launch_stretch_lock(" in body
     assert "hipMalloc" not in body and "new " not in body and "2048-point frames are not built" in body
     assert body.index("VP_ERR_GEOMETRY") < body.index("hipSetDevice")                   # refused before the device is touched
     from vocoderproject_amd import StftRoundTrip

@@ -1866,15 +1866,39 @@ static void stft_free(vp_stft *p)
     (void)hipFree(p->notes); (void)hipFree(p->notesN);
 }
 
+// ---- what the three creators of this file share ----
+static int select_device(int device)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VP_ERR_NO_DEVICE;
+    return hipSetDevice(device) == hipSuccess ? VP_OK : VP_ERR_NO_DEVICE;
+}
+
+// one device allocation, filled from `src` when there is one; counted in *nAllocs when the handle keeps a count
+static bool put(void **d, const void *src, size_t bytes, long *nAllocs)
+{
+    if (hipMalloc(d, bytes) != hipSuccess) return false;
+    if (nAllocs) ++*nAllocs;
+    return !src || hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+static bool put(double **d, const std::vector<double> &v, long *nAllocs) { return put((void **)d, v.data(), v.size() * 8, nAllocs); }
+
+// the pitch tracker's note tables, one per key (PluginProcessor.cpp:148: fMin 100, fMax 800), at create so that its calls allocate nothing
+static bool put_notes(double **notes, int **notesN, long *nAllocs)
+{
+    std::vector<double> tab(13 * VP_NOTES_STRIDE, 0.0);
+    int n[13];
+    for (int k = 0; k < 13; k++) n[k] = build_notes(k, VP_TRACK_FMIN, VP_TRACK_FMAX, tab.data() + (size_t)k * VP_NOTES_STRIDE);
+    return put(notes, tab, nAllocs) && put((void **)notesN, n, sizeof n, nAllocs);
+}
+
 extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int frame_len, int hop, vp_stft **out)
 {
     if (!out || n_streams <= 0 || frame_len < 8 || hop <= 0 || n_samples < frame_len) return VP_ERR_INVALID_ARG;
     // (hop == frame_len: the sqrt-Hann windows do not overlap and w[0]^2 = 0 cannot be normalised; at least two frames must cover every
     // sample.  Frame lengths other than 1024 and 2048 -- eight / sixteen complex points per lane of one wavefront -- are not built.)
     if (!vp_stft_supported(frame_len, hop)) return VP_ERR_GEOMETRY;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VP_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    if (select_device(device)) return VP_ERR_NO_DEVICE;
     vp_stft *p = new vp_stft();
     // The phase-vocoder build needs more than the default 64 KB of dynamic LDS: its ceiling is raised per handle and device
     // (hipFuncSetAttribute acts on the current device).  Only vp_stft_pitch_shift needs it, so a failure is remembered and fails
@@ -1887,15 +1911,8 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     p->nFrames = (n_samples - frame_len) / hop + 1;
     std::vector<double> w, t1, t2, ts, tt;
     p->scale = stft_host_tables(frame_len, hop, w, t1, t2, ts, tt);
-    auto up = [](double **d, const std::vector<double> &v) {
-        return hipMalloc(d, v.size() * 8) == hipSuccess && hipMemcpy(*d, v.data(), v.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!(up(&p->win, w) && up(&p->tw1, t1) && up(&p->tw2, t2) && up(&p->tws, ts) && (frame_len != 2048 || up(&p->twTop, tt)))) { stft_free(p); delete p; return VP_ERR_OOM; }
-    // the pitch tracker's note tables, one per key (PluginProcessor.cpp:148: fMin 100, fMax 800), here so that its calls allocate nothing
-    std::vector<double> notes(13 * VP_NOTES_STRIDE, 0.0);
-    int notesN[13];
-    for (int k = 0; k < 13; k++) notesN[k] = build_notes(k, VP_TRACK_FMIN, VP_TRACK_FMAX, notes.data() + (size_t)k * VP_NOTES_STRIDE);
-    if (!(up(&p->notes, notes) && hipMalloc(&p->notesN, sizeof notesN) == hipSuccess && hipMemcpy(p->notesN, notesN, sizeof notesN, hipMemcpyHostToDevice) == hipSuccess)) {
+    if (!(put(&p->win, w, nullptr) && put(&p->tw1, t1, nullptr) && put(&p->tw2, t2, nullptr) && put(&p->tws, ts, nullptr)
+          && (frame_len != 2048 || put(&p->twTop, tt, nullptr)) && put_notes(&p->notes, &p->notesN, nullptr))) {
         stft_free(p); delete p; return VP_ERR_OOM;
     }
     *out = p;
@@ -1958,17 +1975,36 @@ extern "C" int vp_stft_set_precision(vp_stft *p, int precision)
 }
 extern "C" int vp_stft_get_precision(const vp_stft *p) { return p ? (p->f32 ? VP_STFT_F32 : VP_STFT_F64) : VP_ERR_INVALID_ARG; }
 
-// (d_ratio: the phase-vocoder stage reads its ratio per frame from this table, `ratio` is unused then; d_pos: it reads frame f at input
-// sample d_pos[s][f] of rows of n_in samples -- the time stretch; lifter > 0: the ratio-curve build with the formant correction, d_formant
-// [S] or null; locked: the ratio-curve build with peak locking; d_ratio, d_pos and locked together: the locked time stretch)
-static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag, hipStream_t st, bool pv, double ratio, const double *d_ratio = nullptr,
-                      const int *d_pos = nullptr, int n_in = 0, const double *d_formant = nullptr, int lifter = 0, bool locked = false)
+// What the phase-vocoder stage of one call does, one-shot or streaming: which build runs and the tables it reads.  The named constructors
+// are the only places that fill one, and there is none for a combination that no kernel serves (a formant correction on a locked call,
+// a position table on a formant call).
+struct PvMode {
+    enum Kind { FIXED, CURVE, LOCKED, FORMANT, STRETCH, STRETCH_LOCKED } kind = FIXED;
+    double semitones = 0.0, ratio = 1.0;   // FIXED, STRETCH: the caller's interval and its ratio (a streaming call reads the ratios its records hold)
+    const double *ratioTab = nullptr;   // every other kind: one-shot [S][nFrames], streaming [n_blocks][S]
+    const int *posTab = nullptr;        // STRETCH, STRETCH_LOCKED: frame f of stream s is read at input sample posTab[s][f] ...
+    int nIn = 0;                        // ... of rows of nIn samples
+    const double *formant = nullptr;    // FORMANT: [S] formant ratios or null (1.0)
+    int lifter = 0;                     // FORMANT: the cepstral lifter's length in samples
+
+    static PvMode held() { return PvMode(); }                                     // (streaming: the intervals vp_pv_set_semitones left)
+    static PvMode fixed(double semitones) { PvMode m; m.semitones = semitones; m.ratio = std::pow(2.0, semitones / 12.0); return m; }
+    static PvMode curve(const double *tab) { PvMode m; m.kind = CURVE; m.ratioTab = tab; return m; }
+    static PvMode lock(const double *tab) { PvMode m; m.kind = LOCKED; m.ratioTab = tab; return m; }
+    static PvMode form(const double *tab, const double *formant, int lifter) { PvMode m; m.kind = FORMANT; m.ratioTab = tab; m.formant = formant; m.lifter = lifter; return m; }
+    static PvMode stretch(double semitones, const int *pos, int nIn) { PvMode m = fixed(semitones); m.kind = STRETCH; m.posTab = pos; m.nIn = nIn; return m; }
+    static PvMode stretch_lock(const double *tab, const int *pos, int nIn) { PvMode m; m.kind = STRETCH_LOCKED; m.ratioTab = tab; m.posTab = pos; m.nIn = nIn; return m; }
+    bool locked() const { return kind == LOCKED || kind == STRETCH_LOCKED; }
+};
+
+// the kernel's arguments from the handle; m null: the plain round trip, whose frames split into *nRuns runs per stream
+static VpStftArgs stft_args(const vp_stft *p, const float *d_in, float *d_out, float *d_mag, const PvMode *m, int *nRuns)
 {
     VpStftArgs a;
     memset(&a, 0, sizeof a);
     a.in = d_in; a.out = d_out; a.mag = d_mag; a.win = p->win; a.tw1 = p->tw1; a.tw2 = p->tw2; a.tws = p->tws; a.twTop = p->twTop;
-    a.pvRatio = ratio; a.pv = pv ? 1 : 0;
-    a.f32 = (p->f32 && !pv) ? 1 : 0;                           // (the phase-vocoder stage keeps double: its phases accumulate over the stream)
+    a.pvRatio = m ? m->ratio : 1.0; a.pv = m ? 1 : 0;
+    a.f32 = (p->f32 && !m) ? 1 : 0;                            // (the phase-vocoder stage keeps double: its phases accumulate over the stream)
     a.c = (double)p->scale / (double)(p->F / 2);
     a.T = p->T; a.nFrames = p->nFrames; a.F = p->F; a.hop = p->hop; a.O = p->F / p->hop;
     a.nHops = (p->T + p->hop - 1) / p->hop;
@@ -1980,63 +2016,39 @@ static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
     // runs: enough workgroups for two per CU (the kernel's register budget), but runs of at least four rounds per recomputed one;
     // the phase-vocoder stage carries a recurrence over the frames of a stream: one run
     int runs = 1;
-    if (!pv) {
+    if (!m) {
         // (four workgroups per CU in the single-precision build -- half the registers --, three at 2048 points)
         runs = p->runsPerStream > 0 ? p->runsPerStream : ((a.f32 ? (p->F == 2048 ? 3 : 4) : 2) * 256 + p->S - 1) / p->S;
         runs = std::max(1, std::min(runs, a.nRounds / (4 * a.haloRounds)));
     }
     a.roundsPerRun = (a.nRounds + runs - 1) / runs;
-    const int nRuns = (a.nRounds + a.roundsPerRun - 1) / a.roundsPerRun;
-    if (d_ratio && lifter > 0) return vp_stft_launch_formant(a, d_ratio, d_formant, lifter, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
-    if (d_ratio && d_pos && locked) return vp_stft_launch_stretch_lock(a, d_ratio, d_pos, n_in, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
-    if (d_ratio && locked) return vp_stft_launch_lock(a, d_ratio, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
-    if (d_ratio) return vp_stft_launch_curve(a, d_ratio, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
-    if (d_pos) return vp_stft_launch_stretch(a, d_pos, n_in, p->S, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
-    return vp_stft_launch(a, p->S, nRuns, st) == hipSuccess ? VP_OK : VP_ERR_HIP;
+    *nRuns = (a.nRounds + a.roundsPerRun - 1) / a.roundsPerRun;
+    return a;
 }
 
-// d_in, d_out: device float32 [S][T]; d_mag: optional device float32 [S][nFrames][F/2+1] (or NULL)
-extern "C" int vp_stft_roundtrip(vp_stft *p, const float *d_in, float *d_out, float *d_mag, void *hip_stream)
+// the one place where a mode meets its launcher (m null: the plain round trip)
+static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag, const PvMode *m, hipStream_t st)
 {
-    if (!p || !d_in || !d_out) return VP_ERR_INVALID_ARG;
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return stft_fused(p, d_in, d_out, d_mag, (hipStream_t)hip_stream, false, 1.0);
+    int nRuns;
+    const VpStftArgs a = stft_args(p, d_in, d_out, d_mag, m, &nRuns);
+    hipError_t e = hipErrorInvalidValue;
+    switch (m ? m->kind : PvMode::FIXED) {
+    case PvMode::FIXED: e = vp_stft_launch(a, p->S, nRuns, st); break;
+    case PvMode::CURVE: e = vp_stft_launch_curve(a, m->ratioTab, p->S, st); break;
+    case PvMode::LOCKED: e = vp_stft_launch_lock(a, m->ratioTab, p->S, st); break;
+    case PvMode::FORMANT: e = vp_stft_launch_formant(a, m->ratioTab, m->formant, m->lifter, p->S, st); break;
+    case PvMode::STRETCH: e = vp_stft_launch_stretch(a, m->posTab, m->nIn, p->S, st); break;
+    case PvMode::STRETCH_LOCKED: e = vp_stft_launch_stretch_lock(a, m->ratioTab, m->posTab, m->nIn, p->S, st); break;
+    }
+    return e == hipSuccess ? VP_OK : VP_ERR_HIP;
 }
 
-// the same round trip with the phase-vocoder pitch shift between the transforms (1024- and 2048-point frames: vp_stft_launch picks the build)
-extern "C" int vp_stft_pitch_shift(vp_stft *p, const float *d_in, float *d_out, double semitones, void *hip_stream)
-{
-    if (!p || !d_in || !d_out || !(semitones >= -12.0 && semitones <= 12.0)) return VP_ERR_INVALID_ARG;
-    if (!p->pvOk) return VP_ERR_HIP;                           // (its dynamic-LDS ceiling could not be raised on this device: vp_stft_create)
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, std::pow(2.0, semitones / 12.0));
-}
+static bool lifter_ok(int lifter) { return lifter >= VP_FORMANT_LIFTER_MIN && lifter <= VP_FORMANT_LIFTER_MAX; }
 
-// the pitch shift along a ratio curve: d_ratio [S][nFrames], one workgroup per stream (vp_k_stft_pv_curve / vp_k_stft_pv2k_curve)
-extern "C" int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream)
-{
-    if (!p || !d_in || !d_out || !d_ratio) return VP_ERR_INVALID_ARG;
-    if (!p->pvOk) return VP_ERR_HIP;                           // (as vp_stft_pitch_shift)
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio);
-}
-
-// the pitch shift along a ratio curve with PEAK LOCKING (vp_k_stft_pv_lock; 1024-point frames): the arguments of vp_stft_pitch_shift_curve,
-// checked before the device is touched
-extern "C" int vp_stft_pitch_shift_locked(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream)
-{
-    if (!p) return VP_ERR_INVALID_ARG;
-    if (!d_in || !d_out || !d_ratio) { p->lastError = "locked: null input, output or ratio table"; return VP_ERR_INVALID_ARG; }
-    if (p->F != 1024) { p->lastError = "locked: 2048-point frames are not built (the peak-locked stage exists for 1024-point frames only)"; return VP_ERR_GEOMETRY; }
-    if (!p->pvOk) { p->lastError = "locked: the device refused the phase-vocoder kernels' LDS size at create"; return VP_ERR_HIP; }   // (as vp_stft_pitch_shift)
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio, nullptr, 0, nullptr, 0, true);
-}
-
-// every argument of a formant call that the curve call does not have, checked before the device is touched
+// every argument of a formant call that the curve call does not have
 static int formant_check(vp_stft *p, int lifter)
 {
-    if (lifter < VP_FORMANT_LIFTER_MIN || lifter > VP_FORMANT_LIFTER_MAX) { p->lastError = "formant: lifter outside 4 .. 64 samples"; return VP_ERR_INVALID_ARG; }
+    if (!lifter_ok(lifter)) { p->lastError = "formant: lifter outside 4 .. 64 samples"; return VP_ERR_INVALID_ARG; }
     if (p->F != 1024) {
         p->lastError = "formant: 2048-point frames are not built (the envelope needs a wavefront's exchange buffer to hold the frame's 1025 bins; it holds 1024 doubles)";
         return VP_ERR_GEOMETRY;
@@ -2044,41 +2056,85 @@ static int formant_check(vp_stft *p, int lifter)
     return VP_OK;
 }
 
+// Every argument of a one-shot call, checked before the device is touched, in the order a caller can observe: handle, pointers, row
+// length, interval, lifter, frame length, the device's verdict at create.  who: the entry's name in the text vp_stft_last_error gets, or
+// null for the entries that have never kept one (vp_stft_roundtrip, _pitch_shift, _pitch_shift_curve, vp_stft_time_stretch); ptrs: every
+// pointer the entry requires is there, `what` names them; the mode's interval (of the entries that take one: they keep no text) is
+// tested so that a NaN fails; m null: the plain round trip
+static int stft_check(vp_stft *p, const char *who, bool ptrs, const char *what, const PvMode *m)
+{
+    if (!p) return VP_ERR_INVALID_ARG;
+    const auto fail = [&](int rc, const char *text) { if (who) p->lastError = std::string(who) + ": " + text; return rc; };
+    if (!ptrs) return fail(VP_ERR_INVALID_ARG, what);
+    if (!m) return VP_OK;
+    if (m->posTab && m->nIn < p->F) return fail(VP_ERR_INVALID_ARG, "the input row is shorter than one frame");
+    if (!(m->semitones >= -12.0 && m->semitones <= 12.0)) return VP_ERR_INVALID_ARG;
+    if (m->kind == PvMode::FORMANT) { const int rc = formant_check(p, m->lifter); if (rc) return rc; }
+    if (m->locked() && p->F != 1024) return fail(VP_ERR_GEOMETRY, "2048-point frames are not built (the peak-locked stage exists for 1024-point frames only)");
+    // (the builds' dynamic-LDS ceiling could not be raised on this device: vp_stft_create)
+    if (!p->pvOk) return fail(VP_ERR_HIP, "the device refused the phase-vocoder kernels' LDS size at create");
+    return VP_OK;
+}
+
+// a checked call: the handle's device, then the launch
+static int stft_call(vp_stft *p, int rc, const float *d_in, float *d_out, float *d_mag, const PvMode *m, void *hip_stream)
+{
+    if (rc) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return stft_fused(p, d_in, d_out, d_mag, m, (hipStream_t)hip_stream);
+}
+
+// d_in, d_out: device float32 [S][T]; d_mag: optional device float32 [S][nFrames][F/2+1] (or NULL)
+extern "C" int vp_stft_roundtrip(vp_stft *p, const float *d_in, float *d_out, float *d_mag, void *hip_stream)
+{
+    return stft_call(p, stft_check(p, nullptr, d_in && d_out, nullptr, nullptr), d_in, d_out, d_mag, nullptr, hip_stream);
+}
+
+// the same round trip with the phase-vocoder pitch shift between the transforms (1024- and 2048-point frames: vp_stft_launch picks the build)
+extern "C" int vp_stft_pitch_shift(vp_stft *p, const float *d_in, float *d_out, double semitones, void *hip_stream)
+{
+    const PvMode m = PvMode::fixed(semitones);
+    return stft_call(p, stft_check(p, nullptr, d_in && d_out, nullptr, &m), d_in, d_out, nullptr, &m, hip_stream);
+}
+
+// the pitch shift along a ratio curve: d_ratio [S][nFrames], one workgroup per stream (vp_k_stft_pv_curve / vp_k_stft_pv2k_curve)
+extern "C" int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream)
+{
+    const PvMode m = PvMode::curve(d_ratio);
+    return stft_call(p, stft_check(p, nullptr, d_in && d_out && d_ratio, nullptr, &m), d_in, d_out, nullptr, &m, hip_stream);
+}
+
+// the pitch shift along a ratio curve with PEAK LOCKING (vp_k_stft_pv_lock; 1024-point frames): the arguments of vp_stft_pitch_shift_curve
+extern "C" int vp_stft_pitch_shift_locked(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream)
+{
+    const PvMode m = PvMode::lock(d_ratio);
+    return stft_call(p, stft_check(p, "locked", d_in && d_out && d_ratio, "null input, output or ratio table", &m), d_in, d_out, nullptr, &m, hip_stream);
+}
+
 // vp_stft_pitch_shift_curve with the cepstral formant correction: d_formant [S] formant ratios or NULL (1.0: the envelope stays where it
 // was), lifter the cepstral lifter's length in samples (vp_k_stft_pv_formant; 1024-point frames)
 extern "C" int vp_stft_pitch_shift_formant(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, const double *d_formant, int lifter,
                                            void *hip_stream)
 {
-    if (!p) return VP_ERR_INVALID_ARG;
-    if (!d_in || !d_out || !d_ratio) { p->lastError = "formant: null input, output or ratio table"; return VP_ERR_INVALID_ARG; }
-    const int rc = formant_check(p, lifter);
-    if (rc) return rc;
-    if (!p->pvOk) { p->lastError = "formant: the device refused the phase-vocoder kernels' LDS size at create"; return VP_ERR_HIP; }   // (as vp_stft_pitch_shift)
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio, nullptr, 0, d_formant, lifter);
+    const PvMode m = PvMode::form(d_ratio, d_formant, lifter);
+    return stft_call(p, stft_check(p, "formant", d_in && d_out && d_ratio, "null input, output or ratio table", &m), d_in, d_out, nullptr, &m, hip_stream);
 }
 
 // the time stretch: frame f of stream s is read at input sample d_pos[s][f] (clamped by the kernel) of d_in [S][n_in] and written at output
 // sample f hop of d_out [S][T] (vp_k_stft_pv_stretch / vp_k_stft_pv2k_stretch), with the pitch shift of `semitones` on top
 extern "C" int vp_stft_time_stretch(vp_stft *p, const float *d_in, int n_in, const int *d_pos, float *d_out, double semitones, void *hip_stream)
 {
-    if (!p || !d_in || !d_pos || !d_out || n_in < p->F || !(semitones >= -12.0 && semitones <= 12.0)) return VP_ERR_INVALID_ARG;
-    if (!p->pvOk) return VP_ERR_HIP;                           // (as vp_stft_pitch_shift)
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, std::pow(2.0, semitones / 12.0), nullptr, d_pos, n_in);
+    const PvMode m = PvMode::stretch(semitones, d_pos, n_in);
+    return stft_call(p, stft_check(p, nullptr, d_in && d_pos && d_out, nullptr, &m), d_in, d_out, nullptr, &m, hip_stream);
 }
 
 // the time stretch with PEAK LOCKING (vp_k_stft_pv_stretch_lock; 1024-point frames): vp_stft_time_stretch's input, table and output with
-// vp_stft_pitch_shift_locked's ratio table, checked before the device is touched
+// vp_stft_pitch_shift_locked's ratio table
 extern "C" int vp_stft_time_stretch_locked(vp_stft *p, const float *d_in, int n_in, const int *d_pos, float *d_out, const double *d_ratio, void *hip_stream)
 {
-    if (!p) return VP_ERR_INVALID_ARG;
-    if (!d_in || !d_pos || !d_out || !d_ratio) { p->lastError = "stretch locked: null input, position table, output or ratio table"; return VP_ERR_INVALID_ARG; }
-    if (n_in < p->F) { p->lastError = "stretch locked: the input row is shorter than one frame"; return VP_ERR_INVALID_ARG; }
-    if (p->F != 1024) { p->lastError = "stretch locked: 2048-point frames are not built (the peak-locked stage exists for 1024-point frames only)"; return VP_ERR_GEOMETRY; }
-    if (!p->pvOk) { p->lastError = "stretch locked: the device refused the phase-vocoder kernels' LDS size at create"; return VP_ERR_HIP; }   // (as vp_stft_pitch_shift)
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio, d_pos, n_in, nullptr, 0, true);
+    const PvMode m = PvMode::stretch_lock(d_ratio, d_pos, n_in);
+    return stft_call(p, stft_check(p, "stretch locked", d_in && d_pos && d_out && d_ratio, "null input, position table, output or ratio table", &m),
+                     d_in, d_out, nullptr, &m, hip_stream);
 }
 
 extern "C" int vp_stretch_positions(int *pos, int n_frames, int hop, double stretch, int n_in, int frame_len)
@@ -2141,34 +2197,32 @@ extern "C" int vp_stft_track_pitch(vp_stft *p, const float *d_in, double sample_
     return track_launch(p, d_in, sample_rate, d_key, d_period, d_ratio, (hipStream_t)hip_stream);
 }
 
-// the tracker, then vp_stft_pitch_shift_curve along its table, on the same stream
+// the tracker, then the call of mode m (whose table is the tracker's d_ratio) along its table, on the same stream.  The output and the
+// table are looked at first, when there is a handle to keep the text; then the tracker's arguments, then the mode's
+static int stft_autotune(vp_stft *p, const float *d_in, float *d_out, double fs, const int *d_key, int *d_period, double *d_ratio, const PvMode &m,
+                         void *hip_stream)
+{
+    if (p && (!d_out || !d_ratio)) { p->lastError = "autotune: null output or ratio table (the table is result and scratch)"; return VP_ERR_INVALID_ARG; }
+    int rc = track_check(p, d_in, fs, d_period, d_ratio);
+    if (!rc) rc = stft_check(p, "autotune", true, nullptr, &m);
+    if (rc) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    rc = track_launch(p, d_in, fs, d_key, d_period, d_ratio, (hipStream_t)hip_stream);
+    return rc ? rc : stft_fused(p, d_in, d_out, nullptr, &m, (hipStream_t)hip_stream);
+}
+
+// the tracker, then vp_stft_pitch_shift_curve along its table
 extern "C" int vp_stft_autotune(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int *d_period, double *d_ratio,
                                 void *hip_stream)
 {
-    if (p && (!d_out || !d_ratio)) { p->lastError = "autotune: null output or ratio table (the table is result and scratch)"; return VP_ERR_INVALID_ARG; }
-    int rc = track_check(p, d_in, sample_rate, d_period, d_ratio);
-    if (rc) return rc;
-    if (!p->pvOk) { p->lastError = "autotune: the device refused the phase-vocoder kernels' LDS size at create"; return VP_ERR_HIP; }   // (as vp_stft_pitch_shift)
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    rc = track_launch(p, d_in, sample_rate, d_key, d_period, d_ratio, (hipStream_t)hip_stream);
-    if (rc) return rc;
-    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio);
+    return stft_autotune(p, d_in, d_out, sample_rate, d_key, d_period, d_ratio, PvMode::curve(d_ratio), hip_stream);
 }
 
-// the tracker, then vp_stft_pitch_shift_formant along its table, on the same stream
+// the tracker, then vp_stft_pitch_shift_formant along its table
 extern "C" int vp_stft_autotune_formant(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int *d_period, double *d_ratio,
                                         const double *d_formant, int lifter, void *hip_stream)
 {
-    if (p && (!d_out || !d_ratio)) { p->lastError = "autotune: null output or ratio table (the table is result and scratch)"; return VP_ERR_INVALID_ARG; }
-    int rc = track_check(p, d_in, sample_rate, d_period, d_ratio);
-    if (rc) return rc;
-    rc = formant_check(p, lifter);
-    if (rc) return rc;
-    if (!p->pvOk) { p->lastError = "autotune: the device refused the phase-vocoder kernels' LDS size at create"; return VP_ERR_HIP; }   // (as vp_stft_pitch_shift)
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    rc = track_launch(p, d_in, sample_rate, d_key, d_period, d_ratio, (hipStream_t)hip_stream);
-    if (rc) return rc;
-    return stft_fused(p, d_in, d_out, nullptr, (hipStream_t)hip_stream, true, 1.0, d_ratio, nullptr, 0, d_formant, lifter);
+    return stft_autotune(p, d_in, d_out, sample_rate, d_key, d_period, d_ratio, PvMode::form(d_ratio, d_formant, lifter), hip_stream);
 }
 
 // ---- streaming phase vocoder (no reference counterpart): vp_k_pv_stream of vp_stft.hip, the one-shot stage block by block -----------
@@ -2201,9 +2255,7 @@ extern "C" int vp_pv_create(int device, int n_streams, int block_size, int frame
     if (!out || n_streams <= 0 || block_size <= 0 || frame_len <= 0 || hop <= 0) return VP_ERR_INVALID_ARG;
     if ((long long)n_streams * block_size > (1LL << 28) || (long long)block_size > (1 << 24)) return VP_ERR_INVALID_ARG;
     if (frame_len != 1024 || !vp_stft_supported(frame_len, hop)) return VP_ERR_GEOMETRY;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VP_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    if (select_device(device)) return VP_ERR_NO_DEVICE;
     if (vp_pv_prepare_device() != hipSuccess || vp_pv_curve_prepare_device() != hipSuccess || vp_pv_formant_prepare_device() != hipSuccess
         || vp_pv_lock_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
     vp_pv *p = new vp_pv();
@@ -2218,17 +2270,13 @@ extern "C" int vp_pv_create(int device, int n_streams, int block_size, int frame
     p->ratioPend.assign(n_streams, 0.0);
     p->resetPend.assign(n_streams, 0);
     p->upd.reserve(n_streams + 1);
-    auto al = [p](void **d, size_t bytes) { if (hipMalloc(d, bytes) != hipSuccess) return false; p->nAllocs++; return true; };
-    auto up = [&](double **d, const std::vector<double> &v) {
-        return al((void **)d, v.size() * 8) && hipMemcpy(*d, v.data(), v.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
-    };
     // every stream starts with zero phases, history and carry, ratio 1
     std::vector<unsigned char> rec((size_t)n_streams * VP_PV_REC_BYTES, 0);
     for (int s = 0; s < n_streams; s++) { const double one = 1.0; memcpy(&rec[(size_t)s * VP_PV_REC_BYTES + VP_PV_RATIO * 8], &one, 8); }
     const size_t blk = (size_t)n_streams * block_size * sizeof(float);
-    const bool ok = up(&p->win, w) && up(&p->tw1, t1) && up(&p->tw2, t2) && up(&p->tws, ts)
-        && al((void **)&p->state, rec.size()) && hipMemcpy(p->state, rec.data(), rec.size(), hipMemcpyHostToDevice) == hipSuccess
-        && al((void **)&p->stageIn, blk) && al((void **)&p->stageOut, blk)
+    long *n = &p->nAllocs;
+    const bool ok = put(&p->win, w, n) && put(&p->tw1, t1, n) && put(&p->tw2, t2, n) && put(&p->tws, ts, n)
+        && put((void **)&p->state, rec.data(), rec.size(), n) && put((void **)&p->stageIn, nullptr, blk, n) && put((void **)&p->stageOut, nullptr, blk, n)
         && hipStreamCreateWithFlags(&p->ownStream, hipStreamNonBlocking) == hipSuccess;
     if (!ok) { pv_free(p); delete p; (void)hipGetLastError(); return VP_ERR_OOM; }
     *out = p;
@@ -2282,10 +2330,9 @@ extern "C" int vp_pv_reset(vp_pv *p, int stream)
 
 // the pending changes travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update launches in front of it): ordered on
 // the caller's stream, no host memory the device reads later, no allocation
-// (d_ratio: one ratio per block and stream for this call, [n_blocks][S]; the pending changes travel and are stored as in any call;
-// lifter > 0: the curve call with the formant correction, d_formant [S] or null; locked: the curve call with peak locking)
-static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipStream_t st, const double *d_ratio = nullptr, const double *d_formant = nullptr,
-                  int lifter = 0, bool locked = false)
+// (m: this call's mode -- a table holds one ratio per block and stream, [n_blocks][S]; the pending changes travel and are stored as in
+// any call.  The stream has no position table: the stretch modes do not exist here)
+static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipStream_t st, const PvMode &m)
 {
     p->upd.clear();
     if (p->allRatio > 0.0 || p->allReset) p->upd.push_back(VpPvUpdate{-1, p->allReset ? 1 : 0, p->allRatio});
@@ -2304,45 +2351,51 @@ static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipSt
     }
     a.in = d_in; a.out = d_out; a.nBlocks = n_blocks; a.nUpd = (int)(p->upd.size() - i);
     for (int k = 0; k < a.nUpd; k++) a.upd[k] = p->upd[i + k];
-    if ((d_ratio && locked ? vp_pv_launch_lock(a, d_ratio, st) : d_ratio && lifter > 0 ? vp_pv_launch_formant(a, d_ratio, d_formant, lifter, st)
-         : d_ratio ? vp_pv_launch_curve(a, d_ratio, st) : vp_pv_launch(a, st)) != hipSuccess)
-        return VP_ERR_HIP;
+    hipError_t e = hipErrorInvalidValue;
+    switch (m.kind) {
+    case PvMode::FIXED: e = vp_pv_launch(a, st); break;
+    case PvMode::CURVE: e = vp_pv_launch_curve(a, m.ratioTab, st); break;
+    case PvMode::LOCKED: e = vp_pv_launch_lock(a, m.ratioTab, st); break;
+    case PvMode::FORMANT: e = vp_pv_launch_formant(a, m.ratioTab, m.formant, m.lifter, st); break;
+    case PvMode::STRETCH: case PvMode::STRETCH_LOCKED: return VP_ERR_INVALID_ARG;          // (no entry makes one: the stream has no time stretch)
+    }
+    if (e != hipSuccess) return VP_ERR_HIP;
     p->allRatio = 0.0; p->allReset = false;
     std::fill(p->ratioPend.begin(), p->ratioPend.end(), 0.0);
     std::fill(p->resetPend.begin(), p->resetPend.end(), 0);
     return VP_OK;
 }
 
+// every argument of a streaming call, then the handle's device, then the call.  ptrs: every table the mode requires is there
+static int pv_call(vp_pv *p, const float *d_in, float *d_out, bool ptrs, int n_blocks, const PvMode &m, void *hip_stream)
+{
+    if (!p || !d_in || !d_out || !ptrs || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
+    if (m.kind == PvMode::FORMANT && !lifter_ok(m.lifter)) return VP_ERR_INVALID_ARG;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, m);
+}
+
 extern "C" int vp_pv_process_blocks_device(vp_pv *p, const float *d_in, float *d_out, int n_blocks, void *hip_stream)
 {
-    if (!p || !d_in || !d_out || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream);
+    return pv_call(p, d_in, d_out, true, n_blocks, PvMode::held(), hip_stream);
 }
 
 extern "C" int vp_pv_process_blocks_curve_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream)
 {
-    if (!p || !d_in || !d_out || !d_ratio || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio);
+    return pv_call(p, d_in, d_out, d_ratio != nullptr, n_blocks, PvMode::curve(d_ratio), hip_stream);
 }
 
 // the curve call with peak locking (vp_k_pv_stream_lock): the record's two arrays hold the previous frame's phases and theta
 extern "C" int vp_pv_process_blocks_locked_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream)
 {
-    if (!p || !d_in || !d_out || !d_ratio || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio, nullptr, 0, true);
+    return pv_call(p, d_in, d_out, d_ratio != nullptr, n_blocks, PvMode::lock(d_ratio), hip_stream);
 }
 
 // the curve call with the cepstral formant correction (vp_k_pv_stream_formant): d_formant [S] or NULL (1.0), lifter in samples
 extern "C" int vp_pv_process_blocks_formant_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, const double *d_formant, int lifter,
                                                    int n_blocks, void *hip_stream)
 {
-    if (!p || !d_in || !d_out || !d_ratio || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
-    if (lifter < VP_FORMANT_LIFTER_MIN || lifter > VP_FORMANT_LIFTER_MAX) return VP_ERR_INVALID_ARG;
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio, d_formant, lifter);
+    return pv_call(p, d_in, d_out, d_ratio != nullptr, n_blocks, PvMode::form(d_ratio, d_formant, lifter), hip_stream);
 }
 
 extern "C" int vp_pv_process_block(vp_pv *p, const float *in, float *out)
@@ -2351,7 +2404,7 @@ extern "C" int vp_pv_process_block(vp_pv *p, const float *in, float *out)
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     const size_t bytes = (size_t)p->S * p->N * sizeof(float);
     if (hipMemcpyAsync(p->stageIn, in, bytes, hipMemcpyHostToDevice, p->ownStream) != hipSuccess) return VP_ERR_HIP;
-    const int rc = pv_run(p, p->stageIn, p->stageOut, 1, p->ownStream);
+    const int rc = pv_run(p, p->stageIn, p->stageOut, 1, p->ownStream, PvMode::held());
     if (rc) return rc;
     if (hipMemcpyAsync(out, p->stageOut, bytes, hipMemcpyDeviceToHost, p->ownStream) != hipSuccess) return VP_ERR_HIP;
     return hipStreamSynchronize(p->ownStream) == hipSuccess ? VP_OK : VP_ERR_HIP;
@@ -2385,9 +2438,7 @@ extern "C" int vp_pv_tracker_create(int device, int n_streams, int block_size, i
     const int tauMax = vp_track_tau_max(sample_rate);
     if (tauMax < 0) return VP_ERR_INVALID_ARG;
     if (frame_len != 1024 && frame_len != 2048) return VP_ERR_GEOMETRY;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VP_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    if (select_device(device)) return VP_ERR_NO_DEVICE;
     vp_pv_tracker *t = new vp_pv_tracker();
     t->device = device; t->S = n_streams; t->N = block_size; t->F = frame_len; t->fs = sample_rate;
     t->tauMax = tauMax; t->W = frame_len + tauMax;
@@ -2397,14 +2448,9 @@ extern "C" int vp_pv_tracker_create(int device, int n_streams, int block_size, i
     const size_t ringBytes = (S * t->W * sizeof(float) + 7) & ~(size_t)7;
     std::vector<unsigned char> st(ringBytes + S * (8 + 8 + 8 + 4), 0);                          // count 0, age 0, ring zeros (never read before written)
     for (size_t s = 0; s < 2 * S; s++) { const double one = 1.0; memcpy(&st[ringBytes + S * 8 + s * 8], &one, 8); }   // tgt = cur = 1.0
-    std::vector<double> notes(13 * VP_NOTES_STRIDE, 0.0);
-    int notesN[13];
-    for (int k = 0; k < 13; k++) notesN[k] = build_notes(k, VP_TRACK_FMIN, VP_TRACK_FMAX, notes.data() + (size_t)k * VP_NOTES_STRIDE);
-    auto al = [t](void **d, size_t bytes) { if (hipMalloc(d, bytes) != hipSuccess) return false; t->nAllocs++; return true; };
-    const bool ok = al((void **)&t->state, st.size()) && hipMemcpy(t->state, st.data(), st.size(), hipMemcpyHostToDevice) == hipSuccess
-        && al((void **)&t->scrPeriod, TRKS_SCRATCH_BLOCKS * S * sizeof(int)) && al((void **)&t->scrRatio, TRKS_SCRATCH_BLOCKS * S * sizeof(double))
-        && al((void **)&t->notes, notes.size() * 8) && hipMemcpy(t->notes, notes.data(), notes.size() * 8, hipMemcpyHostToDevice) == hipSuccess
-        && al((void **)&t->notesN, sizeof notesN) && hipMemcpy(t->notesN, notesN, sizeof notesN, hipMemcpyHostToDevice) == hipSuccess;
+    long *n = &t->nAllocs;
+    const bool ok = put((void **)&t->state, st.data(), st.size(), n) && put((void **)&t->scrPeriod, nullptr, TRKS_SCRATCH_BLOCKS * S * sizeof(int), n)
+        && put((void **)&t->scrRatio, nullptr, TRKS_SCRATCH_BLOCKS * S * sizeof(double), n) && put_notes(&t->notes, &t->notesN, n);
     if (!ok) { trks_free(t); delete t; (void)hipGetLastError(); return VP_ERR_OOM; }
     t->ring = (float *)t->state;
     t->count = (long long *)(t->state + ringBytes);
@@ -2502,30 +2548,30 @@ extern "C" int vp_pv_tracker_process_blocks_device(vp_pv_tracker *t, const float
     return trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
 }
 
-// the tracker call, then vp_pv_process_blocks_curve_device along its table, on the same stream
+// the tracker call, then the streaming call of mode m (whose table is the tracker's d_ratio) along its table, on the same stream.  The
+// shifter's handle, output, table and lifter are looked at first, then the tracker's arguments, then whether the two handles match
+static int pv_autotune(vp_pv *p, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, int *d_period, double *d_ratio, int n_blocks,
+                       const PvMode &m, void *hip_stream)
+{
+    if (!p || !d_out || !d_ratio || (m.kind == PvMode::FORMANT && !lifter_ok(m.lifter))) return VP_ERR_INVALID_ARG;
+    int rc = trks_check(t, d_in, d_period, d_ratio, n_blocks);
+    if (rc) return rc;
+    if (p->S != t->S || p->N != t->N || p->device != t->device) return VP_ERR_GEOMETRY;
+    if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
+    return rc ? rc : pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, m);
+}
+
+// the tracker call, then vp_pv_process_blocks_curve_device along its table
 extern "C" int vp_pv_autotune_blocks_device(vp_pv *p, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, int *d_period, double *d_ratio,
                                             int n_blocks, void *hip_stream)
 {
-    if (!p || !d_out || !d_ratio) return VP_ERR_INVALID_ARG;
-    int rc = trks_check(t, d_in, d_period, d_ratio, n_blocks);
-    if (rc) return rc;
-    if (p->S != t->S || p->N != t->N || p->device != t->device) return VP_ERR_GEOMETRY;
-    if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
-    if (rc) return rc;
-    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio);
+    return pv_autotune(p, t, d_in, d_out, d_key, d_period, d_ratio, n_blocks, PvMode::curve(d_ratio), hip_stream);
 }
 
-// the tracker call, then vp_pv_process_blocks_formant_device along its table, on the same stream
+// the tracker call, then vp_pv_process_blocks_formant_device along its table
 extern "C" int vp_pv_autotune_blocks_formant_device(vp_pv *p, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, int *d_period,
                                                     double *d_ratio, const double *d_formant, int lifter, int n_blocks, void *hip_stream)
 {
-    if (!p || !d_out || !d_ratio || lifter < VP_FORMANT_LIFTER_MIN || lifter > VP_FORMANT_LIFTER_MAX) return VP_ERR_INVALID_ARG;
-    int rc = trks_check(t, d_in, d_period, d_ratio, n_blocks);
-    if (rc) return rc;
-    if (p->S != t->S || p->N != t->N || p->device != t->device) return VP_ERR_GEOMETRY;
-    if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
-    if (rc) return rc;
-    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, d_ratio, d_formant, lifter);
+    return pv_autotune(p, t, d_in, d_out, d_key, d_period, d_ratio, n_blocks, PvMode::form(d_ratio, d_formant, lifter), hip_stream);
 }

@@ -171,34 +171,93 @@ def vocode(voices, carriers, fs, order_lpc=40, order_synth=5, **kw):
     return render(voices, carriers, fs, pitch=False, vocoder=True, params=params, **kw)
 
 
-def pv_shift(voices, shift, N=1024, hop=256, device=0, processor=None):
-    """A batch of recordings through the streaming phase vocoder (PhaseVocoderStream: one stream per recording), block by block,
-    its latency taken off the front.  shift: one interval in semitones or one per recording.  Returns float32 [2][len] per
-    recording (the shifted signal on both channels: the layout the pitch flow writes).  `processor` (tests): an object with the
-    PhaseVocoderStream interface (set_semitones, latency, process) to use instead of a new one."""
-    S = len(voices)
-    if S == 0:
+# ---- the phase-vocoder flows: validate, size, pack, call, unpack ------------------------------------------------------------------
+
+def _batch_size(voices):
+    if len(voices) == 0:
         raise ValueError("no recordings")
-    p = processor
-    if p is None:
-        from . import PhaseVocoderStream
-        p = PhaseVocoderStream(S, int(N), hop=int(hop), device=device)
-    per = list(shift) if isinstance(shift, (list, tuple)) else [shift] * S
+    return len(voices)
+
+
+def _per_recording(value, S, name, conv=float, lo=None, hi=None, range_msg=None):
+    """One value or one per recording (list, tuple or array) -> a list of S values through `conv`, each within [lo, hi] (a NaN is
+    outside) where a range is given."""
+    many = isinstance(value, (list, tuple)) or (isinstance(value, np.ndarray) and value.ndim > 0)
+    per = [conv(v) for v in value] if many else [conv(value)] * S
     if len(per) != S:
-        raise ValueError("shift: one value per recording expected")
-    for s, v in enumerate(per):
-        p.set_semitones(float(v), stream=s)
-    lat = int(p.latency)
-    lens = [int(np.asarray(v).shape[-1]) for v in voices]
-    T = -(-(max(lens) + lat) // N) * N
-    x = np.zeros((S, T), np.float32)
+        raise ValueError(f"{name}: one value per recording expected")
+    if range_msg is not None and not all(lo <= v <= hi for v in per):
+        raise ValueError(range_msg)
+    return per
+
+
+def _lengths(voices):
+    return [int(np.asarray(v).shape[-1]) for v in voices]
+
+
+def _pack_mono(voices, lens, T):
+    """Mono recordings of lengths `lens` -> one zeroed float32 [S][T] with each recording at the front of its row."""
+    x = np.zeros((len(voices), int(T)), np.float32)
     for s, v in enumerate(voices):
         v = np.asarray(v, np.float32)
         if v.ndim != 1:
             raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
         x[s, :lens[s]] = v
+    return x
+
+
+def _both_channels(y, lens, offset=0):
+    """[S][T] -> float32 [2][len_s] per recording from sample `offset` on: the signal on both channels, the layout the pitch flow writes."""
+    return [np.ascontiguousarray(np.stack([y[s, offset:offset + n]] * 2)) for s, n in enumerate(lens)]
+
+
+def _check_formant(formant, lifter):
+    if formant is not None and not -12.0 <= float(formant) <= 12.0:
+        raise ValueError("formant: an interval within +-12 semitones expected")
+    if formant is not None and not 4 <= int(lifter) <= 64:
+        raise ValueError("lifter: 4 to 64 samples expected")
+
+
+def _check_locked(locked, formant, F=1024):
+    if locked and formant is not None:
+        raise ValueError("--locked and --formant exclude each other: formant correction on top of peak locking is not built")
+    if locked and int(F) != 1024:
+        raise ValueError("--locked: 1024-point frames expected (the peak-locked kernels are not built for 2048)")
+
+
+def _mode_kw(formant, lifter, locked, formant_name="formant"):
+    """What a call receives beyond the plain call's arguments: nothing, the formant pair, locked=True."""
+    kw = {} if formant is None else {formant_name: float(formant), "lifter": int(lifter)}
+    if locked:
+        kw["locked"] = True
+    return kw
+
+
+SHIFT_RANGE = (-12.0, 12.0, "shift: intervals within +-12 semitones expected")
+
+
+def _stream(processor, S, N, hop, device):
+    if processor is not None:
+        return processor
+    from . import PhaseVocoderStream
+    return PhaseVocoderStream(S, int(N), hop=int(hop), device=device)
+
+
+def pv_shift(voices, shift, N=1024, hop=256, device=0, processor=None):
+    """A batch of recordings through the streaming phase vocoder (PhaseVocoderStream: one stream per recording), block by block,
+    its latency taken off the front.  shift: one interval in semitones or one per recording.  Returns float32 [2][len] per
+    recording (the shifted signal on both channels: the layout the pitch flow writes).  `processor` (tests): an object with the
+    PhaseVocoderStream interface (set_semitones, latency, process) to use instead of a new one."""
+    S = _batch_size(voices)
+    p = _stream(processor, S, N, hop, device)
+    for s, v in enumerate(_per_recording(shift, S, "shift")):
+        p.set_semitones(v, stream=s)
+    lat = int(p.latency)
+    lens = _lengths(voices)
+    T = -(-(max(lens) + lat) // N) * N
+    x = _pack_mono(voices, lens, T)
     y = np.concatenate([p.process(np.ascontiguousarray(x[:, b:b + N])) for b in range(0, T, N)], axis=1)
-    return [np.ascontiguousarray(np.stack([y[s, lat:lat + lens[s]]] * 2)) for s in range(S)]
+    return _both_channels(y, lens, lat)
 
 
 def glide_curve(lens, start, end, N, n_blocks):
@@ -220,72 +279,47 @@ def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, 
     formant-preserving call instead -- the spectral envelope moves by `formant` semitones (0: it stays) whatever the pitch does, with a
     cepstral lifter of `lifter` samples; run then also receives formant_semitones and lifter.  locked: the peak-locked call instead
     (run then also receives locked=True); not together with formant."""
-    S = len(voices)
-    if S == 0:
-        raise ValueError("no recordings")
+    S = _batch_size(voices)
     if not (-12.0 <= float(start) <= 12.0 and -12.0 <= float(end) <= 12.0):
         raise ValueError("glide: intervals within +-12 semitones expected")
     _check_formant(formant, lifter)
     _check_locked(locked, formant)
-    p = processor
-    if p is None:
-        from . import PhaseVocoderStream
-        p = PhaseVocoderStream(S, int(N), hop=int(hop), device=device)
-    lens = [int(np.asarray(v).shape[-1]) for v in voices]
-    T = max(lens)
-    x = np.zeros((S, T), np.float32)
-    for s, v in enumerate(voices):
-        v = np.asarray(v, np.float32)
-        if v.ndim != 1:
-            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
-        x[s, :lens[s]] = v
-    curve = glide_curve(lens, start, end, N, -(-(T + int(p.latency)) // int(N)))
-    kw = {} if formant is None else dict(formant_semitones=float(formant), lifter=int(lifter))
-    if locked:
-        kw["locked"] = True
-    y = p.run(x, blocks_per_call=int(blocks_per_call), curve=curve, **kw)     # aligned with the input: the latency is off
-    return [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
-
-
-def _check_locked(locked, formant, F=1024):
-    if locked and formant is not None:
-        raise ValueError("--locked and --formant exclude each other: formant correction on top of peak locking is not built")
-    if locked and int(F) != 1024:
-        raise ValueError("--locked: 1024-point frames expected (the peak-locked kernels are not built for 2048)")
+    p = _stream(processor, S, N, hop, device)
+    lens = _lengths(voices)
+    x = _pack_mono(voices, lens, max(lens))
+    curve = glide_curve(lens, start, end, N, -(-(max(lens) + int(p.latency)) // int(N)))
+    # (run's output is aligned with its input: the latency is off)
+    y = p.run(x, blocks_per_call=int(blocks_per_call), curve=curve, **_mode_kw(formant, lifter, locked, "formant_semitones"))
+    return _both_channels(y, lens)
 
 
 def pv_shift_locked(voices, shift, N=1024, hop=256, device=0, blocks_per_call=16, processor=None):
     """pv_shift through the PEAK-LOCKED call: every recording by its own fixed interval (one value or one per recording), streamed block
     by block through PhaseVocoderStream.run(curve=..., locked=True) -- a constant curve.  Returns float32 [2][len] per recording.
     `processor` (tests): an object with latency and run(x, blocks_per_call, curve, locked) to use instead of a new PhaseVocoderStream."""
-    S = len(voices)
-    if S == 0:
-        raise ValueError("no recordings")
-    per = [float(v) for v in shift] if isinstance(shift, (list, tuple, np.ndarray)) else [float(shift)] * S
-    if len(per) != S:
-        raise ValueError("shift: one value per recording expected")
-    if not all(-12.0 <= v <= 12.0 for v in per):
-        raise ValueError("shift: intervals within +-12 semitones expected")
-    p = processor
-    if p is None:
-        from . import PhaseVocoderStream
-        p = PhaseVocoderStream(S, int(N), hop=int(hop), device=device)
-    lens = [int(np.asarray(v).shape[-1]) for v in voices]
-    x = np.zeros((S, max(lens)), np.float32)
-    for s, v in enumerate(voices):
-        v = np.asarray(v, np.float32)
-        if v.ndim != 1:
-            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
-        x[s, :lens[s]] = v
-    y = p.run(x, blocks_per_call=int(blocks_per_call), curve=np.array([per]), locked=True)
-    return [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
+    S = _batch_size(voices)
+    per = _per_recording(shift, S, "shift", float, *SHIFT_RANGE)
+    p = _stream(processor, S, N, hop, device)
+    lens = _lengths(voices)
+    y = p.run(_pack_mono(voices, lens, max(lens)), blocks_per_call=int(blocks_per_call), curve=np.array([per]), locked=True)
+    return _both_channels(y, lens)
 
 
-def _check_formant(formant, lifter):
-    if formant is not None and not -12.0 <= float(formant) <= 12.0:
-        raise ValueError("formant: an interval within +-12 semitones expected")
-    if formant is not None and not 4 <= int(lifter) <= 64:
-        raise ValueError("lifter: 4 to 64 samples expected")
+def _one_shot(x, T, F, hop, device, call):
+    """With a StftRoundTrip of x's rows, n_samples T and this geometry: x float32 [S][n_in] goes up, call(st, d_in, d_out) runs, the device
+    is synchronised, d_out float32 [S][T] comes down and the handle is closed.  -> (d_out's array, what `call` returned)."""
+    import torch
+    from . import StftRoundTrip
+    dev = torch.device("cuda", device)
+    st = StftRoundTrip(x.shape[0], int(T), int(F), int(hop), device=device)
+    try:
+        d_in = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
+        d_out = torch.empty((x.shape[0], int(T)), dtype=torch.float32, device=dev)
+        res = call(st, d_in, d_out)
+        torch.cuda.synchronize(dev)
+        return d_out.cpu().numpy(), res
+    finally:
+        st.close()
 
 
 class _FormantShiftRunner:
@@ -295,19 +329,10 @@ class _FormantShiftRunner:
         self.hop, self.device = int(hop), device
 
     def run(self, x, semitones, formant, lifter):
-        import torch
-        from . import StftRoundTrip
-        dev = torch.device("cuda", self.device)
-        st = StftRoundTrip(x.shape[0], x.shape[1], 1024, self.hop, device=self.device)
-        try:
-            d_in = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
-            d_out = torch.empty_like(d_in)
+        def call(st, d_in, d_out):
             st.pitch_shift_formant(d_in, d_out, semitones=np.asarray(semitones, np.float64).reshape(-1, 1) * np.ones((1, st.n_frames)),
                                    formant_semitones=float(formant), lifter=int(lifter))
-            torch.cuda.synchronize(dev)
-            return d_out.cpu().numpy()
-        finally:
-            st.close()
+        return _one_shot(x, x.shape[1], 1024, self.hop, self.device, call)[0]
 
 
 def pv_shift_formant(voices, shift, formant=0.0, lifter=32, N=1024, hop=256, device=0, stream=False, blocks_per_call=16, processor=None):
@@ -317,35 +342,20 @@ def pv_shift_formant(voices, shift, formant=0.0, lifter=32, N=1024, hop=256, dev
     overlap of 1024-point frames; stream: block by block through PhaseVocoderStream.run(curve=..., formant_semitones=...), as pv_glide
     runs.  Returns float32 [2][len] per recording.  `processor` (tests): an object with run(x, semitones, formant, lifter) (batch) or
     latency and run(x, blocks_per_call, curve, formant_semitones, lifter) (stream) to use instead of the GPU."""
-    S = len(voices)
-    if S == 0:
-        raise ValueError("no recordings")
-    per = [float(v) for v in shift] if isinstance(shift, (list, tuple, np.ndarray)) else [float(shift)] * S
-    if len(per) != S:
-        raise ValueError("shift: one value per recording expected")
-    if not all(-12.0 <= v <= 12.0 for v in per):
-        raise ValueError("shift: intervals within +-12 semitones expected")
+    S = _batch_size(voices)
+    per = _per_recording(shift, S, "shift", float, *SHIFT_RANGE)
     _check_formant(formant, lifter)
-    N, hop = int(N), int(hop)
-    lens = [int(np.asarray(v).shape[-1]) for v in voices]
-    p = processor
-    if stream and p is None:
-        from . import PhaseVocoderStream
-        p = PhaseVocoderStream(S, N, hop=hop, device=device)
-    T = max(lens) if stream else 1024 + -(-max(lens) // hop) * hop             # batch: every sample under the full overlap of frames
-    x = np.zeros((S, T), np.float32)
-    for s, v in enumerate(voices):
-        v = np.asarray(v, np.float32)
-        if v.ndim != 1:
-            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
-        x[s, :lens[s]] = v
+    hop = int(hop)
+    lens = _lengths(voices)
     if stream:
-        y = p.run(x, blocks_per_call=int(blocks_per_call), curve=np.array([per]), formant_semitones=float(formant), lifter=int(lifter))
+        p = _stream(processor, S, N, hop, device)
+        y = p.run(_pack_mono(voices, lens, max(lens)), blocks_per_call=int(blocks_per_call), curve=np.array([per]), formant_semitones=float(formant),
+                  lifter=int(lifter))
     else:
-        if p is None:
-            p = _FormantShiftRunner(hop, device)
+        x = _pack_mono(voices, lens, 1024 + -(-max(lens) // hop) * hop)        # every sample under the full overlap of frames
+        p = processor if processor is not None else _FormantShiftRunner(hop, device)
         y = p.run(x, per, float(formant), int(lifter))
-    return [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
+    return _both_channels(y, lens)
 
 
 class _StretchRunner:
@@ -356,21 +366,9 @@ class _StretchRunner:
         self.F, self.hop, self.device = int(F), int(hop), device
 
     def run(self, x, pos, T, semitones, locked=False):
-        import torch
-        from . import StftRoundTrip
-        dev = torch.device("cuda", self.device)
-        st = StftRoundTrip(x.shape[0], int(T), self.F, self.hop, device=self.device)
-        try:
-            d_in = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
-            d_out = torch.empty((x.shape[0], int(T)), dtype=torch.float32, device=dev)
-            if locked:
-                st.time_stretch_locked(d_in, d_out, positions=pos, semitones=float(semitones))
-            else:
-                st.time_stretch(d_in, d_out, positions=pos, semitones=float(semitones))
-            torch.cuda.synchronize(dev)
-            return d_out.cpu().numpy()
-        finally:
-            st.close()
+        def call(st, d_in, d_out):
+            (st.time_stretch_locked if locked else st.time_stretch)(d_in, d_out, positions=pos, semitones=float(semitones))
+        return _one_shot(x, T, self.F, self.hop, self.device, call)[0]
 
 
 def pv_stretch(voices, stretch, shift=0.0, F=1024, hop=256, device=0, processor=None, locked=False):
@@ -381,35 +379,22 @@ def pv_stretch(voices, stretch, shift=0.0, F=1024, hop=256, device=0, processor=
     stretch)] per recording (the signal on both channels).  `processor` (tests): an object with run(x, pos, T, semitones) to use instead
     of the GPU.  locked: the peak-locked time stretch instead (StftRoundTrip.time_stretch_locked; 1024-point frames); run then also
     receives locked=True."""
-    S = len(voices)
-    if S == 0:
-        raise ValueError("no recordings")
-    per = [float(v) for v in stretch] if isinstance(stretch, (list, tuple, np.ndarray)) else [float(stretch)] * S
-    if len(per) != S:
-        raise ValueError("stretch: one value per recording expected")
-    if not all(0.25 <= v <= 4.0 for v in per):
-        raise ValueError("stretch: factors within [0.25, 4] expected")
+    S = _batch_size(voices)
+    per = _per_recording(stretch, S, "stretch", float, 0.25, 4.0, "stretch: factors within [0.25, 4] expected")
     if not -12.0 <= float(shift) <= 12.0:
         raise ValueError("shift: an interval within +-12 semitones expected")
     F, hop = int(F), int(hop)
-    if locked and F != 1024:
-        raise ValueError("--locked: 1024-point frames expected (the peak-locked kernels are not built for 2048)")
-    lens = [int(np.asarray(v).shape[-1]) for v in voices]
+    _check_locked(locked, None, F)
+    lens = _lengths(voices)
     outs = [int(np.ceil(n * a)) for n, a in zip(lens, per)]
-    n_in = max(max(lens), F)
-    x = np.zeros((S, n_in), np.float32)
-    for s, v in enumerate(voices):
-        v = np.asarray(v, np.float32)
-        if v.ndim != 1:
-            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
-        x[s, :lens[s]] = v
+    x = _pack_mono(voices, lens, max(max(lens), F))
     T = F + -(-max(outs) // hop) * hop                                         # every output sample under the full overlap of frames
     nF = (T - F) // hop + 1
     # (the formula of vp_stretch_positions, against each recording's own length: behind its end a recording repeats its last frame)
     pos = np.stack([np.minimum(np.floor(np.arange(nF, dtype=np.int64) * hop / a), max(n, F) - F) for n, a in zip(lens, per)]).astype(np.int32)
     p = processor if processor is not None else _StretchRunner(F, hop, device)
-    y = p.run(x, pos, T, float(shift), locked=True) if locked else p.run(x, pos, T, float(shift))
-    return [np.ascontiguousarray(np.stack([y[s, :outs[s]]] * 2)) for s in range(S)]
+    y = p.run(x, pos, T, float(shift), **_mode_kw(None, 0, locked))
+    return _both_channels(y, outs)
 
 
 class _AutotuneRunner:
@@ -419,19 +404,11 @@ class _AutotuneRunner:
         self.F, self.hop, self.device = int(F), int(hop), device
 
     def run(self, x, fs, keys, formant=None, lifter=32, locked=False):
-        import torch
-        from . import StftRoundTrip
-        dev = torch.device("cuda", self.device)
-        st = StftRoundTrip(x.shape[0], x.shape[1], self.F, self.hop, device=self.device)
-        try:
-            d_in = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
-            d_out = torch.empty_like(d_in)
-            lk = {"locked": True} if locked else {}
-            period, ratio = st.autotune(d_in, d_out, float(fs), keys=[int(k) for k in keys], formant_semitones=formant, lifter=int(lifter), **lk)
-            torch.cuda.synchronize(dev)
-            return d_out.cpu().numpy(), period.cpu().numpy(), ratio.cpu().numpy()
-        finally:
-            st.close()
+        def call(st, d_in, d_out):
+            return st.autotune(d_in, d_out, float(fs), keys=[int(k) for k in keys], formant_semitones=formant, lifter=int(lifter),
+                               **_mode_kw(None, 0, locked))
+        y, (period, ratio) = _one_shot(x, x.shape[1], self.F, self.hop, self.device, call)
+        return y, period.cpu().numpy(), ratio.cpu().numpy()
 
 
 def tune_length(max_len, fs, F, hop):
@@ -439,6 +416,22 @@ def tune_length(max_len, fs, F, hop):
     the tracker's window of F + ceil(fs / 100) samples."""
     F, hop = int(F), int(hop)
     return max(F + -(-int(max_len) // hop) * hop, F + int(np.ceil(float(fs) / 100.0)))
+
+
+def _check_tune(voices, fs, key, formant, lifter):
+    """What both pvtune flows check first -> the keys, one per recording."""
+    keys = _per_recording(key, _batch_size(voices), "key", int, 0, 12, "key: 0..12 expected (12 = chromatic)")
+    if not 8000.0 <= float(fs) <= 51200.0:
+        raise ValueError("pvtune: sample rates from 8000 to 51200 Hz are served")
+    _check_formant(formant, lifter)
+    return keys
+
+
+def _tune(p, voices, lens, T, fs, keys, kw, offset, with_track):
+    """Both pvtune flows from the packed call on: p.run(x, fs, keys, **kw) -> the recordings from sample `offset` on, with the track or not."""
+    y, period, ratio = p.run(_pack_mono(voices, lens, T), float(fs), keys, **kw)
+    outs = _both_channels(y, lens, offset)
+    return (outs, period, ratio) if with_track else outs
 
 
 def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, with_track=False, formant=None, lifter=32, locked=False):
@@ -451,35 +444,13 @@ def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, w
     singer's formants where they were; lifter: the cepstral lifter, 4 .. 64 samples; run then also receives formant and lifter.
     locked: the correction runs through the peak-locked call (StftRoundTrip.autotune(locked=True); 1024-point frames, not together with
     formant); run then also receives locked=True."""
-    S = len(voices)
-    if S == 0:
-        raise ValueError("no recordings")
-    keys = [int(k) for k in key] if isinstance(key, (list, tuple, np.ndarray)) else [int(key)] * S
-    if len(keys) != S:
-        raise ValueError("key: one value per recording expected")
-    if not all(0 <= k <= 12 for k in keys):
-        raise ValueError("key: 0..12 expected (12 = chromatic)")
-    if not 8000.0 <= float(fs) <= 51200.0:
-        raise ValueError("pvtune: sample rates from 8000 to 51200 Hz are served")
-    _check_formant(formant, lifter)
+    keys = _check_tune(voices, fs, key, formant, lifter)
     if formant is not None and int(F) != 1024:
         raise ValueError("pvtune --formant: 1024-point frames expected (the formant kernels are not built for 2048)")
     _check_locked(locked, formant, F)
-    lens = [int(np.asarray(v).shape[-1]) for v in voices]
-    T = tune_length(max(lens), fs, F, hop)
-    x = np.zeros((S, T), np.float32)
-    for s, v in enumerate(voices):
-        v = np.asarray(v, np.float32)
-        if v.ndim != 1:
-            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
-        x[s, :lens[s]] = v
+    lens = _lengths(voices)
     p = processor if processor is not None else _AutotuneRunner(F, hop, device)
-    kw = {} if formant is None else dict(formant=float(formant), lifter=int(lifter))
-    if locked:
-        kw["locked"] = True
-    y, period, ratio = p.run(x, float(fs), keys, **kw)
-    outs = [np.ascontiguousarray(np.stack([y[s, :lens[s]]] * 2)) for s in range(S)]
-    return (outs, period, ratio) if with_track else outs
+    return _tune(p, voices, lens, tune_length(max(lens), fs, F, hop), fs, keys, _mode_kw(formant, lifter, locked), 0, with_track)
 
 
 class _StreamTuneRunner:
@@ -492,7 +463,7 @@ class _StreamTuneRunner:
     def run(self, x, fs, keys, formant=None, lifter=32, locked=False):
         import torch
         from . import PhaseVocoderStream, StreamingPitchTracker
-        lk = {"locked": True} if locked else {}
+        lk = _mode_kw(None, 0, locked)
         S, N = x.shape[0], self.N
         nb = x.shape[1] // N
         dev = torch.device("cuda", self.device)
@@ -530,37 +501,16 @@ def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glid
     costs the same at every N: N = 64 costs 16 times as much per second of audio as N = 1024.  `processor` (tests): an object with
     run(x, fs, keys) to use instead of the GPU.  formant, lifter, locked: as pv_autotune's (the shifter's frames are 1024 points whatever
     F)."""
-    S = len(voices)
-    if S == 0:
-        raise ValueError("no recordings")
-    keys = [int(k) for k in key] if isinstance(key, (list, tuple, np.ndarray)) else [int(key)] * S
-    if len(keys) != S:
-        raise ValueError("key: one value per recording expected")
-    if not all(0 <= k <= 12 for k in keys):
-        raise ValueError("key: 0..12 expected (12 = chromatic)")
-    if not 8000.0 <= float(fs) <= 51200.0:
-        raise ValueError("pvtune: sample rates from 8000 to 51200 Hz are served")
-    _check_formant(formant, lifter)
+    keys = _check_tune(voices, fs, key, formant, lifter)
     _check_locked(locked, formant)
     if int(N) < 1 or int(F) not in (1024, 2048):
         raise ValueError("pvtune --stream: a block of at least one sample and a tracker frame of 1024 or 2048 expected")
     if not (0 <= int(hold) <= 1 << 20 and 0.0 < float(glide) <= 1.0):
         raise ValueError("pvtune --stream: 0 <= hold <= 2^20 blocks and 0 < glide <= 1 expected")
-    lens = [int(np.asarray(v).shape[-1]) for v in voices]
+    lens = _lengths(voices)
     T, lat = stream_tune_length(max(lens), N, hop)
-    x = np.zeros((S, T), np.float32)
-    for s, v in enumerate(voices):
-        v = np.asarray(v, np.float32)
-        if v.ndim != 1:
-            raise ValueError(f"voice {s}: expected a mono signal, got shape {v.shape}")
-        x[s, :lens[s]] = v
     p = processor if processor is not None else _StreamTuneRunner(N, hop, F, hold, glide, device)
-    kw = {} if formant is None else dict(formant=float(formant), lifter=int(lifter))
-    if locked:
-        kw["locked"] = True
-    y, period, ratio = p.run(x, float(fs), keys, **kw)
-    outs = [np.ascontiguousarray(np.stack([y[s, lat:lat + lens[s]]] * 2)) for s in range(S)]
-    return (outs, period, ratio) if with_track else outs
+    return _tune(p, voices, lens, T, fs, keys, _mode_kw(formant, lifter, locked), lat, with_track)
 
 
 def write_track_csv(path, fs, hop, period, ratio, n_samples=None):

@@ -535,6 +535,36 @@ def stretch_positions(n_frames, hop, stretch, n_in, frame_len=1024):
     return pos
 
 
+def _is(t, dtype, shape):
+    """The contract of every device argument: a tensor on the GPU of this dtype and shape, contiguous."""
+    return t.is_cuda and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()
+
+
+_T = None                               # torch, once a helper below has needed it (the package imports without it)
+
+
+def _torch():
+    global _T
+    import torch
+    _T = torch
+    return torch
+
+
+def _stream_of(stream, t):
+    """`stream`, or torch's current stream on t's device when there is none, as the library takes it."""
+    return C.c_void_p((_T or _torch()).cuda.current_stream(t.device).cuda_stream if stream is None else stream)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _not_formant_on_locked(formant_semitones, d_formant=None):
+    """A locked call's first check (callers test `locked` themselves: the other calls pay nothing for it)."""
+    if formant_semitones is not None or d_formant is not None:
+        raise ValueError("locked and formant_semitones exclude each other: formant correction on top of locking is not built")
+
+
 def _upload_ratios(tables, semitones, dev):
     """The ratios of a table of intervals (already in the kernel's layout) in a device table of that shape, allocated once per shape in
     the caller's `tables`; the copy goes on torch's current stream."""
@@ -554,7 +584,7 @@ def _device_keys(owner, keys, dev):
     if keys is None:
         return None
     if isinstance(keys, torch.Tensor):
-        assert keys.is_cuda and keys.dtype == torch.int32 and tuple(keys.shape) == (owner.S,) and keys.is_contiguous()
+        assert _is(keys, torch.int32, (owner.S,))
         return keys
     k = np.asarray(keys)
     assert k.dtype.kind in "iu" and k.shape in ((), (owner.S,)), (k.dtype, k.shape)
@@ -574,7 +604,7 @@ def _device_formants(owner, formant_semitones, d_formant, dev):
     (owner._formant_table), rewritten on torch's current stream."""
     import torch
     if d_formant is not None:
-        assert d_formant.is_cuda and d_formant.dtype == torch.float64 and tuple(d_formant.shape) == (owner.S,) and d_formant.is_contiguous()
+        assert _is(d_formant, torch.float64, (owner.S,))
         return d_formant
     st = np.asarray(0.0 if formant_semitones is None else formant_semitones, dtype=np.float64)
     assert st.shape in ((), (owner.S,)), st.shape
@@ -596,17 +626,11 @@ class StftRoundTrip:
             raise VpError(rc, self.L.vp_error_string(rc).decode())
         self.h, self.S, self.T, self.F, self.hop = h, n_streams, n_samples, frame_len, hop
         self.n_frames = self.L.vp_stft_num_frames(h)
+        self._curve_tables, self._stretch_tables = {}, {}      # device ratio / position tables, one per shape, allocated at first use
 
     def __call__(self, d_in, d_out, d_mag=None, stream=None):
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
-        assert d_out.is_cuda and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
-        if stream is None:
-            stream = torch.cuda.current_stream(d_in.device).cuda_stream
-        rc = self.L.vp_stft_roundtrip(self.h, d_in.data_ptr(), d_out.data_ptr(), d_mag.data_ptr() if d_mag is not None else None,
-                                      C.c_void_p(stream))
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
+        self._io(d_in, d_out)
+        self._chk(self.L.vp_stft_roundtrip(self.h, d_in.data_ptr(), d_out.data_ptr(), _ptr(d_mag), _stream_of(stream, d_in)))
 
     @property
     def fused(self):
@@ -629,18 +653,45 @@ class StftRoundTrip:
     def precision(self):
         return "f32" if self.L.vp_stft_get_precision(self.h) == 1 else "f64"
 
+    def _chk(self, rc):
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+
+    def _io(self, d_in, d_out, any_length=False):
+        """The contract of a call's input and output: device float32 [S][n_samples], contiguous (any_length: the input is [S][n_in] with
+        n_in >= frame_len).  Returns the input's row length."""
+        f32 = (_T or _torch()).float32
+        n_in = int(d_in.shape[1]) if any_length and d_in.dim() == 2 else self.T
+        assert d_in.is_cuda and d_in.dtype == f32 and tuple(d_in.shape) == (self.S, n_in) and d_in.is_contiguous()
+        assert d_out.is_cuda and d_out.dtype == f32 and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
+        assert n_in >= self.F, n_in
+        return n_in
+
+    def _ratio_table(self, semitones, d_ratio, dev, scalar=False, per_stream=False, none_is_zero=False):
+        """`semitones` or `d_ratio` as the checked device ratio table [S][n_frames] of a call.  Host intervals are [n_frames] or
+        [S][n_frames], with `scalar` also one value, with `per_stream` also [S] (when S != n_frames: a vector of n_frames is a curve); they
+        become ratios in the device table the handle keeps per shape.  none_is_zero: neither given means no shift."""
+        torch = _T or _torch()
+        if none_is_zero:
+            assert semitones is None or d_ratio is None, "at most one of semitones and d_ratio"
+            semitones = 0.0 if semitones is None and d_ratio is None else semitones
+        assert (semitones is None) != (d_ratio is None), "one of semitones and d_ratio"
+        if d_ratio is None:
+            st = np.asarray(semitones, dtype=np.float64)
+            if per_stream and st.shape == (self.S,) and self.S != self.n_frames:
+                st = st[:, None]
+            admitted = [(self.n_frames,), (self.S, self.n_frames)] + [()] * scalar + [(self.S, 1)] * per_stream
+            assert st.shape in admitted, st.shape
+            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(st, (self.S, self.n_frames)), dev)
+        assert _is(d_ratio, torch.float64, (self.S, self.n_frames))
+        return d_ratio
+
     def pitch_shift(self, d_in, d_out, semitones, stream=None):
         """Round trip with the phase-vocoder stage (per-bin phase unwrap / accumulate) shifting the pitch by `semitones`
         (|semitones| <= 12), for 1024- and 2048-point frames at every hop the handle admits.  Always double precision
         (set_precision has no effect on it); every call starts from zero phase state."""
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
-        assert d_out.is_cuda and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
-        if stream is None:
-            stream = torch.cuda.current_stream(d_in.device).cuda_stream
-        rc = self.L.vp_stft_pitch_shift(self.h, d_in.data_ptr(), d_out.data_ptr(), float(semitones), C.c_void_p(stream))
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
+        self._io(d_in, d_out)
+        self._chk(self.L.vp_stft_pitch_shift(self.h, d_in.data_ptr(), d_out.data_ptr(), float(semitones), _stream_of(stream, d_in)))
 
     def pitch_shift_curve(self, d_in, d_out, semitones=None, stream=None, d_ratio=None):
         """pitch_shift along a pitch curve (vp_stft_pitch_shift_curve): `semitones` is array-like [n_frames] (every stream follows it) or
@@ -648,42 +699,18 @@ class StftRoundTrip:
         semitones_to_ratios and are uploaded into a device table the handle allocates once (on torch's current stream: with another
         `stream`, order it behind that one).  d_ratio instead: a device float64 tensor [S][n_frames] of ratios, used as it is (the
         kernel clamps to [0.5, 2])."""
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
-        assert d_out.is_cuda and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
-        assert (semitones is None) != (d_ratio is None), "one of semitones and d_ratio"
-        if d_ratio is None:
-            st = np.asarray(semitones, dtype=np.float64)
-            assert st.shape in ((self.n_frames,), (self.S, self.n_frames)), st.shape
-            if not hasattr(self, "_curve_tables"):
-                self._curve_tables = {}
-            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(st, (self.S, self.n_frames)), d_in.device)
-        assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (self.S, self.n_frames) and d_ratio.is_contiguous()
-        if stream is None:
-            stream = torch.cuda.current_stream(d_in.device).cuda_stream
-        rc = self.L.vp_stft_pitch_shift_curve(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), C.c_void_p(stream))
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
+        self._io(d_in, d_out)
+        d_ratio = self._ratio_table(semitones, d_ratio, d_in.device)
+        self._chk(self.L.vp_stft_pitch_shift_curve(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), _stream_of(stream, d_in)))
 
     def pitch_shift_locked(self, d_in, d_out, semitones=None, stream=None, d_ratio=None):
         """pitch_shift_curve with peak locking (vp_stft_pitch_shift_locked; 1024-point frames): every frame's spectral peaks are found and a
         peak's whole region of bins moves by one integer offset and turns by one accumulated angle, so a sinusoid's main lobe stays one
         windowed sinusoid (the definition is tests/pv_lock_reference.py).  `semitones`, `d_ratio` and `stream` as in pitch_shift_curve --
         the same table-building path.  A 2048-point handle raises VpError (VP_ERR_GEOMETRY)."""
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
-        assert d_out.is_cuda and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
-        assert (semitones is None) != (d_ratio is None), "one of semitones and d_ratio"
-        if d_ratio is None:
-            st = np.asarray(semitones, dtype=np.float64)
-            assert st.shape in ((self.n_frames,), (self.S, self.n_frames)), st.shape
-            if not hasattr(self, "_curve_tables"):
-                self._curve_tables = {}
-            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(st, (self.S, self.n_frames)), d_in.device)
-        assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (self.S, self.n_frames) and d_ratio.is_contiguous()
-        if stream is None:
-            stream = torch.cuda.current_stream(d_in.device).cuda_stream
-        self._track_chk(self.L.vp_stft_pitch_shift_locked(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), C.c_void_p(stream)))
+        self._io(d_in, d_out)
+        d_ratio = self._ratio_table(semitones, d_ratio, d_in.device)
+        self._track_chk(self.L.vp_stft_pitch_shift_locked(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), _stream_of(stream, d_in)))
 
     def pitch_shift_formant(self, d_in, d_out, semitones=None, stream=None, d_ratio=None, formant_semitones=0.0, lifter=FORMANT_LIFTER, d_formant=None):
         """pitch_shift_curve with the spectral envelope kept apart from the pitch (vp_stft_pitch_shift_formant; 1024-point frames): the
@@ -691,43 +718,32 @@ class StftRoundTrip:
         |value| <= 12 (d_formant instead: a device float64 tensor [S] of ratios, used as it is).  `semitones`: a scalar, [S] (one interval
         per stream; with S == n_frames a vector is a curve), [n_frames] or [S][n_frames]; d_ratio as in pitch_shift_curve -- the same
         table-building path.  lifter: length of the cepstral lifter in samples, 4 .. 64 (short: a smoother envelope)."""
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
-        assert d_out.is_cuda and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
-        assert (semitones is None) != (d_ratio is None), "one of semitones and d_ratio"
-        if d_ratio is None:
-            st = np.asarray(semitones, dtype=np.float64)
-            if st.shape == (self.S,) and self.S != self.n_frames:
-                st = st[:, None]
-            assert st.shape in ((), (self.S, 1), (self.n_frames,), (self.S, self.n_frames)), st.shape
-            if not hasattr(self, "_curve_tables"):
-                self._curve_tables = {}
-            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(st, (self.S, self.n_frames)), d_in.device)
-        assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (self.S, self.n_frames) and d_ratio.is_contiguous()
+        self._io(d_in, d_out)
+        d_ratio = self._ratio_table(semitones, d_ratio, d_in.device, scalar=True, per_stream=True)
         d_formant = _device_formants(self, formant_semitones, d_formant, d_in.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(d_in.device).cuda_stream
         self._track_chk(self.L.vp_stft_pitch_shift_formant(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), d_formant.data_ptr(), int(lifter),
-                                                           C.c_void_p(stream)))
+                                                           _stream_of(stream, d_in)))
 
-    def _position_table(self, positions, stretch, n_in, dev):
-        """The position table of a time-stretch call from host data -- `stretch` through stretch_positions, `positions` broadcast and
-        clipped to int32 -- in the device table the handle keeps per shape (self._stretch_tables), rewritten on torch's current stream."""
-        import torch
+    def _position_table(self, positions, stretch, d_pos, n_in, dev):
+        """The checked device position table [S][n_frames] of a time-stretch call: d_pos as it is, or host data -- `stretch` through
+        stretch_positions, `positions` broadcast and clipped to int32 -- in the device table the handle keeps per shape
+        (self._stretch_tables), rewritten on torch's current stream."""
+        torch = _T or _torch()
+        assert (positions is not None) + (stretch is not None) + (d_pos is not None) == 1, "one of positions, stretch and d_pos"
         if stretch is not None:
             a = np.broadcast_to(np.asarray(stretch, dtype=np.float64).reshape(-1), (self.S,))
             pos = np.stack([stretch_positions(self.n_frames, self.hop, v, n_in, self.F) for v in a])
-        else:
+        elif positions is not None:
             pos = np.asarray(positions)
             assert pos.dtype.kind in "iu" and pos.shape in ((self.n_frames,), (self.S, self.n_frames)), (pos.dtype, pos.shape)
             pos = np.clip(np.broadcast_to(pos, (self.S, self.n_frames)), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
-        if not hasattr(self, "_stretch_tables"):
-            self._stretch_tables = {}
-        tab = self._stretch_tables.get(pos.shape)
-        if tab is None:
-            tab = self._stretch_tables[pos.shape] = torch.empty(pos.shape, dtype=torch.int32, device=dev)
-        tab.copy_(torch.from_numpy(np.ascontiguousarray(pos)))
-        return tab
+        if d_pos is None:
+            d_pos = self._stretch_tables.get(pos.shape)
+            if d_pos is None:
+                d_pos = self._stretch_tables[pos.shape] = torch.empty(pos.shape, dtype=torch.int32, device=dev)
+            d_pos.copy_(torch.from_numpy(np.ascontiguousarray(pos)))
+        assert _is(d_pos, torch.int32, (self.S, self.n_frames))
+        return d_pos
 
     def time_stretch(self, d_in, d_out, positions=None, stretch=None, semitones=0.0, stream=None, d_pos=None):
         """Time stretch (vp_stft_time_stretch): pitch_shift with frame f of stream s analysed at input sample positions[s][f] and written
@@ -740,20 +756,9 @@ class StftRoundTrip:
         device table the handle allocates once per shape (on torch's current stream: with another `stream`, order it behind that one).
         semitones (|value| <= 12): the pitch shift on top, 0 = pure stretch.  Always double precision; every call starts from zero phase
         state."""
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float32 and d_in.dim() == 2 and d_in.shape[0] == self.S and d_in.is_contiguous()
-        assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
-        n_in = int(d_in.shape[1])
-        assert n_in >= self.F, n_in
-        assert (positions is not None) + (stretch is not None) + (d_pos is not None) == 1, "one of positions, stretch and d_pos"
-        if d_pos is None:
-            d_pos = self._position_table(positions, stretch, n_in, d_in.device)
-        assert d_pos.is_cuda and d_pos.dtype == torch.int32 and tuple(d_pos.shape) == (self.S, self.n_frames) and d_pos.is_contiguous()
-        if stream is None:
-            stream = torch.cuda.current_stream(d_in.device).cuda_stream
-        rc = self.L.vp_stft_time_stretch(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), float(semitones), C.c_void_p(stream))
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
+        n_in = self._io(d_in, d_out, any_length=True)
+        d_pos = self._position_table(positions, stretch, d_pos, n_in, d_in.device)
+        self._chk(self.L.vp_stft_time_stretch(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), float(semitones), _stream_of(stream, d_in)))
 
     def time_stretch_locked(self, d_in, d_out, positions=None, stretch=None, semitones=None, stream=None, d_pos=None, d_ratio=None):
         """time_stretch with peak locking (vp_stft_time_stretch_locked; 1024-point frames): the frames are analysed at the table's positions
@@ -763,27 +768,11 @@ class StftRoundTrip:
         is per frame and per stream: `semitones` a scalar, [n_frames] (every stream follows the curve) or [S][n_frames], each |value| <= 12,
         None = no shift; d_ratio instead: a device float64 tensor [S][n_frames] of ratios, used as it is (the kernel clamps to [0.5, 2]).
         A 2048-point handle raises VpError (VP_ERR_GEOMETRY)."""
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float32 and d_in.dim() == 2 and d_in.shape[0] == self.S and d_in.is_contiguous()
-        assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
-        n_in = int(d_in.shape[1])
-        assert n_in >= self.F, n_in
-        assert (positions is not None) + (stretch is not None) + (d_pos is not None) == 1, "one of positions, stretch and d_pos"
-        assert semitones is None or d_ratio is None, "at most one of semitones and d_ratio"
-        if d_pos is None:
-            d_pos = self._position_table(positions, stretch, n_in, d_in.device)
-        assert d_pos.is_cuda and d_pos.dtype == torch.int32 and tuple(d_pos.shape) == (self.S, self.n_frames) and d_pos.is_contiguous()
-        if d_ratio is None:
-            st = np.asarray(0.0 if semitones is None else semitones, dtype=np.float64)
-            assert st.shape in ((), (self.n_frames,), (self.S, self.n_frames)), st.shape
-            if not hasattr(self, "_curve_tables"):
-                self._curve_tables = {}
-            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(st, (self.S, self.n_frames)), d_in.device)
-        assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (self.S, self.n_frames) and d_ratio.is_contiguous()
-        if stream is None:
-            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        n_in = self._io(d_in, d_out, any_length=True)
+        d_pos = self._position_table(positions, stretch, d_pos, n_in, d_in.device)
+        d_ratio = self._ratio_table(semitones, d_ratio, d_in.device, scalar=True, none_is_zero=True)
         self._track_chk(self.L.vp_stft_time_stretch_locked(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(),
-                                                           C.c_void_p(stream)))
+                                                           _stream_of(stream, d_in)))
 
     def _track_tables(self, keys, dev):
         """(d_key or None, period, ratio): the call's key table and outputs.  The key table is kept per handle (one device int32 [S],
@@ -807,12 +796,10 @@ class StftRoundTrip:
         a device int32 tensor [S]; None = chromatic.  8000 <= sample_rate <= 51200 and n_samples >= frame_len + ceil(sample_rate / 100)
         (VpError otherwise).  Frames are independent: no smoothing, no hold across unvoiced frames."""
         import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
+        assert _is(d_in, torch.float32, (self.S, self.T))
         d_key, period, ratio = self._track_tables(keys, d_in.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(d_in.device).cuda_stream
-        self._track_chk(self.L.vp_stft_track_pitch(self.h, d_in.data_ptr(), float(sample_rate), d_key.data_ptr() if d_key is not None else None,
-                                                   period.data_ptr(), ratio.data_ptr(), C.c_void_p(stream)))
+        self._track_chk(self.L.vp_stft_track_pitch(self.h, d_in.data_ptr(), float(sample_rate), _ptr(d_key), period.data_ptr(), ratio.data_ptr(),
+                                                   _stream_of(stream, d_in)))
         return period, ratio
 
     def autotune(self, d_in, d_out, sample_rate, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False):
@@ -822,26 +809,19 @@ class StftRoundTrip:
         (vp_stft_autotune_formant) -- 0 keeps the formants where the singer had them.
         locked=True: track_pitch followed by pitch_shift_locked along its ratios, on the same stream (not together with
         formant_semitones: ValueError before any launch)."""
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == (self.S, self.T) and d_in.is_contiguous()
-        assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == (self.S, self.T) and d_out.is_contiguous()
+        self._io(d_in, d_out)
         if locked:
-            if formant_semitones is not None:
-                raise ValueError("locked and formant_semitones exclude each other: formant correction on top of locking is not built")
+            _not_formant_on_locked(formant_semitones)
             period, ratio = self.track_pitch(d_in, sample_rate, keys=keys, stream=stream)
             self.pitch_shift_locked(d_in, d_out, stream=stream, d_ratio=ratio)
             return period, ratio
         d_key, period, ratio = self._track_tables(keys, d_in.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        head = (self.h, d_in.data_ptr(), d_out.data_ptr(), float(sample_rate), _ptr(d_key), period.data_ptr(), ratio.data_ptr())
         if formant_semitones is not None:
             d_formant = _device_formants(self, formant_semitones, None, d_in.device)
-            self._track_chk(self.L.vp_stft_autotune_formant(self.h, d_in.data_ptr(), d_out.data_ptr(), float(sample_rate),
-                                                            d_key.data_ptr() if d_key is not None else None, period.data_ptr(), ratio.data_ptr(),
-                                                            d_formant.data_ptr(), int(lifter), C.c_void_p(stream)))
-            return period, ratio
-        self._track_chk(self.L.vp_stft_autotune(self.h, d_in.data_ptr(), d_out.data_ptr(), float(sample_rate),
-                                                d_key.data_ptr() if d_key is not None else None, period.data_ptr(), ratio.data_ptr(), C.c_void_p(stream)))
+            self._track_chk(self.L.vp_stft_autotune_formant(*head, d_formant.data_ptr(), int(lifter), _stream_of(stream, d_in)))
+        else:
+            self._track_chk(self.L.vp_stft_autotune(*head, _stream_of(stream, d_in)))
         return period, ratio
 
     def close(self):
@@ -872,6 +852,7 @@ class PhaseVocoderStream:
         if rc:
             raise VpError(rc, self.L.vp_error_string(rc).decode())
         self.h, self.S, self.N, self.hop, self.F, self.device = h, int(n_streams), int(block_size), int(hop), int(frame_len), device
+        self._curve_tables = {}                                # device ratio tables, one per n_blocks, allocated at first use
 
     def _chk(self, rc):
         if rc:
@@ -903,6 +884,11 @@ class PhaseVocoderStream:
         self._chk(self.L.vp_pv_process_block(self.h, x.ctypes.data, y.ctypes.data))
         return y
 
+    def _held_table(self, n_blocks, dev):
+        """The device ratio table [n_blocks][S] of a curve call without one of its own: the intervals set_semitones holds, for every block."""
+        held = np.array([self.semitones(s) for s in range(self.S)])
+        return _upload_ratios(self._curve_tables, np.broadcast_to(held, (n_blocks, self.S)), dev)
+
     def process_device(self, d_in, d_out, n_blocks=1, stream=None, semitones_per_block=None, d_ratio=None, formant_semitones=None, lifter=FORMANT_LIFTER,
                        d_formant=None, locked=False):
         """n_blocks blocks on the device: torch float32 [n_blocks][S][N] (or [S][N] for one block), enqueued on `stream`
@@ -919,43 +905,36 @@ class PhaseVocoderStream:
         intervals set_semitones holds, like a formant call.  Not together with formant_semitones / d_formant: ValueError before any
         launch.  The kinds of call share the stream's state: after a change of kind the output is finite but carries a phase jump
         (reset() the stream at the change to avoid it)."""
+        # (the asserts and the stream's default are written out here and in autotune_device: a helper's call would be most of what a
+        # call of one small block costs the host)
         import torch
-        if locked and (formant_semitones is not None or d_formant is not None):
-            raise ValueError("locked and formant_semitones exclude each other: formant correction on top of locking is not built")
-        shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
+        if locked:
+            _not_formant_on_locked(formant_semitones, d_formant)
+        n = int(n_blocks)
+        shape = (self.S, self.N) if n == 1 and d_in.dim() == 2 else (n, self.S, self.N)
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
         assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == shape and d_out.is_contiguous()
         if stream is None:
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        io, st = (self.h, d_in.data_ptr(), d_out.data_ptr()), C.c_void_p(stream)
         if semitones_per_block is not None:
             assert d_ratio is None, "one of semitones_per_block and d_ratio"
-            st = np.asarray(semitones_per_block, dtype=np.float64)
-            assert st.shape in ((int(n_blocks),), (int(n_blocks), self.S)), st.shape
-            if not hasattr(self, "_curve_tables"):
-                self._curve_tables = {}
-            st = np.broadcast_to(st.reshape(int(n_blocks), -1), (int(n_blocks), self.S))
-            d_ratio = _upload_ratios(self._curve_tables, st, d_in.device)
+            semi = np.asarray(semitones_per_block, dtype=np.float64)
+            assert semi.shape in ((n,), (n, self.S)), semi.shape
+            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(semi.reshape(n, -1), (n, self.S)), d_in.device)
         formant = formant_semitones is not None or d_formant is not None
-        if (formant or locked) and d_ratio is None:
-            if not hasattr(self, "_curve_tables"):
-                self._curve_tables = {}
-            held = np.array([self.semitones(s) for s in range(self.S)])
-            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(held, (int(n_blocks), self.S)), d_in.device)
-        if d_ratio is not None:
-            assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (int(n_blocks), self.S) and d_ratio.is_contiguous()
-            if locked:
-                self._chk(self.L.vp_pv_process_blocks_locked_device(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), int(n_blocks),
-                                                                    C.c_void_p(stream)))
-                return
-            if formant:
-                d_formant = _device_formants(self, formant_semitones, d_formant, d_in.device)
-                self._chk(self.L.vp_pv_process_blocks_formant_device(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), d_formant.data_ptr(),
-                                                                     int(lifter), int(n_blocks), C.c_void_p(stream)))
-                return
-            self._chk(self.L.vp_pv_process_blocks_curve_device(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), int(n_blocks),
-                                                               C.c_void_p(stream)))
-            return
-        self._chk(self.L.vp_pv_process_blocks_device(self.h, d_in.data_ptr(), d_out.data_ptr(), int(n_blocks), C.c_void_p(stream)))
+        if d_ratio is None:
+            if not (formant or locked):
+                return self._chk(self.L.vp_pv_process_blocks_device(*io, n, st))
+            d_ratio = self._held_table(n, d_in.device)
+        assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (n, self.S) and d_ratio.is_contiguous()
+        if locked:
+            self._chk(self.L.vp_pv_process_blocks_locked_device(*io, d_ratio.data_ptr(), n, st))
+        elif formant:
+            d_formant = _device_formants(self, formant_semitones, d_formant, d_in.device)
+            self._chk(self.L.vp_pv_process_blocks_formant_device(*io, d_ratio.data_ptr(), d_formant.data_ptr(), int(lifter), n, st))
+        else:
+            self._chk(self.L.vp_pv_process_blocks_curve_device(*io, d_ratio.data_ptr(), n, st))
 
     def autotune_device(self, tracker, d_in, d_out, n_blocks=1, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False):
         """Automatic pitch correction block by block (vp_pv_autotune_blocks_device): `tracker` (a StreamingPitchTracker of the same
@@ -966,27 +945,25 @@ class PhaseVocoderStream:
         (vp_pv_autotune_blocks_formant_device).
         locked=True: tracker.process_device followed by process_device(d_ratio=..., locked=True) on the same stream (not together with
         formant_semitones: ValueError before any launch)."""
-        import torch
         if locked:
-            if formant_semitones is not None:
-                raise ValueError("locked and formant_semitones exclude each other: formant correction on top of locking is not built")
+            _not_formant_on_locked(formant_semitones)
             period, ratio = tracker.process_device(d_in, n_blocks=n_blocks, keys=keys, stream=stream)
             self.process_device(d_in, d_out, n_blocks=n_blocks, stream=stream, d_ratio=ratio, locked=True)
             return period, ratio
-        shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
+        import torch
+        n = int(n_blocks)
+        shape = (self.S, self.N) if n == 1 and d_in.dim() == 2 else (n, self.S, self.N)
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
         assert d_out.is_cuda and d_out.dtype == torch.float32 and tuple(d_out.shape) == shape and d_out.is_contiguous()
-        d_key, period, ratio = tracker._tables(keys, int(n_blocks), d_in.device)
+        d_key, period, ratio = tracker._tables(keys, n, d_in.device)
         if stream is None:
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        head = (self.h, tracker.h, d_in.data_ptr(), d_out.data_ptr(), d_key.data_ptr() if d_key is not None else None, period.data_ptr(), ratio.data_ptr())
         if formant_semitones is not None:
             d_formant = _device_formants(self, formant_semitones, None, d_in.device)
-            self._chk(self.L.vp_pv_autotune_blocks_formant_device(self.h, tracker.h, d_in.data_ptr(), d_out.data_ptr(),
-                                                                  d_key.data_ptr() if d_key is not None else None, period.data_ptr(), ratio.data_ptr(),
-                                                                  d_formant.data_ptr(), int(lifter), int(n_blocks), C.c_void_p(stream)))
-            return period, ratio
-        self._chk(self.L.vp_pv_autotune_blocks_device(self.h, tracker.h, d_in.data_ptr(), d_out.data_ptr(), d_key.data_ptr() if d_key is not None else None,
-                                                      period.data_ptr(), ratio.data_ptr(), int(n_blocks), C.c_void_p(stream)))
+            self._chk(self.L.vp_pv_autotune_blocks_formant_device(*head, d_formant.data_ptr(), int(lifter), n, C.c_void_p(stream)))
+        else:
+            self._chk(self.L.vp_pv_autotune_blocks_device(*head, n, C.c_void_p(stream)))
         return period, ratio
 
     def run(self, x, blocks_per_call=8, curve=None, autotune=None, keys=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False):
@@ -1000,8 +977,8 @@ class PhaseVocoderStream:
         formant_semitones (a scalar or [S]; None: as above, unchanged): every call is a formant call (process_device / autotune_device).
         locked=True: every call is a peak-locked call (process_device / autotune_device with locked=True; not with formant_semitones)."""
         assert curve is None or autotune is None, "one of curve and autotune"
-        if locked and formant_semitones is not None:
-            raise ValueError("locked and formant_semitones exclude each other: formant correction on top of locking is not built")
+        if locked:
+            _not_formant_on_locked(formant_semitones)
         lk = {"locked": True} if locked else {}                     # (without the flag: exactly the calls made before it existed)
         import torch
         x = np.asarray(x, dtype=np.float32)
