@@ -389,6 +389,22 @@ int vp_stft_pitch_shift_locked(vp_stft *p, const float *d_in, float *d_out, cons
 #define VP_FORMANT_LIFTER_MAX 64
 int vp_stft_pitch_shift_formant(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, const double *d_formant, int lifter,
                                 void *hip_stream);
+/* STFT cross-synthesis, the vocoder of this path (kernel vp_k_stft_cross): the spectral envelope of one signal, the voice, imposed on
+ * another, the carrier.  The definition is tests/pv_cross_reference.py.  Frames, window, scale and overlap-add are vp_stft_roundtrip's;
+ * between the transforms, per frame:
+ *   V = rfft(w v_frame), C = rfft(w c_frame);
+ *   env(m): L[k] = 0.5 log(m[k]^2 + 1e-12), k <= 512;  c = irfft(L, 1024);  c[n] kept for n < lifter, halved at n = lifter, 0 beyond
+ *   (symmetric);  env = rfft(c).real -- vp_stft_pitch_shift_formant's smoothed log envelope;
+ *   d = fmin(fmax(depth[s], 0), 1) (a NaN is 0; a NULL table is 1);  delta = min(d (env(|V|) - env(|C|)), ln 256);  Y = C exp(delta).
+ * The gain is real, so bins 0 and 512 stay real by themselves.  Only the upper clamp exists (+48 dB: a carrier band without energy is not
+ * amplified without limit); a silent voice silences the carrier.  depth 0 gives vp_stft_roundtrip's bits of the carrier, and so does
+ * voice == carrier up to rounding.  The stage has no state across frames: streams split into runs as in vp_stft_roundtrip
+ * (vp_stft_set_runs applies).  1024-point frames, every hop, always double (whatever vp_stft_set_precision says), no allocation.
+ * d_voice, d_carrier, d_out: device float [n_streams][n_samples]; d_out must not alias an input (a run re-reads the frames in front of
+ * it).  d_depth: device double [n_streams] or NULL; lifter: VP_FORMANT_LIFTER_MIN .. VP_FORMANT_LIFTER_MAX (callers default it to 32).
+ * VP_ERR_INVALID_ARG (null handle or pointer; lifter out of range) and VP_ERR_GEOMETRY (a 2048-point handle: "2048-point frames are not
+ * built") are reported before the device is touched, in that order; vp_stft_last_error says which under the name "cross". */
+int vp_stft_cross_synth(vp_stft *p, const float *d_voice, const float *d_carrier, float *d_out, const double *d_depth, int lifter, void *hip_stream);
 /* pow(2, st / 12) exactly as vp_stft_pitch_shift / vp_pv_set_semitones compute it (same bits).
  * VP_ERR_INVALID_ARG if an entry is outside +-12 or not finite; nothing is written then.  Host arrays; no device is touched. */
 int vp_semitones_to_ratios(const double *semitones, double *ratios, long n);
@@ -522,6 +538,25 @@ int vp_pv_process_blocks_locked_device(vp_pv *p, const float *d_in, float *d_out
 int vp_pv_process_blocks_formant_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, const double *d_formant, int lifter,
                                         int n_blocks, void *hip_stream);
 long vp_pv_debug_alloc_count(const vp_pv *p);                           /* constant across process calls */
+
+/* Streaming cross-synthesis: vp_stft_cross_synth driven block by block (kernel vp_k_xs_stream).  One handle holds S independent
+ * streams of two inputs each, frame length 1024 (VP_ERR_GEOMETRY otherwise, also for a hop vp_stft_supported(1024, hop) refuses), block
+ * size N >= 1 fixed at create.  Frame grid, latency L = F - gcd(N, hop) and call bookkeeping are vp_pv_*'s: output sample t of a stream is
+ * sample t - L of the one-shot result on everything received, the first L samples are 0, and the concatenated outputs are BIT-IDENTICAL
+ * to vp_stft_cross_synth over every sample emitted however the blocks are grouped into calls.  depth and lifter are the call's (a frame
+ * takes those of the call in which its last sample arrives).  vp_xs_reset takes effect at the next process call and travels in its
+ * arguments; a reset stream behaves like a fresh one, the others are untouched.  Per stream the handle keeps 12 KB of state: samples
+ * received (int64), voice history, carrier history and overlap-add carry (1024 floats each).  Device memory is allocated at create only.
+ * d_voice, d_carrier, d_out: device float [n_blocks][S][N]; d_depth: device double [S] or NULL = 1.  VP_ERR_INVALID_ARG (null pointer,
+ * n_blocks <= 0, lifter outside 4 .. 64, stream out of range) is reported before the device is touched. */
+typedef struct vp_xs vp_xs;
+int vp_xs_create(int device, int n_streams, int block_size, int frame_len, int hop, vp_xs **out);
+int vp_xs_destroy(vp_xs *x);
+int vp_xs_get_latency(const vp_xs *x);                                  /* F - gcd(N, hop) */
+int vp_xs_reset(vp_xs *x, int stream);                                  /* stream -1 = all; takes effect at the next call */
+int vp_xs_process_blocks_device(vp_xs *x, const float *d_voice, const float *d_carrier, float *d_out, const double *d_depth, int lifter,
+                                int n_blocks, void *hip_stream);
+long vp_xs_debug_alloc_count(const vp_xs *x);                           /* constant across process calls; -1 on NULL */
 
 /* Streaming pitch tracker and automatic correction for the stream above (kernels vp_k_yin_track_stream and vp_k_track_follow,
  * csrc/vp_track.hip): vp_stft_track_pitch's decision once per block and stream, from the audio received so far, followed across unvoiced

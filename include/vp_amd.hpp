@@ -452,4 +452,41 @@ private:
     vp_pv *p_ = nullptr;
 };
 
+// vp::StreamingCrossSynth -- the streaming STFT cross-synthesis (vp_xs_*, vp_amd.h): S pairs of voice and carrier, blocks of N samples,
+// state kept across calls.  Output sample t of a stream is sample t - latency() of the one-shot vp_stft_cross_synth on everything the
+// stream received: the carrier with the voice's spectral envelope.
+//
+//     vp::StreamingCrossSynth xs(/*device*/ 0, /*streams*/ 256, /*block*/ 1024);     // hop 256
+//     xs.processBlocksDevice(dVoice, dCarrier, dOut, /*dDepth*/ nullptr, 16);        // device float [16][256][1024] each
+class StreamingCrossSynth {
+public:
+    StreamingCrossSynth(int device, int nStreams, int blockSize, int hop = 256, int frameLen = 1024)
+    {
+        check(vp_xs_create(device, nStreams, blockSize, frameLen, hop, &x_), "vp_xs_create");
+    }
+    ~StreamingCrossSynth() { if (x_) vp_xs_destroy(x_); }
+    StreamingCrossSynth(const StreamingCrossSynth &) = delete;
+    StreamingCrossSynth &operator=(const StreamingCrossSynth &) = delete;
+
+    int latency() const { return vp_xs_get_latency(x_); }
+    // takes effect at the next process call; stream = -1: all streams
+    void reset(int stream = -1) { check(vp_xs_reset(x_, stream), "reset"); }
+    // device float [nBlocks][S][N] each, dOut no alias of an input; dDepth: device double [S] in [0, 1] or null = 1 (0: the carrier's
+    // plain round trip); lifter: the cepstral lifter's length, 4 .. 64 samples; enqueued on hipStream without synchronising
+    void processBlocksDevice(const float *dVoice, const float *dCarrier, float *dOut, const double *dDepth, int nBlocks, int lifter = 32,
+                             void *hipStream = nullptr)
+    {
+        check(vp_xs_process_blocks_device(x_, dVoice, dCarrier, dOut, dDepth, lifter, nBlocks, hipStream), "processBlocksDevice");
+    }
+    long debugAllocCount() const { return vp_xs_debug_alloc_count(x_); }
+    vp_xs *handle() const { return x_; }
+
+private:
+    static void check(int rc, const std::string &what)
+    {
+        if (rc != VP_OK) throw Error(rc, what + ": " + vp_error_string(rc));
+    }
+    vp_xs *x_ = nullptr;
+};
+
 }  // namespace vp

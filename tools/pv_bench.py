@@ -8,6 +8,7 @@
     [VP_AMD_LIB=...] python tools/pv_bench.py --track-stream [--reps 7] [--out profiles/pv_track_stream_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --locked [--reps 7] [--out profiles/pv_lock_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --stretch-locked [--reps 7] [--out profiles/pv_stretch_lock_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --cross [--reps 7] [--out profiles/pv_cross_bench.txt]
 
 --curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
 "steps" curve, fixed, ...): 256 streams x 65 536 samples at 1024 points / hop 256 and 2048 points / hop 512 (vp_stft_pitch_shift against
@@ -42,6 +43,12 @@ streams, 65 536 output samples, 1024 points / hop 256, on noise and on voiced si
 (vp_k_stft_pv_lock) and the new kernel at the identity table f hop on the same input: the ratio is the cost of the positions alone.  Then
 the plain time stretch (vp_k_stft_pv_stretch) and the new kernel at stretch 0.5 and 2, each pair on the same input and table.  The kernels'
 resource listings follow.
+
+--cross: the cross-synthesis (vp_stft_cross_synth, vp_xs_process_blocks_device) beside the kernels it is made of, alternating in one
+process: 256 streams x 65 536 samples, 1024 points / hop 256, voiced voices over sawtooth carriers.  The plain double-precision round trip
+of the carrier (two transforms per frame), the formant kernel on the voice (four, and the phase-vocoder stage), the cross-synthesis (seven),
+and the streaming cross-synthesis, 16 blocks of 1024 per call.  The cross-synthesis's mean over the round trip's and over the formant
+kernel's from the same run are the comparisons; the kernels' resource listings follow.
 """
 import argparse
 import os
@@ -322,6 +329,51 @@ def track_stream_legs(reps, emit):
         h.close()
 
 
+def saw_rows(S, T, fs, seed=12):
+    """--cross's carriers: one sawtooth per stream, 55 .. 220 Hz; float32 [S][T]."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    ph = np.arange(T)[None, :] * (rng.uniform(55.0, 220.0, (S, 1)) / fs)
+    return (0.4 * (2.0 * (ph - np.floor(ph)) - 1.0)).astype(np.float32)
+
+
+def cross_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import CrossSynthStream, StftRoundTrip
+    S, T, F, hop, fs = 256, 65536, 1024, 256, 44100.0
+    v = torch.from_numpy(voiced_rows(S, T, fs)).cuda()
+    c = torch.from_numpy(saw_rows(S, T, fs)).cuda()
+    y = torch.empty_like(c)
+    st = StftRoundTrip(S, T, F, hop)
+    nF = st.n_frames
+    ones = torch.from_numpy(np.ones((S, nF))).cuda()
+    depth = torch.from_numpy(np.ones(S)).cuda()
+    base = "round trip of the carrier, f64"
+    legs = {base: lambda: st(c, y),
+            "formant kernel, ratio 1": lambda: st.pitch_shift_formant(v, y, d_ratio=ones, d_formant=depth),
+            "cross-synthesis": lambda: st.cross_synth(v, c, y, d_depth=depth)}
+    times = alternate(legs, reps, 60)
+    report(f"one-shot, {S} streams x {T} samples of voiced voices over sawtooth carriers, F = {F}, hop = {hop}", times, S * nF, base, emit)
+    mean = {k: sum(t) / len(t) for k, t in times.items()}
+    emit(f"  cross-synthesis = {mean['formant kernel, ratio 1'] / mean['cross-synthesis']:.3f} x the formant kernel (frames/s, the same run)")
+    st.close()
+    N, K = 1024, 16
+    xs = CrossSynthStream(S, N, hop=hop)
+
+    def slab(x):
+        return x[:, :K * N].reshape(S, K, N).permute(1, 0, 2).contiguous()
+    vb, cb = slab(v), slab(c)
+    yb = torch.empty_like(cb)
+    legs = {"streaming cross-synthesis": lambda: xs.process_device(vb, cb, yb, n_blocks=K, d_depth=depth)}
+    stimes = alternate(legs, reps, 300)
+    r = [S * K * N // hop / t / 1e6 for t in stimes["streaming cross-synthesis"]]
+    emit(f"streaming, {S} streams, {K} blocks of {N} per call, hop = {hop}")
+    emit(f"  {'streaming cross-synthesis':<28s} {sum(r) / len(r):8.1f} M frames/s  (min {min(r):.1f}, max {max(r):.1f}, {len(r)} repetitions)  "
+         f"{sum(r) / len(r) / (S * nF / mean['cross-synthesis'] / 1e6):.3f} x the one-shot cross-synthesis")
+    xs.close()
+
+
 def resource_listing(emit, kernels=("vp_k_stft_fused<true, false>", "vp_k_stft_pv_stretch", "vp_k_stft_pv2k", "vp_k_stft_pv2k_stretch")):
     try:
         import kernel_resources
@@ -343,10 +395,11 @@ def main():
     ap.add_argument("--track-stream", action="store_true", help="the streaming-tracker legs instead of the fixed intervals")
     ap.add_argument("--locked", action="store_true", help="the peak-locked legs instead of the fixed intervals")
     ap.add_argument("--stretch-locked", action="store_true", help="the locked time-stretch legs instead of the fixed intervals")
+    ap.add_argument("--cross", action="store_true", help="the cross-synthesis legs instead of the fixed intervals")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="--curve / --stretch / --track: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.stretch_locked:
+    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.stretch_locked and not a.cross:
         return fixed_intervals()
     lines = []
 
@@ -370,6 +423,9 @@ def main():
     if a.stretch_locked:
         stretch_locked_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_stft_pv_lock", "vp_k_stft_pv_stretch", "vp_k_stft_pv_stretch_lock"))
+    if a.cross:
+        cross_legs(max(5, a.reps), emit)
+        resource_listing(emit, ("vp_k_stft_fused<false, false>", "vp_k_stft_pv_formant", "vp_k_stft_cross", "vp_k_xs_stream"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -1997,14 +1997,15 @@ struct PvMode {
     bool locked() const { return kind == LOCKED || kind == STRETCH_LOCKED; }
 };
 
-// the kernel's arguments from the handle; m null: the plain round trip, whose frames split into *nRuns runs per stream
-static VpStftArgs stft_args(const vp_stft *p, const float *d_in, float *d_out, float *d_mag, const PvMode *m, int *nRuns)
+// the kernel's arguments from the handle; m null: the plain round trip, whose frames split into *nRuns runs per stream (f64: in double
+// whatever vp_stft_set_precision says -- the cross-synthesis, which splits the same way)
+static VpStftArgs stft_args(const vp_stft *p, const float *d_in, float *d_out, float *d_mag, const PvMode *m, int *nRuns, bool f64 = false)
 {
     VpStftArgs a;
     memset(&a, 0, sizeof a);
     a.in = d_in; a.out = d_out; a.mag = d_mag; a.win = p->win; a.tw1 = p->tw1; a.tw2 = p->tw2; a.tws = p->tws; a.twTop = p->twTop;
     a.pvRatio = m ? m->ratio : 1.0; a.pv = m ? 1 : 0;
-    a.f32 = (p->f32 && !m) ? 1 : 0;                            // (the phase-vocoder stage keeps double: its phases accumulate over the stream)
+    a.f32 = (p->f32 && !m && !f64) ? 1 : 0;                    // (the phase-vocoder stage keeps double: its phases accumulate over the stream; f64: so does the cross-synthesis)
     a.c = (double)p->scale / (double)(p->F / 2);
     a.T = p->T; a.nFrames = p->nFrames; a.F = p->F; a.hop = p->hop; a.O = p->F / p->hop;
     a.nHops = (p->T + p->hop - 1) / p->hop;
@@ -2135,6 +2136,25 @@ extern "C" int vp_stft_time_stretch_locked(vp_stft *p, const float *d_in, int n_
     const PvMode m = PvMode::stretch_lock(d_ratio, d_pos, n_in);
     return stft_call(p, stft_check(p, "stretch locked", d_in && d_pos && d_out && d_ratio, "null input, position table, output or ratio table", &m),
                      d_in, d_out, nullptr, &m, hip_stream);
+}
+
+// cross-synthesis (vp_k_stft_cross; 1024-point frames): the carrier takes the plain round trip's path -- its runs included, always in
+// double -- with the voice's envelope imposed between the transforms.  Checked before the device is touched, in stft_check's order: handle,
+// pointers, lifter, frame length (the kernel needs no more than the default 64 KB of LDS: the device has no verdict to give)
+extern "C" int vp_stft_cross_synth(vp_stft *p, const float *d_voice, const float *d_carrier, float *d_out, const double *d_depth, int lifter, void *hip_stream)
+{
+    const int rc = stft_check(p, "cross", d_voice && d_carrier && d_out, "null voice, carrier or output", nullptr);
+    if (rc) return rc;
+    if (!lifter_ok(lifter)) { p->lastError = "cross: lifter outside 4 .. 64 samples"; return VP_ERR_INVALID_ARG; }
+    if (p->F != 1024) {
+        p->lastError = "cross: 2048-point frames are not built (the envelope needs a wavefront's exchange buffer to hold the frame's 1025 bins; it holds 1024 doubles)";
+        return VP_ERR_GEOMETRY;
+    }
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    int nRuns;
+    VpStftArgs a = stft_args(p, d_carrier, d_out, nullptr, nullptr, &nRuns, true);
+    if (((uintptr_t)d_voice & 7) != 0) a.aligned = 0;                          // (one flag for both inputs' float2 loads)
+    return vp_stft_launch_cross(a, d_voice, d_depth, lifter, p->S, nRuns, (hipStream_t)hip_stream) == hipSuccess ? VP_OK : VP_ERR_HIP;
 }
 
 extern "C" int vp_stretch_positions(int *pos, int n_frames, int hop, double stretch, int n_in, int frame_len)
@@ -2408,6 +2428,103 @@ extern "C" int vp_pv_process_block(vp_pv *p, const float *in, float *out)
     if (rc) return rc;
     if (hipMemcpyAsync(out, p->stageOut, bytes, hipMemcpyDeviceToHost, p->ownStream) != hipSuccess) return VP_ERR_HIP;
     return hipStreamSynchronize(p->ownStream) == hipSuccess ? VP_OK : VP_ERR_HIP;
+}
+
+// ---- streaming cross-synthesis (no reference counterpart): vp_k_xs_stream of vp_stft_cross.inc, the one-shot stage block by block ------
+struct vp_xs {
+    int device = 0, S = 0, N = 0, F = 0, hop = 0, L = 0;
+    double *win = nullptr, *tw1 = nullptr, *tw2 = nullptr, *tws = nullptr;
+    double c = 0;
+    unsigned char *state = nullptr;             // [S][VP_XS_REC_BYTES] (vp_stft.h)
+    long nAllocs = 0;
+    // resets made since the last process call, as the updates it carries (an all-stream reset clears the per-stream ones)
+    bool allReset = false;
+    std::vector<char> resetPend;                // [S]
+    std::vector<VpPvUpdate> upd;                // staging of the updates (capacity S + 1, reserved at create)
+};
+
+static void xs_free(vp_xs *x)
+{
+    (void)hipFree(x->win); (void)hipFree(x->tw1); (void)hipFree(x->tw2); (void)hipFree(x->tws); (void)hipFree(x->state);
+}
+
+extern "C" int vp_xs_create(int device, int n_streams, int block_size, int frame_len, int hop, vp_xs **out)
+{
+    if (!out || n_streams <= 0 || block_size <= 0 || frame_len <= 0 || hop <= 0) return VP_ERR_INVALID_ARG;
+    if ((long long)n_streams * block_size > (1LL << 28) || (long long)block_size > (1 << 24)) return VP_ERR_INVALID_ARG;
+    if (frame_len != 1024 || !vp_stft_supported(frame_len, hop)) return VP_ERR_GEOMETRY;
+    if (select_device(device)) return VP_ERR_NO_DEVICE;
+    vp_xs *x = new vp_xs();
+    x->device = device; x->S = n_streams; x->N = block_size; x->F = frame_len; x->hop = hop;
+    int g = block_size, b = hop;
+    while (b) { const int t = g % b; g = b; b = t; }
+    x->L = frame_len - g;
+    std::vector<double> w, t1, t2, ts, tt;
+    const float scale = stft_host_tables(frame_len, hop, w, t1, t2, ts, tt);
+    x->c = (double)scale / (double)(frame_len / 2);                      // (as stft_fused)
+    x->resetPend.assign(n_streams, 0);
+    x->upd.reserve(n_streams + 1);
+    // every stream starts with no samples received, zero histories and carry
+    std::vector<unsigned char> rec((size_t)n_streams * VP_XS_REC_BYTES, 0);
+    long *n = &x->nAllocs;
+    const bool ok = put(&x->win, w, n) && put(&x->tw1, t1, n) && put(&x->tw2, t2, n) && put(&x->tws, ts, n)
+        && put((void **)&x->state, rec.data(), rec.size(), n);
+    if (!ok) { xs_free(x); delete x; (void)hipGetLastError(); return VP_ERR_OOM; }
+    *out = x;
+    return VP_OK;
+}
+
+extern "C" int vp_xs_destroy(vp_xs *x)
+{
+    if (!x) return VP_ERR_INVALID_ARG;
+    (void)hipSetDevice(x->device);
+    (void)hipDeviceSynchronize();
+    xs_free(x);
+    delete x;
+    return VP_OK;
+}
+
+extern "C" int vp_xs_get_latency(const vp_xs *x) { return x ? x->L : VP_ERR_INVALID_ARG; }
+extern "C" long vp_xs_debug_alloc_count(const vp_xs *x) { return x ? x->nAllocs : VP_ERR_INVALID_ARG; }
+
+extern "C" int vp_xs_reset(vp_xs *x, int stream)
+{
+    if (!x || stream < -1 || stream >= x->S) return VP_ERR_INVALID_ARG;
+    if (stream < 0) {
+        x->allReset = true;
+        std::fill(x->resetPend.begin(), x->resetPend.end(), 0);
+    } else x->resetPend[stream] = 1;
+    return VP_OK;
+}
+
+// the pending resets travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update launches in front of it), as pv_run's do
+extern "C" int vp_xs_process_blocks_device(vp_xs *x, const float *d_voice, const float *d_carrier, float *d_out, const double *d_depth, int lifter,
+                                           int n_blocks, void *hip_stream)
+{
+    if (!x || !d_voice || !d_carrier || !d_out || n_blocks <= 0 || (long long)n_blocks * x->N > (1 << 28) || !lifter_ok(lifter)) return VP_ERR_INVALID_ARG;
+    if (hipSetDevice(x->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    x->upd.clear();
+    if (x->allReset) x->upd.push_back(VpPvUpdate{-1, 1, 0.0});
+    for (int s = 0; s < x->S; s++)
+        if (x->resetPend[s]) x->upd.push_back(VpPvUpdate{s, 1, 0.0});
+    VpXsArgs a;
+    memset(&a, 0, sizeof a);
+    a.state = x->state; a.win = x->win; a.tw1 = x->tw1; a.tw2 = x->tw2; a.tws = x->tws; a.c = x->c;
+    a.S = x->S; a.N = x->N; a.hop = x->hop; a.L = x->L; a.nc = lifter;
+    size_t i = 0;
+    while (x->upd.size() - i > VP_PV_MAX_UPDATES) {
+        a.nBlocks = 0; a.nUpd = VP_PV_MAX_UPDATES;
+        for (int k = 0; k < VP_PV_MAX_UPDATES; k++) a.upd[k] = x->upd[i + k];
+        if (vp_xs_launch(a, st) != hipSuccess) return VP_ERR_HIP;
+        i += VP_PV_MAX_UPDATES;
+    }
+    a.voice = d_voice; a.carrier = d_carrier; a.out = d_out; a.depth = d_depth; a.nBlocks = n_blocks; a.nUpd = (int)(x->upd.size() - i);
+    for (int k = 0; k < a.nUpd; k++) a.upd[k] = x->upd[i + k];
+    if (vp_xs_launch(a, st) != hipSuccess) return VP_ERR_HIP;
+    x->allReset = false;
+    std::fill(x->resetPend.begin(), x->resetPend.end(), 0);
+    return VP_OK;
 }
 
 // ---- streaming pitch tracker of the phase-vocoder stream (csrc/vp_track.hip): vp_k_yin_track_stream, then vp_k_track_follow -----------

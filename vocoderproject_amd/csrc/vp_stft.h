@@ -56,6 +56,10 @@ size_t vp_stft_lock_lds_bytes(int hop);
 // vp_stft_launch_lock, d_pos and nIn as in vp_stft_launch_stretch; a.F == 1024.  Its dynamic LDS is vp_stft_lock_lds_bytes(a.hop)
 hipError_t vp_stft_launch_stretch_lock(const VpStftArgs &a, const double *d_ratio, const int *d_pos, int nIn, int nStreams, hipStream_t st);
 hipError_t vp_stft_stretch_lock_prepare_device();
+// the 1024-point cross-synthesis build (vp_k_stft_cross; csrc/vp_stft_cross.inc): a.in is the carrier, d_voice [nStreams][a.T] the signal whose
+// spectral envelope it takes, d_depth [nStreams] or nullptr (1), nc the lifter length (4 .. 64); grid = nRuns x nStreams as vp_stft_launch,
+// always double, dynamic LDS vp_stft_lds_bytes(1024, hop) (under 64 KB: no ceiling to raise); a.F == 1024
+hipError_t vp_stft_launch_cross(const VpStftArgs &a, const float *d_voice, const double *d_depth, int nc, int nStreams, int nRuns, hipStream_t st);
 
 // ---- streaming phase vocoder (vp_pv_*): one workgroup per stream and call, state in HBM between calls -----------------------------
 #define VP_PV_MAX_UPDATES 16            // interval changes / resets carried in a process call's arguments
@@ -100,3 +104,27 @@ hipError_t vp_pv_formant_prepare_device();
 hipError_t vp_pv_launch_lock(const VpPvArgs &a, const double *d_ratio, hipStream_t st);
 hipError_t vp_pv_lock_prepare_device();
 size_t vp_pv_lock_lds_bytes();
+
+// ---- streaming cross-synthesis (vp_xs_*): vp_k_pv_stream's bookkeeping with two inputs and no phases (csrc/vp_stft_cross.inc) ------------
+// one stream's state, VP_XS_REC_BYTES each: samples received (int64) | voice history [1024] | carrier history [1024] | overlap-add carry
+// [1024] (floats)
+#define VP_XS_VOICE_BYTES 8
+#define VP_XS_CARRIER_BYTES (VP_XS_VOICE_BYTES + 1024 * 4)
+#define VP_XS_CARRY_BYTES (VP_XS_CARRIER_BYTES + 1024 * 4)
+#define VP_XS_REC_BYTES (VP_XS_CARRY_BYTES + 1024 * 4)
+
+struct VpXsArgs {
+    const float *voice, *carrier;       // [nBlocks][S][N]
+    float *out;                         // [nBlocks][S][N]
+    unsigned char *state;               // [S][VP_XS_REC_BYTES]
+    const double *win, *tw1, *tw2, *tws;   // the one-shot's tables (VpStftArgs)
+    const double *depth;                // [S] or nullptr (1)
+    double c;                           // the one-shot's normalisation
+    int S, N, nBlocks, hop, L, nc;      // streams, block, blocks in this call, hop, latency F - gcd(N, hop), lifter length
+    int nUpd;
+    VpPvUpdate upd[VP_PV_MAX_UPDATES];  // pending resets (ratio 0)
+};
+
+size_t vp_xs_lds_bytes();
+// the streaming kernel (grid = S workgroups); nBlocks = 0 launches the small kernel that only applies the resets
+hipError_t vp_xs_launch(const VpXsArgs &a, hipStream_t st);

@@ -1119,5 +1119,8 @@ hipError_t vp_pv_launch(const VpPvArgs &a, hipStream_t st)
 // ---- the peak-locked kernel with frames analysed at caller-given positions: the locked time stretch (vp_stft_time_stretch_locked) ----
 #include "vp_stft_stretch_lock.inc"
 
+// ---- cross-synthesis: the voice's spectral envelope on the carrier (vp_stft_cross_synth, vp_xs_process_blocks_device) ----
+#include "vp_stft_cross.inc"
+
 // ---- the ratio-curve kernels with the cepstral formant correction (vp_stft_pitch_shift_formant, vp_pv_process_blocks_formant_device) ----
 #include "vp_stft_formant.inc"

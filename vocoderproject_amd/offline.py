@@ -17,6 +17,7 @@ There is no CPU path here either: without a GPU the processor raises.
     python -m vocoderproject_amd.offline stretch a.wav b.wav --stretch 1.5 [--shift 3] [--locked] --out-dir out/   (time stretch, one-shot phase vocoder)
     python -m vocoderproject_amd.offline pvtune a.wav b.wav --key 0 --out-dir out/ [--track-csv]        (pitch tracker + phase-vocoder correction)
     python -m vocoderproject_amd.offline pvtune a.wav --stream [--block 256 --hold 8 --glide 0.5] --out-dir out/   (... block by block: the streaming tracker)
+    python -m vocoderproject_amd.offline pvcross voice.wav [more.wav] --carrier synth.wav [--depth D] [--lifter N] [--stream --block N] [--hop H] --out-dir out/   (STFT cross-synthesis)
 """
 import argparse
 import os
@@ -513,6 +514,69 @@ def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glid
     return _tune(p, voices, lens, T, fs, keys, _mode_kw(formant, lifter, locked), lat, with_track)
 
 
+class _CrossRunner:
+    """StftRoundTrip.cross_synth from host arrays: voice, carrier float32 [S][T], depth [S] -> float32 [S][T]."""
+
+    def __init__(self, F, hop, device):
+        self.F, self.hop, self.device = int(F), int(hop), device
+
+    def run(self, v, c, depth, lifter):
+        import torch
+        d_c = torch.from_numpy(np.ascontiguousarray(c, np.float32)).to(torch.device("cuda", self.device))
+
+        def call(st, d_in, d_out):
+            st.cross_synth(d_in, d_c, d_out, depth=depth, lifter=int(lifter))
+        return _one_shot(v, v.shape[1], self.F, self.hop, self.device, call)[0]
+
+
+def _pack_carriers(carriers, S, lens, T):
+    """One carrier for every voice or one per voice -> float32 [S][T]: row s is the carrier cut to voice s's length, silence behind."""
+    many = isinstance(carriers, (list, tuple))
+    cs = list(carriers) if many else [carriers]
+    if len(cs) == 1:
+        cs = cs * S
+    if len(cs) != S:
+        raise ValueError("carrier: one for all voices or one per voice expected")
+    c = np.zeros((S, int(T)), np.float32)
+    for s, a in enumerate(cs):
+        a = np.asarray(a, np.float32)
+        if a.ndim != 1:
+            raise ValueError(f"carrier {s}: expected a mono signal, got shape {a.shape}")
+        n = min(a.size, lens[s])
+        c[s, :n] = a[:n]
+    return c
+
+
+def pv_cross(voices, carriers, depth=1.0, lifter=32, F=1024, hop=256, N=1024, stream=False, blocks_per_call=16, device=0, processor=None):
+    """STFT cross-synthesis of a batch (one stream per voice): every voice's spectral envelope on its carrier.  carriers: one mono signal for
+    all voices or a list with one per voice; a carrier shorter than its voice is padded with silence, a longer one is cut to the voice.
+    depth: 0 (the carrier unchanged) .. 1 (the voice's envelope in full), one value or one per voice; lifter: the cepstral lifter, 4 .. 64
+    samples.  Batch (default): the one-shot call StftRoundTrip.cross_synth on the recordings padded to a common length under the full
+    overlap of 1024-point frames; stream: block by block through CrossSynthStream.run, its latency taken off.  Returns float32 [2][len]
+    per voice (the signal on both channels).  `processor` (tests): an object with run(voice, carrier, depth, lifter) (batch) or
+    run(voice, carrier, blocks_per_call, depth, lifter) (stream) to use instead of the GPU."""
+    S = _batch_size(voices)
+    per = _per_recording(depth, S, "depth", float, 0.0, 1.0, "depth: values within [0, 1] expected")
+    if not 4 <= int(lifter) <= 64:
+        raise ValueError("lifter: 4 to 64 samples expected")
+    if int(F) != 1024:
+        raise ValueError("pvcross: 1024-point frames expected (the cross-synthesis kernels are not built for 2048)")
+    hop = int(hop)
+    lens = _lengths(voices)
+    T = max(lens) if stream else 1024 + -(-max(lens) // hop) * hop             # (batch: every sample under the full overlap of frames)
+    v = _pack_mono(voices, lens, T)
+    c = _pack_carriers(carriers, S, lens, T)
+    if stream:
+        if processor is None:
+            from . import CrossSynthStream
+            processor = CrossSynthStream(S, int(N), hop=hop, device=device)
+        y = processor.run(v, c, blocks_per_call=int(blocks_per_call), depth=per, lifter=int(lifter))
+    else:
+        p = processor if processor is not None else _CrossRunner(F, hop, device)
+        y = p.run(v, c, per, int(lifter))
+    return _both_channels(y, lens)
+
+
 def write_track_csv(path, fs, hop, period, ratio, n_samples=None):
     """One recording's track: a line per frame with its start time in seconds, the period in samples (0 = unvoiced) and the correction in
     semitones (12 log2 ratio); n_samples: only the frames that start inside the recording."""
@@ -528,10 +592,10 @@ def write_track_csv(path, fs, hop, period, ratio, n_samples=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m vocoderproject_amd.offline", description=__doc__.split("\n\n")[0])
-    ap.add_argument("flow", choices=["pitch", "vocode", "both", "pvshift", "stretch", "pvtune"])
+    ap.add_argument("flow", choices=["pitch", "vocode", "both", "pvshift", "stretch", "pvtune", "pvcross"])
     ap.add_argument("inputs", nargs="+", help="voice recordings (WAV; channel 0 is used, like the notebook)")
     ap.add_argument("--carrier", action="append", default=None,
-                    help="side-chain recording(s) for vocode/both: one for all voices or one per voice")
+                    help="side-chain recording(s) for vocode/both, carrier(s) for pvcross (channel 0): one for all voices or one per voice")
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--key", type=int, default=12, help="keyPitch 0..12 (12 = chromatic, the plugin's default)")
     ap.add_argument("--shift", type=float, default=None, help="fixed interval in semitones instead of the key correction")
@@ -547,7 +611,8 @@ def main(argv=None):
     ap.add_argument("--locked", action="store_true",
                     help="pvshift (--shift or --glide), pvtune [--stream], stretch: the peak-locked phase vocoder -- a spectral peak's whole region moves "
                          "and turns as one, so tones keep their level (1024-point frames; not together with --formant)")
-    ap.add_argument("--lifter", type=int, default=32, help="--formant: length of the cepstral lifter in samples, 4 to 64 (short: a smoother envelope)")
+    ap.add_argument("--depth", type=float, default=1.0, help="pvcross: 0 (the carrier unchanged) to 1 (the voice's spectral envelope in full)")
+    ap.add_argument("--lifter", type=int, default=32, help="--formant, pvcross: length of the cepstral lifter in samples, 4 to 64 (short: a smoother envelope)")
     ap.add_argument("--hold", type=int, default=0, help="pvtune --stream: unvoiced blocks over which the last voiced ratio is kept")
     ap.add_argument("--stretch", type=float, default=None, help="stretch: output duration / input duration, 0.25 to 4 (--shift: semitones on top)")
     ap.add_argument("--frame", type=int, default=1024, help="stretch, pvtune: frame length (1024 or 2048)")
@@ -565,6 +630,11 @@ def main(argv=None):
             argv[i:i + 2] = ["--glide=" + argv[i + 1]]
             break
     a = ap.parse_args(argv)
+    if a.flow == "pvcross":
+        for flag, given in (("--formant", a.formant is not None), ("--locked", a.locked), ("--shift", a.shift is not None), ("--glide", a.glide is not None),
+                            ("--stretch", a.stretch is not None)):
+            if given:
+                raise SystemExit(f"{flag}: pvcross does not take it (the cross-synthesis moves neither pitch nor time)")
     if a.formant is not None and a.flow not in ("pvshift", "pvtune"):
         raise SystemExit("--formant: pvshift and pvtune take it")
     if a.locked and a.flow not in ("pvshift", "pvtune", "stretch"):
@@ -580,6 +650,19 @@ def main(argv=None):
     if any(r[0] != fs for r in recs):
         raise SystemExit("all recordings of a batch must share one sample rate (one prepareToPlay)")
     voices = [r[1][0] for r in recs]
+    if a.flow == "pvcross":
+        if not a.carrier:
+            raise SystemExit("pvcross needs --carrier")
+        cs = [read_wav(f) for f in a.carrier]
+        if any(c[0] != fs for c in cs):
+            raise SystemExit("carrier sample rate differs from the voices'")
+        if len(cs) not in (1, len(voices)):
+            raise SystemExit("--carrier: give one, or one per voice")
+        try:
+            outs = pv_cross(voices, [c[1][0] for c in cs], depth=a.depth, lifter=a.lifter, hop=a.hop, N=a.block, stream=a.stream, device=a.device)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        return _write_outputs(a, fs, outs)
     if a.flow == "stretch":
         if a.stretch is None:
             raise SystemExit("stretch needs --stretch FACTOR")

@@ -177,6 +177,15 @@ def load_library():
         L.vp_stft_autotune_formant.argtypes = [vp, fp, fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.vp_pv_process_blocks_formant_device.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.vp_pv_autotune_blocks_formant_device.argtypes = [vp, vp, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "vp_stft_cross_synth"):              # (the cross-synthesis entries; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_stft_cross_synth.argtypes = [vp, fp, fp, fp, C.c_void_p, C.c_int, C.c_void_p]
+        L.vp_xs_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.vp_xs_destroy.argtypes = [vp]
+        L.vp_xs_get_latency.argtypes = [vp]
+        L.vp_xs_reset.argtypes = [vp, C.c_int]
+        L.vp_xs_process_blocks_device.argtypes = [vp, fp, fp, fp, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.vp_xs_debug_alloc_count.argtypes = [vp]
+        L.vp_xs_debug_alloc_count.restype = C.c_long
     L.vp_error_string.argtypes = [C.c_int]
     L.vp_error_string.restype = C.c_char_p
     L.vp_last_error.argtypes = [vp]
@@ -615,6 +624,44 @@ def _device_formants(owner, formant_semitones, d_formant, dev):
     return owner._formant_table
 
 
+def _cross_check(d_voice, d_carrier, d_out, shape, lifter):
+    """The contract of a cross-synthesis call, before anything is launched: three float32 device tensors of `shape`, contiguous, the output
+    no alias of an input; the lifter within its range.  ValueError otherwise."""
+    torch = _T or _torch()
+    for name, t in (("voice", d_voice), ("carrier", d_carrier), ("output", d_out)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError(f"cross_synth: {name}: a contiguous float32 tensor on the GPU expected")
+    if tuple(d_voice.shape) != tuple(d_carrier.shape):
+        raise ValueError(f"cross_synth: voice {tuple(d_voice.shape)} and carrier {tuple(d_carrier.shape)} differ in shape")
+    for name, t in (("voice", d_voice), ("output", d_out)):
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"cross_synth: {name}: shape {tuple(shape)} expected, got {tuple(t.shape)}")
+    if d_out.data_ptr() in (d_voice.data_ptr(), d_carrier.data_ptr()):
+        raise ValueError("cross_synth: the output must not alias an input")
+    if not 4 <= int(lifter) <= 64:
+        raise ValueError("cross_synth: lifter: 4 to 64 samples expected")
+
+
+def _device_depths(owner, depth, d_depth, dev):
+    """The depth table of a cross-synthesis call: a device float64 tensor [S] as it is; host values (a scalar or S values, each finite) go
+    into one device table kept on `owner` (owner._depth_table), rewritten on torch's current stream.  The kernel clamps to [0, 1].
+    Neither (depth None): None, the library's NULL -- depth 1 everywhere."""
+    torch = _T or _torch()
+    if depth is None and d_depth is None:
+        return None
+    if d_depth is not None:
+        if not _is(d_depth, torch.float64, (owner.S,)):
+            raise ValueError(f"cross_synth: d_depth: a contiguous float64 tensor [{owner.S}] on the GPU expected")
+        return d_depth
+    d = np.asarray(depth, dtype=np.float64)
+    if d.shape not in ((), (owner.S,)) or not np.all(np.isfinite(d)):
+        raise ValueError(f"cross_synth: depth: one finite value or {owner.S} of them expected")
+    if getattr(owner, "_depth_table", None) is None:
+        owner._depth_table = torch.empty((owner.S,), dtype=torch.float64, device=dev)
+    owner._depth_table.copy_(torch.from_numpy(np.array(np.broadcast_to(d, (owner.S,)))))
+    return owner._depth_table
+
+
 class StftRoundTrip:
     """Standalone batched STFT -> iSTFT (no reference counterpart; see include/vp_amd.h vp_stft_*)."""
 
@@ -723,6 +770,18 @@ class StftRoundTrip:
         d_formant = _device_formants(self, formant_semitones, d_formant, d_in.device)
         self._track_chk(self.L.vp_stft_pitch_shift_formant(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), d_formant.data_ptr(), int(lifter),
                                                            _stream_of(stream, d_in)))
+
+    def cross_synth(self, d_voice, d_carrier, d_out, depth=1.0, lifter=FORMANT_LIFTER, stream=None, d_depth=None):
+        """STFT cross-synthesis (vp_stft_cross_synth; 1024-point frames): the spectral envelope of d_voice imposed on d_carrier, frame by
+        frame -- the carrier's bins times exp(min(depth (env voice - env carrier), ln 256)) with pitch_shift_formant's cepstral envelope
+        (the definition is tests/pv_cross_reference.py).  d_voice, d_carrier, d_out: device float32 [S][n_samples], the output no alias of
+        an input.  depth: 0 (the carrier's plain round trip, bit for bit) .. 1, a scalar or [S] values, None for the library's NULL table (1
+        everywhere); d_depth instead: a device float64 tensor [S], used as it is (the kernel clamps to [0, 1]).  lifter: the cepstral lifter, 4 .. 64 samples.  Always double precision;
+        set_runs applies.  Wrong dtypes, shapes or lifter raise ValueError before any launch; a 2048-point handle raises VpError."""
+        _cross_check(d_voice, d_carrier, d_out, (self.S, self.T), lifter)
+        d_depth = _device_depths(self, depth, d_depth, d_voice.device)
+        self._track_chk(self.L.vp_stft_cross_synth(self.h, d_voice.data_ptr(), d_carrier.data_ptr(), d_out.data_ptr(), _ptr(d_depth), int(lifter),
+                                                   _stream_of(stream, d_voice)))
 
     def _position_table(self, positions, stretch, d_pos, n_in, dev):
         """The checked device position table [S][n_frames] of a time-stretch call: d_pos as it is, or host data -- `stretch` through
@@ -1019,6 +1078,91 @@ class PhaseVocoderStream:
     def close(self):
         if getattr(self, "h", None):
             self.L.vp_pv_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CrossSynthStream:
+    """Streaming STFT cross-synthesis: `n_streams` independent pairs of voice and carrier, blocks of `block_size` samples, state kept
+    across calls (include/vp_amd.h vp_xs_*).  Output sample t of a stream is sample t - latency of what StftRoundTrip.cross_synth gives
+    on everything the stream has received, bit for bit; the first `latency` samples are 0."""
+
+    def __init__(self, n_streams, block_size, hop=256, frame_len=1024, device=0):
+        try:
+            import torch  # noqa: F401  (run() and process_device() use torch: load its HIP runtime before the library loads one)
+        except ImportError:
+            pass
+        self.L = load_library()
+        h = C.c_void_p()
+        rc = self.L.vp_xs_create(int(device), int(n_streams), int(block_size), int(frame_len), int(hop), C.byref(h))
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+        self.h, self.S, self.N, self.hop, self.F, self.device = h, int(n_streams), int(block_size), int(hop), int(frame_len), device
+
+    def _chk(self, rc):
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+
+    @property
+    def latency(self):
+        """F - gcd(N, hop) samples."""
+        return self.L.vp_xs_get_latency(self.h)
+
+    def reset(self, stream=-1):
+        """The stream (-1: all) starts again like a fresh one at the next process call."""
+        self._chk(self.L.vp_xs_reset(self.h, int(stream)))
+
+    def process_device(self, d_voice, d_carrier, d_out, n_blocks=1, depth=1.0, lifter=FORMANT_LIFTER, stream=None, d_depth=None):
+        """n_blocks blocks on the device: torch float32 [n_blocks][S][N] each (or [S][N] for one block), enqueued on `stream` (default: the
+        current torch stream) without synchronising.  depth, d_depth, lifter: as StftRoundTrip.cross_synth's, for the frames this call
+        completes.  Wrong dtypes, shapes or lifter raise ValueError before any launch."""
+        n = int(n_blocks)
+        if n < 1:
+            raise ValueError("cross_synth: at least one block expected")
+        shape = (self.S, self.N) if n == 1 and d_voice.dim() == 2 else (n, self.S, self.N)
+        _cross_check(d_voice, d_carrier, d_out, shape, lifter)
+        d_depth = _device_depths(self, depth, d_depth, d_voice.device)
+        self._chk(self.L.vp_xs_process_blocks_device(self.h, d_voice.data_ptr(), d_carrier.data_ptr(), d_out.data_ptr(), _ptr(d_depth), int(lifter), n,
+                                                     _stream_of(stream, d_voice)))
+
+    def run(self, voice, carrier, blocks_per_call=8, depth=1.0, lifter=FORMANT_LIFTER):
+        """Whole signals float [S][T] each -> output aligned with the inputs, [S][T]: the inputs padded with `latency` zeros (and up to
+        whole blocks), streamed through process_device `blocks_per_call` blocks at a time, the first `latency` samples dropped.  Continues
+        from the handle's state (reset() first for a fresh start)."""
+        import torch
+        v, c = np.asarray(voice, dtype=np.float32), np.asarray(carrier, dtype=np.float32)
+        if v.ndim != 2 or v.shape[0] != self.S or v.shape != c.shape:
+            raise ValueError(f"cross_synth: voice {v.shape} and carrier {c.shape}: two arrays [{self.S}][T] expected")
+        if not 4 <= int(lifter) <= 64:
+            raise ValueError("cross_synth: lifter: 4 to 64 samples expected")
+        T, Lat, N = v.shape[1], self.latency, self.N
+        nb = -(-(T + Lat) // N)
+        dev = torch.device("cuda", self.device)
+
+        def slab(x):
+            xp = np.zeros((self.S, nb * N), np.float32)
+            xp[:, :T] = x
+            return torch.from_numpy(np.ascontiguousarray(xp.reshape(self.S, nb, N).transpose(1, 0, 2))).to(dev)
+        d_v, d_c = slab(v), slab(c)
+        d_out = torch.empty_like(d_v)
+        for b in range(0, nb, int(blocks_per_call)):
+            k = min(int(blocks_per_call), nb - b)
+            self.process_device(d_v[b:b + k], d_c[b:b + k], d_out[b:b + k], n_blocks=k, depth=depth, lifter=lifter)
+        torch.cuda.synchronize(dev)
+        y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, nb * N)
+        return np.ascontiguousarray(y[:, Lat:Lat + T])
+
+    def debug_alloc_count(self):
+        return self.L.vp_xs_debug_alloc_count(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vp_xs_destroy(self.h)
             self.h = None
 
     def __del__(self):
