@@ -366,12 +366,25 @@ int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d_out, const
  *   theta[k] = th[own[k]] for every k.  A frame without peaks (all zeros) gives Y = 0 and leaves theta.
  * A region is translated whole: at r > 1 the gaps stay empty, at r < 1 neighbouring regions are cut where they meet, not added.  At
  * r = 1 the stage is the identity.  1024-point frames, every hop, always double, one workgroup per stream, no allocation.
- * Out of scope: 2048-point frames; formant correction on top of locking; fractional-bin interpolation of the offset (the integer offset
- * is why a tone at -12 semitones loses level); adding overlapping regions; several voices per call.  Locking in the time stretch is
- * vp_stft_time_stretch_locked.
+ * Out of scope: 2048-point frames; formant correction on top of locking; adding overlapping regions; several voices per call.  The
+ * integer offset costs level (a 0.5 tone leaves at 0.38 at -12 and at +7 semitones): vp_stft_pitch_shift_locked_subbin interpolates.
+ * Locking in the time stretch is vp_stft_time_stretch_locked.
  * VP_ERR_INVALID_ARG (null handle, input, output or ratio table) and VP_ERR_GEOMETRY (a 2048-point handle) are reported before the
  * device is touched and vp_stft_last_error says which; VP_ERR_HIP as vp_stft_pitch_shift. */
 int vp_stft_pitch_shift_locked(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream);
+/* vp_stft_pitch_shift_locked with SUB-BIN region offsets (kernel vp_k_stft_pv_lockf; the definition is tests/pv_lockf_reference.py).  The
+ * locked stage moves a region by an integer while its angle turns at the true frequency, so the lobe sits up to half a bin (plus the
+ * peak's own sub-bin position) from the frequency its phase turns at, and frames do not add up in the overlap-add.  Here peaks,
+ * ownership, th[P], P', theta and silent frames are the locked stage's; what changes, with m the magnitudes:
+ *   per peak P: delta = 0 if P is 0 or 512, else (m[P-1] - m[P+1]) / (2 (m[P-1] - 2 m[P] + m[P+1])), in [-1/2, 1/2];  D = (P + delta)(r - 1);
+ *   synthesis bin kk (its shifted peak P', its peak P):  u = kk - D, u0 = floor(u), f = u - u0;  f == 0: the one tap k = u0, weight 1;
+ *     else six taps k_j = u0 + j, j = -2 .. 3, w_j = sinc(f - j) (1/2 + 1/2 cos(pi (f - j) / 3));  a tap counts if 0 <= k_j <= 512 and
+ *     own[k_j] == P;  Y[kk] = exp(2 pi i th[P]) sum_j w_j (-1)^(kk - k_j) X[k_j];  bins 0 and 512 keep their real parts.
+ * At r = 1 the stage is the identity.  A 0.5 tone leaves at 0.486 - 0.498 where the integer offset gives 0.38 - 0.50
+ * (profiles/pv_lockf_quality.txt).  1024-point frames, every hop, always double, one workgroup per stream, no allocation.  Out of
+ * scope: the locked time stretch (it keeps integer offsets), 2048-point frames, formant correction on top, adding overlapping regions,
+ * single precision.  Arguments, checks, their order and codes as vp_stft_pitch_shift_locked's; the texts begin "locked subbin: ". */
+int vp_stft_pitch_shift_locked_subbin(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream);
 /* vp_stft_pitch_shift_curve with the spectral envelope kept apart from the pitch (kernel vp_k_stft_pv_formant): the formants stay where
  * they were, or move by a ratio of their own, while the pitch follows d_ratio.  The definition is tests/pv_formant_reference.py.  Per
  * frame, with m the analysis magnitudes, r the frame's pitch ratio and phi the stream's formant ratio (both clamped to [0.5, 2] as in
@@ -530,6 +543,11 @@ int vp_pv_process_blocks_curve_device(vp_pv *p, const float *d_in, float *d_out,
  * formant calls may follow each other on one handle: they share the two arrays, so after a change of kind the output is defined and
  * finite but carries a phase jump -- a caller who minds that resets the stream (vp_pv_reset) at the change.  No allocation. */
 int vp_pv_process_blocks_locked_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream);
+/* vp_pv_process_blocks_locked_device with vp_stft_pitch_shift_locked_subbin's stage (kernel vp_k_pv_stream_lockf): table, record, state
+ * arrays, latency, bookkeeping, checks and codes are the locked call's.  The output, less the latency, is bit-identical to
+ * vp_stft_pitch_shift_locked_subbin on the concatenated input with the table expanded per frame.  Sub-bin, locked, curve, plain and
+ * formant calls may follow each other on one handle under the locked call's rule.  No allocation. */
+int vp_pv_process_blocks_locked_subbin_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream);
 /* vp_pv_process_blocks_curve_device with vp_stft_pitch_shift_formant's correction (kernel vp_k_pv_stream_formant): d_formant device
  * double [S] or NULL = 1.0, lifter as there (VP_ERR_INVALID_ARG outside 4 .. 64, before the device is touched).  The stream's state
  * record, latency and call bookkeeping are the curve call's, so formant, curve and plain calls mix freely on one handle; pending resets

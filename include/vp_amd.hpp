@@ -420,6 +420,12 @@ public:
     {
         check(vp_pv_process_blocks_locked_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksLocked");
     }
+    // processBlocksLocked with sub-bin region offsets (vp_pv_process_blocks_locked_subbin_device): a region is translated by the
+    // real-valued offset of its peak's interpolated centre and the spectrum interpolated, so a shifted tone keeps its level
+    void processBlocksLockedSubbin(const float *dIn, float *dOut, const double *dRatio, int nBlocks, void *hipStream = nullptr)
+    {
+        check(vp_pv_process_blocks_locked_subbin_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksLockedSubbin");
+    }
     // automatic correction: the tracker's call, then processBlocksCurve along its table (dRatio: result and scratch, required; dPeriod
     // may be null), on one stream.  The tracker must have this shifter's streams, block size and device.  reset() does not reach it.
     void autotuneBlocks(StreamingPitchTracker &tracker, const float *dIn, float *dOut, const int *dKey, int *dPeriod, double *dRatio, int nBlocks,

@@ -8,6 +8,7 @@
     [VP_AMD_LIB=...] python tools/pv_bench.py --track-stream [--reps 7] [--out profiles/pv_track_stream_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --locked [--reps 7] [--out profiles/pv_lock_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --stretch-locked [--reps 7] [--out profiles/pv_stretch_lock_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --locked-subbin [--reps 7] [--out profiles/pv_lockf_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --cross [--reps 7] [--out profiles/pv_cross_bench.txt]
 
 --curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
@@ -37,6 +38,12 @@ time per call against the sum of its parts'.
 copied from, alternating in one process on the SAME "steps" table: one-shot, 256 streams x 65 536 samples, 1024 points / hop 256, on noise
 and on voiced signals (the stage's mask searches depend on how far apart the peaks are); then streaming, 16 blocks of 1024 per call.  The
 locked kernel's mean over the curve kernel's from the same run is the comparison; the kernels' resource listings follow.
+
+--locked-subbin: the peak-locked builds with sub-bin region offsets (vp_stft_pitch_shift_locked_subbin,
+vp_pv_process_blocks_locked_subbin_device) beside the integer-offset locked kernels they were copied from, alternating in one process on the
+SAME "steps" table: one-shot, 256 streams x 65 536 samples, 1024 points / hop 256, on noise and on voiced signals; then streaming, 16 blocks
+of 1024 per call, on both.  The sub-bin kernel's mean over the integer kernel's from the same run is the comparison; the kernels' resource
+listings follow.
 
 --stretch-locked: the locked time stretch (vp_stft_time_stretch_locked) beside both of its parents, alternating in one process: 256
 streams, 65 536 output samples, 1024 points / hop 256, on noise and on voiced signals, every call at +7 semitones.  The locked pitch shift
@@ -166,6 +173,36 @@ def locked_legs(reps, emit):
     legs = {base: lambda: a.process_device(xb, yb, n_blocks=K, d_ratio=steps),
             "locked, steps": lambda: b.process_device(xb, yb, n_blocks=K, d_ratio=steps, locked=True)}
     report(f"streaming, {S} streams, {K} blocks of {N} per call of noise, hop = {hop}", alternate(legs, reps, 300), S * K * N // hop, base, emit)
+    a.close()
+    b.close()
+
+
+def locked_subbin_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import PhaseVocoderStream, StftRoundTrip, semitones_to_ratios
+    S, T, F, hop, fs = 256, 65536, 1024, 256, 44100.0
+    rng = np.random.default_rng(9)
+    st = StftRoundTrip(S, T, F, hop)
+    nF = st.n_frames
+    steps = torch.from_numpy(semitones_to_ratios(rng.uniform(-12.0, 12.0, (S, nF)))).cuda()
+    base, new = "locked, steps (parent kernel)", "locked sub-bin, steps"
+    inputs = (("noise", torch.randn(S, T, device="cuda", dtype=torch.float32) * 0.1), ("voiced signals", torch.from_numpy(voiced_rows(S, T, fs)).cuda()))
+    for what, x in inputs:
+        y = torch.empty_like(x)
+        legs = {base: lambda x=x, y=y: st.pitch_shift_locked(x, y, d_ratio=steps),
+                new: lambda x=x, y=y: st.pitch_shift_locked(x, y, d_ratio=steps, subbin=True)}
+        report(f"one-shot, {S} streams x {T} samples of {what}, F = {F}, hop = {hop}", alternate(legs, reps, 100), S * nF, base, emit)
+    st.close()
+    N, K = 1024, 16
+    a, b = PhaseVocoderStream(S, N, hop=hop), PhaseVocoderStream(S, N, hop=hop)
+    steps = torch.from_numpy(semitones_to_ratios(rng.uniform(-12.0, 12.0, (K, S)))).cuda()
+    for what, x in inputs:
+        xb = x[:, :K * N].reshape(S, K, N).transpose(0, 1).contiguous()
+        yb = torch.empty_like(xb)
+        legs = {base: lambda xb=xb, yb=yb: a.process_device(xb, yb, n_blocks=K, d_ratio=steps, locked=True),
+                new: lambda xb=xb, yb=yb: b.process_device(xb, yb, n_blocks=K, d_ratio=steps, locked=True, subbin=True)}
+        report(f"streaming, {S} streams, {K} blocks of {N} per call of {what}, hop = {hop}", alternate(legs, reps, 300), S * K * N // hop, base, emit)
     a.close()
     b.close()
 
@@ -394,12 +431,13 @@ def main():
     ap.add_argument("--track", action="store_true", help="the pitch-tracker legs instead of the fixed intervals")
     ap.add_argument("--track-stream", action="store_true", help="the streaming-tracker legs instead of the fixed intervals")
     ap.add_argument("--locked", action="store_true", help="the peak-locked legs instead of the fixed intervals")
+    ap.add_argument("--locked-subbin", action="store_true", help="the sub-bin peak-locked legs instead of the fixed intervals")
     ap.add_argument("--stretch-locked", action="store_true", help="the locked time-stretch legs instead of the fixed intervals")
     ap.add_argument("--cross", action="store_true", help="the cross-synthesis legs instead of the fixed intervals")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="--curve / --stretch / --track: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.stretch_locked and not a.cross:
+    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.locked_subbin and not a.stretch_locked and not a.cross:
         return fixed_intervals()
     lines = []
 
@@ -420,6 +458,9 @@ def main():
     if a.locked:
         locked_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_stft_pv_curve", "vp_k_stft_pv_lock", "vp_k_pv_stream_curve", "vp_k_pv_stream_lock"))
+    if a.locked_subbin:
+        locked_subbin_legs(max(5, a.reps), emit)
+        resource_listing(emit, ("vp_k_stft_pv_lock", "vp_k_stft_pv_lockf", "vp_k_pv_stream_lock", "vp_k_pv_stream_lockf"))
     if a.stretch_locked:
         stretch_locked_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_stft_pv_lock", "vp_k_stft_pv_stretch", "vp_k_stft_pv_stretch_lock"))

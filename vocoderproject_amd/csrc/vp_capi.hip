@@ -1905,7 +1905,8 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     // THAT call; the plain and single-precision round trips (<= 64 KB) are served regardless.  The sticky HIP error is cleared so
     // that a later hipGetLastError() behind a launch does not report this one.
     p->pvOk = vp_stft_prepare_device() == hipSuccess && vp_stft_curve_prepare_device() == hipSuccess && vp_stft_stretch_prepare_device() == hipSuccess
-        && vp_stft_formant_prepare_device() == hipSuccess && vp_stft_lock_prepare_device() == hipSuccess && vp_stft_stretch_lock_prepare_device() == hipSuccess;
+        && vp_stft_formant_prepare_device() == hipSuccess && vp_stft_lock_prepare_device() == hipSuccess && vp_stft_stretch_lock_prepare_device() == hipSuccess
+        && vp_stft_lockf_prepare_device() == hipSuccess;
     if (!p->pvOk) (void)hipGetLastError();
     p->device = device; p->F = frame_len; p->hop = hop; p->S = n_streams; p->T = n_samples;
     p->nFrames = (n_samples - frame_len) / hop + 1;
@@ -1979,7 +1980,7 @@ extern "C" int vp_stft_get_precision(const vp_stft *p) { return p ? (p->f32 ? VP
 // are the only places that fill one, and there is none for a combination that no kernel serves (a formant correction on a locked call,
 // a position table on a formant call).
 struct PvMode {
-    enum Kind { FIXED, CURVE, LOCKED, FORMANT, STRETCH, STRETCH_LOCKED } kind = FIXED;
+    enum Kind { FIXED, CURVE, LOCKED, LOCKED_SUBBIN, FORMANT, STRETCH, STRETCH_LOCKED } kind = FIXED;
     double semitones = 0.0, ratio = 1.0;   // FIXED, STRETCH: the caller's interval and its ratio (a streaming call reads the ratios its records hold)
     const double *ratioTab = nullptr;   // every other kind: one-shot [S][nFrames], streaming [n_blocks][S]
     const int *posTab = nullptr;        // STRETCH, STRETCH_LOCKED: frame f of stream s is read at input sample posTab[s][f] ...
@@ -1991,10 +1992,11 @@ struct PvMode {
     static PvMode fixed(double semitones) { PvMode m; m.semitones = semitones; m.ratio = std::pow(2.0, semitones / 12.0); return m; }
     static PvMode curve(const double *tab) { PvMode m; m.kind = CURVE; m.ratioTab = tab; return m; }
     static PvMode lock(const double *tab) { PvMode m; m.kind = LOCKED; m.ratioTab = tab; return m; }
+    static PvMode lock_subbin(const double *tab) { PvMode m; m.kind = LOCKED_SUBBIN; m.ratioTab = tab; return m; }
     static PvMode form(const double *tab, const double *formant, int lifter) { PvMode m; m.kind = FORMANT; m.ratioTab = tab; m.formant = formant; m.lifter = lifter; return m; }
     static PvMode stretch(double semitones, const int *pos, int nIn) { PvMode m = fixed(semitones); m.kind = STRETCH; m.posTab = pos; m.nIn = nIn; return m; }
     static PvMode stretch_lock(const double *tab, const int *pos, int nIn) { PvMode m; m.kind = STRETCH_LOCKED; m.ratioTab = tab; m.posTab = pos; m.nIn = nIn; return m; }
-    bool locked() const { return kind == LOCKED || kind == STRETCH_LOCKED; }
+    bool locked() const { return kind == LOCKED || kind == LOCKED_SUBBIN || kind == STRETCH_LOCKED; }
 };
 
 // the kernel's arguments from the handle; m null: the plain round trip, whose frames split into *nRuns runs per stream (f64: in double
@@ -2037,6 +2039,7 @@ static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
     case PvMode::FIXED: e = vp_stft_launch(a, p->S, nRuns, st); break;
     case PvMode::CURVE: e = vp_stft_launch_curve(a, m->ratioTab, p->S, st); break;
     case PvMode::LOCKED: e = vp_stft_launch_lock(a, m->ratioTab, p->S, st); break;
+    case PvMode::LOCKED_SUBBIN: e = vp_stft_launch_lockf(a, m->ratioTab, p->S, st); break;
     case PvMode::FORMANT: e = vp_stft_launch_formant(a, m->ratioTab, m->formant, m->lifter, p->S, st); break;
     case PvMode::STRETCH: e = vp_stft_launch_stretch(a, m->posTab, m->nIn, p->S, st); break;
     case PvMode::STRETCH_LOCKED: e = vp_stft_launch_stretch_lock(a, m->ratioTab, m->posTab, m->nIn, p->S, st); break;
@@ -2110,6 +2113,14 @@ extern "C" int vp_stft_pitch_shift_locked(vp_stft *p, const float *d_in, float *
 {
     const PvMode m = PvMode::lock(d_ratio);
     return stft_call(p, stft_check(p, "locked", d_in && d_out && d_ratio, "null input, output or ratio table", &m), d_in, d_out, nullptr, &m, hip_stream);
+}
+
+// vp_stft_pitch_shift_locked with SUB-BIN region offsets (vp_k_stft_pv_lockf; 1024-point frames): a peak's region is translated by the
+// real-valued offset of its interpolated centre and the spectrum interpolated; arguments, checks and codes as the locked entry's
+extern "C" int vp_stft_pitch_shift_locked_subbin(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream)
+{
+    const PvMode m = PvMode::lock_subbin(d_ratio);
+    return stft_call(p, stft_check(p, "locked subbin", d_in && d_out && d_ratio, "null input, output or ratio table", &m), d_in, d_out, nullptr, &m, hip_stream);
 }
 
 // vp_stft_pitch_shift_curve with the cepstral formant correction: d_formant [S] formant ratios or NULL (1.0: the envelope stays where it
@@ -2277,7 +2288,7 @@ extern "C" int vp_pv_create(int device, int n_streams, int block_size, int frame
     if (frame_len != 1024 || !vp_stft_supported(frame_len, hop)) return VP_ERR_GEOMETRY;
     if (select_device(device)) return VP_ERR_NO_DEVICE;
     if (vp_pv_prepare_device() != hipSuccess || vp_pv_curve_prepare_device() != hipSuccess || vp_pv_formant_prepare_device() != hipSuccess
-        || vp_pv_lock_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
+        || vp_pv_lock_prepare_device() != hipSuccess || vp_pv_lockf_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
     vp_pv *p = new vp_pv();
     p->device = device; p->S = n_streams; p->N = block_size; p->F = frame_len; p->hop = hop;
     int g = block_size, b = hop;
@@ -2376,6 +2387,7 @@ static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipSt
     case PvMode::FIXED: e = vp_pv_launch(a, st); break;
     case PvMode::CURVE: e = vp_pv_launch_curve(a, m.ratioTab, st); break;
     case PvMode::LOCKED: e = vp_pv_launch_lock(a, m.ratioTab, st); break;
+    case PvMode::LOCKED_SUBBIN: e = vp_pv_launch_lockf(a, m.ratioTab, st); break;
     case PvMode::FORMANT: e = vp_pv_launch_formant(a, m.ratioTab, m.formant, m.lifter, st); break;
     case PvMode::STRETCH: case PvMode::STRETCH_LOCKED: return VP_ERR_INVALID_ARG;          // (no entry makes one: the stream has no time stretch)
     }
@@ -2409,6 +2421,12 @@ extern "C" int vp_pv_process_blocks_curve_device(vp_pv *p, const float *d_in, fl
 extern "C" int vp_pv_process_blocks_locked_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream)
 {
     return pv_call(p, d_in, d_out, d_ratio != nullptr, n_blocks, PvMode::lock(d_ratio), hip_stream);
+}
+
+// the locked call with sub-bin region offsets (vp_k_pv_stream_lockf): arguments, checks, codes and state as the locked call's
+extern "C" int vp_pv_process_blocks_locked_subbin_device(vp_pv *p, const float *d_in, float *d_out, const double *d_ratio, int n_blocks, void *hip_stream)
+{
+    return pv_call(p, d_in, d_out, d_ratio != nullptr, n_blocks, PvMode::lock_subbin(d_ratio), hip_stream);
 }
 
 // the curve call with the cepstral formant correction (vp_k_pv_stream_formant): d_formant [S] or NULL (1.0), lifter in samples

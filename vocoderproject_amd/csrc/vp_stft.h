@@ -52,6 +52,11 @@ hipError_t vp_stft_formant_prepare_device();
 hipError_t vp_stft_launch_lock(const VpStftArgs &a, const double *d_ratio, int nStreams, hipStream_t st);
 hipError_t vp_stft_lock_prepare_device();
 size_t vp_stft_lock_lds_bytes(int hop);
+// the peak-locked build with sub-bin region offsets (vp_k_stft_pv_lockf; csrc/vp_stft_lockf.inc): arguments and dynamic LDS as
+// vp_stft_launch_lock's (the offsets lie in free slots of the locked stage's rows)
+hipError_t vp_stft_launch_lockf(const VpStftArgs &a, const double *d_ratio, int nStreams, hipStream_t st);
+hipError_t vp_stft_lockf_prepare_device();
+size_t vp_stft_lockf_lds_bytes(int hop);
 // the peak-locked build with frames at given positions (vp_k_stft_pv_stretch_lock; csrc/vp_stft_stretch_lock.inc): d_ratio as in
 // vp_stft_launch_lock, d_pos and nIn as in vp_stft_launch_stretch; a.F == 1024.  Its dynamic LDS is vp_stft_lock_lds_bytes(a.hop)
 hipError_t vp_stft_launch_stretch_lock(const VpStftArgs &a, const double *d_ratio, const int *d_pos, int nIn, int nStreams, hipStream_t st);
@@ -104,6 +109,10 @@ hipError_t vp_pv_formant_prepare_device();
 hipError_t vp_pv_launch_lock(const VpPvArgs &a, const double *d_ratio, hipStream_t st);
 hipError_t vp_pv_lock_prepare_device();
 size_t vp_pv_lock_lds_bytes();
+// ... and with sub-bin region offsets (vp_k_pv_stream_lockf): state, record and LDS as the locked call's
+hipError_t vp_pv_launch_lockf(const VpPvArgs &a, const double *d_ratio, hipStream_t st);
+hipError_t vp_pv_lockf_prepare_device();
+size_t vp_pv_lockf_lds_bytes();
 
 // ---- streaming cross-synthesis (vp_xs_*): vp_k_pv_stream's bookkeeping with two inputs and no phases (csrc/vp_stft_cross.inc) ------------
 // one stream's state, VP_XS_REC_BYTES each: samples received (int64) | voice history [1024] | carrier history [1024] | overlap-add carry

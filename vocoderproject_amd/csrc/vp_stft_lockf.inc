@@ -1,90 +1,35 @@
-// vp_stft_lock.inc -- the phase-vocoder kernels with PEAK LOCKING (included by vp_stft.hip behind vp_stft_curve.inc: its helpers, tables,
-// carves and pv_curve_clamp).
+// vp_stft_lockf.inc -- the peak-locked phase-vocoder kernels with SUB-BIN region offsets (enters vp_stft.hip behind vp_stft_lock.inc, from
+// that file's last line: its carve, masks, pv_lock_nearest, pv_lock_bin and pv_lock_turn).
 //
-// The plain stage moves every bin on its own and runs one phase accumulator per synthesis bin: a sinusoid's main lobe is torn apart and
-// its bins lose the phase relation that makes them one windowed sinusoid.  Here (Laroche & Dolson 1999, identity locking with integer
-// offsets; the definition is tests/pv_lock_reference.py) the frame's spectral peaks are found, every bin belongs to its nearest peak, and
-// a peak's whole region is translated by ONE integer offset floor(P r + 0.5) - P and rotated by ONE angle, the peak's accumulated
-// theta[P] + nu[P] (r - 1) / O, wrapped every frame.  The synthesis is a gather with one source per bin; the angle of a region is handed to
-// all of its bins, so that a peak that moves to a neighbouring bin continues the angle of the region it was in.
+// The locked stage moves a peak's region by the integer floor(P r + 0.5) - P while its angle advances at the true frequency: the lobe
+// sits up to half a bin, plus the peak's own sub-bin position, from the frequency its phase turns at, and successive frames do not add
+// up in the overlap-add (a 0.5 tone leaves at 0.38).  Here (Laroche & Dolson's remedy; the definition is tests/pv_lockf_reference.py)
+// the peak's centre c = P + delta is the vertex of the parabola through its three linear magnitudes, the region is translated by the
+// real-valued D = c (r - 1), and the spectrum is interpolated at u = kk - D with six taps of a Hann-tapered sinc,
 //
-// vp_k_stft_pv_lock and vp_k_pv_stream_lock are WRITTEN-OUT COPIES of vp_k_stft_pv_curve and vp_k_pv_stream_curve (docs/HISTORY.md, "One
+//     Y[kk] = exp(2 pi i th[P]) sum_j w_j (-1)^(kk - k_j) X[k_j],   k_j = floor(u) + j,  j = -2 .. 3,  own[k_j] == P.
+//
+// With f = u - floor(u): sinc(f - j) = (-1)^j sin(pi f) / (pi (f - j)), and (-1)^(kk - k_j) = (-1)^(kk - floor(u)) (-1)^j, so the two
+// alternations cancel and what is left per bin is ONE sign, ONE sin(pi f), and per tap the taper over f - j.  The taper's angle
+// pi (f - j) / 3 is pi f / 3 less a constant: one sincos and angle addition.  The six 1 / (f - j) come from one division (prefix and
+// suffix products).  f == 0 is the single tap of weight 1 (the identity at r = 1, where D is exactly 0).
+//
+// vp_k_stft_pv_lockf and vp_k_pv_stream_lockf are WRITTEN-OUT COPIES of vp_k_stft_pv_lock and vp_k_pv_stream_lock (docs/HISTORY.md, "One
 // phase-vocoder stage for both kernels", for why copies): framing, transforms, ratio table, overlap-add, state record and bookkeeping are
-// the parents', statement for statement.  The stage between split and merge is replaced; what differs is marked "lock:".
+// the parents', statement for statement.  What differs is marked "lockf:".
 //
-// State: theta lives where the parents keep the synthesis accumulator (PvLds::sum, the record's second array) and the previous frame's
-// phases where they keep them (phPrev), so plain, curve, formant and locked calls may follow each other on one streaming handle; after a
-// change of kind the output is defined and finite but carries a phase jump.
+// State: as the parents' (phPrev, theta in PvLds::sum), so sub-bin, locked, curve, plain and formant calls may follow each other on one
+// streaming handle; after a change of kind the output is defined and finite but carries a phase jump.
 //
-// lock: LDS on top of the parents' carve, per wavefront: the two 513-bit masks (peaks, shifted peaks) as nine 64-bit words each, the owner
-// of every bin and the map from a shifted peak back to its peak.  The wavefront's `ana` row holds the complex spectrum (not magnitude and
-// frequency), its `inc` row the magnitudes and then, at peaks, the angle's advance.
-#define PV_LOCK_WORDS 10                                                       // nine used; ten keeps the int arrays 16-byte aligned
-#define PV_LOCK_INTS 520                                                       // 513 used
-#define PV_LOCK_WV_BYTES (2 * PV_LOCK_WORDS * 8 + 2 * PV_LOCK_INTS * 4)
-__host__ __device__ constexpr size_t pv_lock_lds_bytes() { return (size_t)NWV * PV_LOCK_WV_BYTES; }
+// lockf: LDS is the parents', byte for byte.  D of a peak P < N lies in the wavefront's `inc` row at P + 1: peaks are at least three bins
+// apart, so the slot is no peak's, and pv_lock_turn reads the row at peaks only.  P == N has delta = 0 and D = N (r - 1), formed where
+// it is used.
 
-typedef __attribute__((address_space(3))) unsigned long long lds_u64;
-typedef __attribute__((address_space(3))) int lds_i32;
-
-struct PvLockLds {
-    lds_u64 *peaks;            // [9] bit k & 63 of word k >> 6: bin k is a peak of this wavefront's frame
-    lds_u64 *moved;            // [9] ... is a shifted peak P'
-    lds_i32 *own;              // [513] the peak that owns bin k
-    lds_i32 *back;             // [513] P' -> P, -1 elsewhere
-};
-__device__ __forceinline__ PvLockLds pv_lock_carve(lds_f64 *p, int wv)
-{
-    PvLockLds l;
-    lds_u64 *w = (lds_u64 *)p + (size_t)wv * (PV_LOCK_WV_BYTES / 8);
-    l.peaks = w; l.moved = w + PV_LOCK_WORDS;
-    l.own = (lds_i32 *)(w + 2 * PV_LOCK_WORDS); l.back = l.own + PV_LOCK_INTS;
-    return l;
-}
-
-// bin e of the lane's nine: even e the pair's k = 64 (e / 2) + lane, odd e its mirror 512 - k, e = 8 bin 256 (lane 0 only)
-__device__ __forceinline__ int pv_lock_bin(int e, int lane) { return e == 8 ? 256 : (e & 1) ? 512 - (64 * (e >> 1) + lane) : 64 * (e >> 1) + lane; }
-
-// The 513-bit mask of a per-bin flag from its nine ballots (bal[e]: bit `lane` is the flag of bin pv_lock_bin(e, lane)), written by lane 0.
-// The pairs' words are the ballots; a mirror ballot reversed and moved up by one is bins 512 - 64 q - lane, lane = 1 .. 63, of word 7 - q,
-// and its lane 0 is bit 0 of word 8 - q.
-__device__ __forceinline__ void pv_lock_mask(lds_u64 *W, const unsigned long long (&bal)[9], bool lane0)
-{
-    if (!lane0) return;
-#pragma unroll
-    for (int q = 0; q < 4; q++) W[q] = bal[2 * q];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const unsigned long long below = q < 3 ? bal[2 * q + 3] : bal[8];      // bin 64 (7 - q): lane 0 of the next mirror, or bin 256
-        W[7 - q] = (__builtin_bitreverse64(bal[2 * q + 1]) << 1) | (below & 1ull);
-    }
-    W[8] = bal[1] & 1ull;
-}
-
-// the set bit of the mask nearest to bin k (0 .. 512), the lower one on equal distance; -1 if the mask is empty
-__device__ __forceinline__ int pv_lock_nearest(const lds_u64 *W, int k)
-{
-    const int wi = k >> 6, b = k & 63;
-    const unsigned long long w0 = W[wi];
-    unsigned long long x = w0 & (~0ull >> (63 - b));                           // bits 0 .. b
-    int j = wi;
-    while (x == 0ull && j > 0) x = W[--j];
-    const int lo = x ? 64 * j + 63 - __builtin_clzll(x) : -1;
-    x = b == 63 ? 0ull : w0 & (~0ull << (b + 1));                              // bits b + 1 .. 63
-    j = wi;
-    while (x == 0ull && j < 8) x = W[++j];
-    const int hi = x ? 64 * j + __builtin_ctzll(x) : -1;
-    if (lo < 0) return hi;
-    if (hi < 0) return lo;
-    return (k - lo <= hi - k) ? lo : hi;
-}
-
-// lock: everything of the stage in front of the turns, by one live wavefront: magnitudes, phases and the spectrum to LDS are the caller's
-// (before its barrier); here peaks, owners, the peaks' advance of the angle (into the wavefront's `inc` row), the shifted peaks and the
-// gather's indices.  own[e]: the peak that owns the lane's bin e; src[e]: the source bin of synthesis bin e or -1 (zero); pk[e]: the peak
-// whose angle rotates it.  Returns whether the frame has a peak (wavefront-uniform).
-__device__ __forceinline__ bool pv_lock_plan(const PvLds &pv, const PvLockLds &lk, int wv, int prevSlot, int ln, bool lane0, double ratio, double invO, int O,
-                                             int (&own)[9], int (&src)[9], int (&pk)[9])
+// lockf: pv_lock_plan with the peak's offset: own[e], pk[e] as there; src[e] is 0 where synthesis bin e has a region (a shifted peak is
+// left), else -1 (zero).  The parabola's three magnitudes are read before the row is overwritten: a peak's neighbours are no peaks, so
+// only this lane writes P and P + 1.
+__device__ __forceinline__ bool pv_lockf_plan(const PvLds &pv, const PvLockLds &lk, int wv, int prevSlot, int ln, bool lane0, double ratio, double invO, int O,
+                                              int (&own)[9], int (&src)[9], int (&pk)[9])
 {
     constexpr int N = 512, nb = N + 1;
     lds_f64 *mrow = pv.inc + wv * nb;
@@ -114,6 +59,15 @@ __device__ __forceinline__ bool pv_lock_plan(const PvLds &pv, const PvLockLds &l
     for (int e = 0; e < 9; e++) {
         if (!isPk[e]) continue;
         const int k = pv_lock_bin(e, ln);
+        // lockf: the centre of the peak and its region's offset
+        if (k < N) {
+            double delta = 0.0;
+            if (k > 0) {
+                const double a = mrow[k - 1], c = mrow[k], b = mrow[k + 1];
+                delta = fmin(fmax(0.5 * (a - b) / (a - 2.0 * c + b), -0.5), 0.5);
+            }
+            mrow[k + 1] = ((double)k + delta) * (ratio - 1.0);
+        }
         double d = pv.phPrev[(wv + 1) * nb + k] - pv.phPrev[prevSlot * nb + k] - (double)k * invO;
         d -= rint(d);
         const double nu = (double)k + d * (double)O;
@@ -139,47 +93,62 @@ __device__ __forceinline__ bool pv_lock_plan(const PvLds &pv, const PvLockLds &l
         for (int e = 0; e < 9; e++) {
             const int kk = pv_lock_bin(e, ln);
             const int ps = pv_lock_nearest(lk.moved, kk);
-            const int pa = lk.back[ps];
-            const int k = kk - (ps - pa);
-            pk[e] = pa;
-            src[e] = (k >= 0 && k <= N && lk.own[min(max(k, 0), N)] == pa) ? k : -1;
+            pk[e] = lk.back[ps];
+            src[e] = 0;                                                        // lockf: the taps are chosen in the gather
         }
     }
     return true;
 }
 
-// lock: a wavefront's turn at theta (pv.sum), in frame order between the caller's barriers: every bin takes its owner's new angle; then
-// the angles that rotate the lane's synthesis bins are read back (theta[P] of a peak is its own new angle).
-__device__ __forceinline__ void pv_lock_turn(const PvLds &pv, int wv, int ln, bool lane0, const int (&own)[9], const int (&src)[9], const int (&pk)[9], double (&th)[9])
+// lockf: the interpolating gather: synthesis bin e of the lane is the six-tap interpolation of the wavefront's spectrum at kk - D over
+// the bins its peak owns, rotated by th[e]; or zero
+__device__ __forceinline__ void pv_lockf_gather(const PvLds &pv, const PvLockLds &lk, int wv, int ln, bool lane0, double ratio, const int (&src)[9],
+                                                const int (&pk)[9], const double (&th)[9], RPairs &X)
 {
-    constexpr int nb = 513;
-    double t[9];
-#pragma unroll
-    for (int e = 0; e < 9; e++) {
-        t[e] = pv.sum[own[e]] + pv.inc[wv * nb + own[e]];
-        t[e] -= rint(t[e]);
-    }
-    wave_sync();                                                               // (other lanes read theta[P] of bins this lane overwrites)
-#pragma unroll
-    for (int e = 0; e < 9; e++) if (e < 8 || lane0) pv.sum[pv_lock_bin(e, ln)] = t[e];
-    wave_sync();
-#pragma unroll
-    for (int e = 0; e < 9; e++) th[e] = src[e] >= 0 ? pv.sum[pk[e]] : 0.0;
-}
-
-// lock: the gather: synthesis bin e of the lane is its source bin of the wavefront's spectrum rotated by th[e], or zero
-__device__ __forceinline__ void pv_lock_gather(const PvLds &pv, bool lane0, const int (&src)[9], const double (&th)[9], RPairs &X)
-{
+    constexpr int N = 512, nb = N + 1;
+    // cos and sin of pi j / 3, j = -2 .. 3
+    constexpr double H3 = 0.8660254037844386;
+    constexpr double CJ[6] = {-0.5, 0.5, 1.0, 0.5, -0.5, -1.0}, SJ[6] = {-H3, -H3, 0.0, H3, H3, 0.0};
 #pragma unroll
     for (int e = 0; e < 9; e++) {
         if (e == 8 && !lane0) continue;
         double re = 0.0, im = 0.0;
         if (src[e] >= 0) {
-            const d2 x = pv.ana[src[e]];
+            const int kk = pv_lock_bin(e, ln), pa = pk[e];
+            const double D = pa < N ? pv.inc[wv * nb + pa + 1] : (double)N * (ratio - 1.0);
+            const double u = (double)kk - D, uf = floor(u), f = u - uf;        // |u| < 1024
+            const int u0 = (int)uf;
+            double w[6] = {0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+            if (f != 0.0) {
+                double s1, c1, s3, c3;
+                pv_sincos_turns(0.5 * f, s1, c1);                              // sin(pi f)
+                pv_sincos_turns(f * (1.0 / 6.0), s3, c3);                      // (sin, cos)(pi f / 3)
+                double a[6], pre[6], run = 1.0;
+#pragma unroll
+                for (int j = 0; j < 6; j++) { a[j] = f - (double)(j - 2); pre[j] = run; run *= a[j]; }
+                double suf = 0.3183098861837907 * s1 / run;                    // sin(pi f) / pi over the product of all six
+#pragma unroll
+                for (int j = 5; j >= 0; j--) {
+                    // taper 1/2 + 1/2 cos(pi (f - j) / 3) by angle addition
+                    w[j] = (0.5 + 0.5 * __builtin_fma(c3, CJ[j], s3 * SJ[j])) * (pre[j] * suf);
+                    suf *= a[j];
+                }
+            }
+            double ar = 0.0, ai = 0.0;
+#pragma unroll
+            for (int j = 0; j < 6; j++) {
+                const int kj = u0 + j - 2;
+                if (kj >= 0 && kj <= N && lk.own[kj] == pa) {
+                    const d2 x = pv.ana[kj];
+                    ar = __builtin_fma(w[j], x.x, ar);
+                    ai = __builtin_fma(w[j], x.y, ai);
+                }
+            }
+            if ((kk - u0) & 1) { ar = -ar; ai = -ai; }                         // the one sign left of (-1)^(kk - k_j) and the sinc's own
             double sn, cs;
             pv_sincos_turns(th[e], sn, cs);
-            re = __builtin_fma(x.x, cs, -(x.y * sn));
-            im = __builtin_fma(x.x, sn, x.y * cs);
+            re = __builtin_fma(ar, cs, -(ai * sn));
+            im = __builtin_fma(ar, sn, ai * cs);
         }
         if (e == 8) { X.hr = re; X.hi = im; }
         else if (e & 1) { X.mr[e >> 1] = re; X.mi[e >> 1] = im; }
@@ -188,7 +157,7 @@ __device__ __forceinline__ void pv_lock_gather(const PvLds &pv, bool lane0, cons
     if (lane0) { X.ki[0] = 0.0; X.mi[0] = 0.0; }
 }
 
-__global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_lock(VpStftArgs A, const double *ratioTab)
+__global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_lockf(VpStftArgs A, const double *ratioTab)
 {
     extern __shared__ double smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -199,7 +168,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_lock(VpStftArgs A, cons
     lds_f32 *slots = (lds_f32 *)smem;
     lds_f32 *carry = (lds_f32 *)smem + NWV * 2048;                             // [(O - 1) hop]
     const PvLds pv = pv_lds_carve((lds_f64 *)smem + stft_lds_base(F, hop) / 8, wv);
-    const PvLockLds lk = pv_lock_carve((lds_f64 *)smem + (stft_lds_base(F, hop) + pv_lds_bytes()) / 8, wv);   // lock:
+    const PvLockLds lk = pv_lock_carve((lds_f64 *)smem + (stft_lds_base(F, hop) + pv_lds_bytes()) / 8, wv);
 #ifdef VP_POISON_LDS
     for (int i = tid; i < (int)((stft_lds_base(F, hop) + pv_lds_bytes() + pv_lock_lds_bytes()) / 8); i += 64 * NWV) ((lds_f64 *)smem)[i] = __builtin_nan("0x5a5a");
     __syncthreads();
@@ -246,14 +215,14 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_lock(VpStftArgs A, cons
             rfft_split(z, xb, lane, (const d2 *)ws, X);
         }
         {
-            // ---- lock: the peak-locked stage, phases in TURNS (to the merge)
+            // ---- the peak-locked stage, phases in TURNS (to the merge)
             const int nb = N + 1;
             const double invO = 1.0 / (double)O;
-            // lock: (the lane number through a register the compiler cannot see through: vp_k_stft_pv2k)
+            // (the lane number through a register the compiler cannot see through: vp_k_stft_pv2k)
             int ln = lane;
             asm volatile("" : "+v"(ln));
             if (live) {
-                // lock: spectrum, magnitude and phase of the lane's bins, straight to LDS
+                // spectrum, magnitude and phase of the lane's bins, straight to LDS
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const int k = 64 * q + ln, m = N - k;
@@ -269,8 +238,8 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_lock(VpStftArgs A, cons
             __syncthreads();
             int own[9], src[9], pk[9];
             bool has = false;
-            if (live) has = pv_lock_plan(pv, lk, wv, wv, ln, lane0, ratio, invO, O, own, src, pk);
-            // lock: theta is handed through the round in frame order, in place
+            if (live) has = pv_lockf_plan(pv, lk, wv, wv, ln, lane0, ratio, invO, O, own, src, pk);   // lockf:
+            // theta is handed through the round in frame order, in place
             double th[9];
 #pragma unroll
             for (int e = 0; e < 9; e++) th[e] = 0.0;
@@ -279,7 +248,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_lock(VpStftArgs A, cons
                 if (w > 0) __syncthreads();
                 if (live && has && wv == w) pv_lock_turn(pv, wv, ln, lane0, own, src, pk, th);
             }
-            if (live) pv_lock_gather(pv, lane0, src, th, X);
+            if (live) pv_lockf_gather(pv, lk, wv, ln, lane0, ratio, src, pk, th, X);                  // lockf:
             // (every live wavefront is past its reads of the previous frame's phases: the turns' barriers, or program order when the
             // round's only live wavefront is wavefront 0)
             const int lastLive = min(NWV - 1, A.nFrames - 1 - rd * NWV);
@@ -291,7 +260,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_lock(VpStftArgs A, cons
                     pv.phPrev[k] = pv.phPrev[(wv + 1) * nb + k];
                 }
             }
-            // ---- lock: end of the stage
+            // ---- end of the stage
         }
         lds_f2 *slot = (lds_f2 *)(slots + wv * 2048);
         if (live) {
@@ -310,9 +279,9 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_lock(VpStftArgs A, cons
     }
 }
 
-// ---- streaming: vp_k_pv_stream_curve with the locked stage.  theta is the record's second array, handed from the call's first live frame
+// ---- streaming: vp_k_pv_stream_lock with the sub-bin stage.  theta is the record's second array, handed from the call's first live frame
 // to its last whatever their wavefronts.
-__global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lock(VpPvArgs A, const double *ratioTab)
+__global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lockf(VpPvArgs A, const double *ratioTab)
 {
     extern __shared__ double smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -324,7 +293,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lock(VpPvArgs A, cons
     lds_f32 *ring = (lds_f32 *)smem + NWV * 2048;                              // [VP_PV_RING]
     lds_f32 *hist = ring + VP_PV_RING;                                         // [F]
     const PvLds pv = pv_lds_carve((lds_f64 *)(hist + F), wv);
-    const PvLockLds lk = pv_lock_carve((lds_f64 *)smem + pv_stream_lds_bytes() / 8, wv);   // lock:
+    const PvLockLds lk = pv_lock_carve((lds_f64 *)smem + pv_stream_lds_bytes() / 8, wv);
 #ifdef VP_POISON_LDS
     for (int i = tid; i < (int)((pv_stream_lds_bytes() + pv_lock_lds_bytes()) / 8); i += 64 * NWV) ((lds_f64 *)smem)[i] = __builtin_nan("0x5a5a");
     __syncthreads();
@@ -408,7 +377,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lock(VpPvArgs A, cons
             rfft_split(z, xb, lane, (const d2 *)ws, X);
         }
         {
-            // ---- lock: the peak-locked stage (vp_k_stft_pv_lock's), to the merge
+            // ---- the peak-locked stage (vp_k_stft_pv_lockf's), to the merge
             const double invO = 1.0 / (double)O;
             const int prevSlot = wv == wFirst ? 0 : wv;
             int ln = lane;
@@ -429,8 +398,8 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lock(VpPvArgs A, cons
             __syncthreads();
             int own[9], src[9], pk[9];
             bool has = false;
-            if (live) has = pv_lock_plan(pv, lk, wv, prevSlot, ln, lane0, ratio, invO, O, own, src, pk);
-            // lock: theta continues from the state at the call's first live frame and is left by its last
+            if (live) has = pv_lockf_plan(pv, lk, wv, prevSlot, ln, lane0, ratio, invO, O, own, src, pk);   // lockf:
+            // theta continues from the state at the call's first live frame and is left by its last
             double th[9];
 #pragma unroll
             for (int e = 0; e < 9; e++) th[e] = 0.0;
@@ -439,7 +408,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lock(VpPvArgs A, cons
                 if (w > 0) __syncthreads();
                 if (live && has && wv == w) pv_lock_turn(pv, wv, ln, lane0, own, src, pk, th);
             }
-            if (live) pv_lock_gather(pv, lane0, src, th, X);
+            if (live) pv_lockf_gather(pv, lk, wv, ln, lane0, ratio, src, pk, th, X);                        // lockf:
             if (live && wv == wLast) {
 #pragma unroll
                 for (int e = 0; e < 9; e++) {
@@ -448,7 +417,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lock(VpPvArgs A, cons
                     pv.phPrev[k_] = pv.phPrev[(wv + 1) * nb + k_];
                 }
             }
-            // ---- lock: end of the stage
+            // ---- end of the stage
         }
         lds_f2 *slot = (lds_f2 *)(slots + wv * 2048);
         if (live) {
@@ -488,32 +457,28 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lock(VpPvArgs A, cons
     if (tid == 0) { recD[VP_PV_RATIO] = recRatio; ((long long *)recD)[VP_PV_COUNT] = R; }
 }
 
-hipError_t vp_stft_lock_prepare_device()
+hipError_t vp_stft_lockf_prepare_device()
 {
-    return hipFuncSetAttribute((const void *)vp_k_stft_pv_lock, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+    return hipFuncSetAttribute((const void *)vp_k_stft_pv_lockf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
 }
 
-size_t vp_stft_lock_lds_bytes(int hop) { return stft_lds_base(1024, hop) + pv_lds_bytes() + pv_lock_lds_bytes(); }
-size_t vp_pv_lock_lds_bytes() { return pv_stream_lds_bytes() + pv_lock_lds_bytes(); }
+size_t vp_stft_lockf_lds_bytes(int hop) { return vp_stft_lock_lds_bytes(hop); }                       // lockf: no row of its own
+size_t vp_pv_lockf_lds_bytes() { return vp_pv_lock_lds_bytes(); }
 
-hipError_t vp_stft_launch_lock(const VpStftArgs &a, const double *d_ratio, int nStreams, hipStream_t st)
+hipError_t vp_stft_launch_lockf(const VpStftArgs &a, const double *d_ratio, int nStreams, hipStream_t st)
 {
     const dim3 grid(1, nStreams), block(64 * NWV);                             // (one run: theta is a recurrence over the stream's frames)
-    hipLaunchKernelGGL(vp_k_stft_pv_lock, grid, block, vp_stft_lock_lds_bytes(a.hop), st, a, d_ratio);
+    hipLaunchKernelGGL(vp_k_stft_pv_lockf, grid, block, vp_stft_lockf_lds_bytes(a.hop), st, a, d_ratio);
     return hipGetLastError();
 }
 
-hipError_t vp_pv_lock_prepare_device()
+hipError_t vp_pv_lockf_prepare_device()
 {
-    return hipFuncSetAttribute((const void *)vp_k_pv_stream_lock, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+    return hipFuncSetAttribute((const void *)vp_k_pv_stream_lockf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
 }
 
-hipError_t vp_pv_launch_lock(const VpPvArgs &a, const double *d_ratio, hipStream_t st)
+hipError_t vp_pv_launch_lockf(const VpPvArgs &a, const double *d_ratio, hipStream_t st)
 {
-    hipLaunchKernelGGL(vp_k_pv_stream_lock, dim3(a.S), dim3(64 * NWV), vp_pv_lock_lds_bytes(), st, a, d_ratio);
+    hipLaunchKernelGGL(vp_k_pv_stream_lockf, dim3(a.S), dim3(64 * NWV), vp_pv_lockf_lds_bytes(), st, a, d_ratio);
     return hipGetLastError();
 }
-
-// ---- the same kernels with sub-bin region offsets (vp_stft_pitch_shift_locked_subbin, vp_pv_process_blocks_locked_subbin_device): a
-// part of this family, so it enters vp_stft.hip here, behind everything above
-#include "vp_stft_lockf.inc"

@@ -15,6 +15,7 @@ There is no CPU path here either: without a GPU the processor raises.
     python -m vocoderproject_amd.offline pvshift a.wav b.wav --shift 7 --out-dir out/     (streaming phase vocoder)
     python -m vocoderproject_amd.offline pvshift a.wav --glide -12:12 --out-dir out/      (... along a glide, one interval per block)
     python -m vocoderproject_amd.offline stretch a.wav b.wav --stretch 1.5 [--shift 3] [--locked] --out-dir out/   (time stretch, one-shot phase vocoder)
+    python -m vocoderproject_amd.offline pvshift a.wav --shift -12 --locked --subbin --out-dir out/   (peak locking with sub-bin region offsets)
     python -m vocoderproject_amd.offline pvtune a.wav b.wav --key 0 --out-dir out/ [--track-csv]        (pitch tracker + phase-vocoder correction)
     python -m vocoderproject_amd.offline pvtune a.wav --stream [--block 256 --hold 8 --glide 0.5] --out-dir out/   (... block by block: the streaming tracker)
     python -m vocoderproject_amd.offline pvcross voice.wav [more.wav] --carrier synth.wav [--depth D] [--lifter N] [--stream --block N] [--hop H] --out-dir out/   (STFT cross-synthesis)
@@ -226,11 +227,18 @@ def _check_locked(locked, formant, F=1024):
         raise ValueError("--locked: 1024-point frames expected (the peak-locked kernels are not built for 2048)")
 
 
-def _mode_kw(formant, lifter, locked, formant_name="formant"):
-    """What a call receives beyond the plain call's arguments: nothing, the formant pair, locked=True."""
+def _check_subbin(subbin, locked):
+    if subbin and not locked:
+        raise ValueError("--subbin: valid only together with --locked (the sub-bin region offsets are a variant of the peak-locked call)")
+
+
+def _mode_kw(formant, lifter, locked, formant_name="formant", subbin=False):
+    """What a call receives beyond the plain call's arguments: nothing, the formant pair, locked=True, subbin=True (only when set)."""
     kw = {} if formant is None else {formant_name: float(formant), "lifter": int(lifter)}
     if locked:
         kw["locked"] = True
+    if subbin:
+        kw["subbin"] = True
     return kw
 
 
@@ -272,37 +280,41 @@ def glide_curve(lens, start, end, N, n_blocks):
     return c
 
 
-def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, processor=None, formant=None, lifter=32, locked=False):
+def pv_glide(voices, start, end, N=1024, hop=256, device=0, blocks_per_call=16, processor=None, formant=None, lifter=32, locked=False,
+             subbin=False):
     """pv_shift with a glide: every recording's interval moves linearly from `start` to `end` semitones over its length, one value per
     block, through the streaming phase vocoder's ratio-curve call (PhaseVocoderStream.run(curve=...): several blocks per call, each
     with its own interval).  Returns float32 [2][len] per recording.  `processor` (tests): an object with latency and
     run(x, blocks_per_call, curve) to use instead of a new PhaseVocoderStream.  formant (semitones; None: the call above, unchanged): the
     formant-preserving call instead -- the spectral envelope moves by `formant` semitones (0: it stays) whatever the pitch does, with a
     cepstral lifter of `lifter` samples; run then also receives formant_semitones and lifter.  locked: the peak-locked call instead
-    (run then also receives locked=True); not together with formant."""
+    (run then also receives locked=True); not together with formant.  subbin (with locked only): the locked call with sub-bin region
+    offsets (run then also receives subbin=True)."""
     S = _batch_size(voices)
     if not (-12.0 <= float(start) <= 12.0 and -12.0 <= float(end) <= 12.0):
         raise ValueError("glide: intervals within +-12 semitones expected")
     _check_formant(formant, lifter)
     _check_locked(locked, formant)
+    _check_subbin(subbin, locked)
     p = _stream(processor, S, N, hop, device)
     lens = _lengths(voices)
     x = _pack_mono(voices, lens, max(lens))
     curve = glide_curve(lens, start, end, N, -(-(max(lens) + int(p.latency)) // int(N)))
     # (run's output is aligned with its input: the latency is off)
-    y = p.run(x, blocks_per_call=int(blocks_per_call), curve=curve, **_mode_kw(formant, lifter, locked, "formant_semitones"))
+    y = p.run(x, blocks_per_call=int(blocks_per_call), curve=curve, **_mode_kw(formant, lifter, locked, "formant_semitones", subbin))
     return _both_channels(y, lens)
 
 
-def pv_shift_locked(voices, shift, N=1024, hop=256, device=0, blocks_per_call=16, processor=None):
+def pv_shift_locked(voices, shift, N=1024, hop=256, device=0, blocks_per_call=16, processor=None, subbin=False):
     """pv_shift through the PEAK-LOCKED call: every recording by its own fixed interval (one value or one per recording), streamed block
     by block through PhaseVocoderStream.run(curve=..., locked=True) -- a constant curve.  Returns float32 [2][len] per recording.
-    `processor` (tests): an object with latency and run(x, blocks_per_call, curve, locked) to use instead of a new PhaseVocoderStream."""
+    `processor` (tests): an object with latency and run(x, blocks_per_call, curve, locked) to use instead of a new PhaseVocoderStream.
+    subbin: the locked call with sub-bin region offsets (run then also receives subbin=True)."""
     S = _batch_size(voices)
     per = _per_recording(shift, S, "shift", float, *SHIFT_RANGE)
     p = _stream(processor, S, N, hop, device)
     lens = _lengths(voices)
-    y = p.run(_pack_mono(voices, lens, max(lens)), blocks_per_call=int(blocks_per_call), curve=np.array([per]), locked=True)
+    y = p.run(_pack_mono(voices, lens, max(lens)), blocks_per_call=int(blocks_per_call), curve=np.array([per]), **_mode_kw(None, 0, True, subbin=subbin))
     return _both_channels(y, lens)
 
 
@@ -404,10 +416,10 @@ class _AutotuneRunner:
     def __init__(self, F, hop, device):
         self.F, self.hop, self.device = int(F), int(hop), device
 
-    def run(self, x, fs, keys, formant=None, lifter=32, locked=False):
+    def run(self, x, fs, keys, formant=None, lifter=32, locked=False, subbin=False):
         def call(st, d_in, d_out):
             return st.autotune(d_in, d_out, float(fs), keys=[int(k) for k in keys], formant_semitones=formant, lifter=int(lifter),
-                               **_mode_kw(None, 0, locked))
+                               **_mode_kw(None, 0, locked, subbin=subbin))
         y, (period, ratio) = _one_shot(x, x.shape[1], self.F, self.hop, self.device, call)
         return y, period.cpu().numpy(), ratio.cpu().numpy()
 
@@ -435,7 +447,8 @@ def _tune(p, voices, lens, T, fs, keys, kw, offset, with_track):
     return (outs, period, ratio) if with_track else outs
 
 
-def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, with_track=False, formant=None, lifter=32, locked=False):
+def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, with_track=False, formant=None, lifter=32, locked=False,
+                subbin=False):
     """A batch of recordings through the pitch tracker and the one-shot phase vocoder (StftRoundTrip.autotune: one stream per recording):
     every frame is moved onto the nearest note of its recording's key.  key: Notes::key 0..12 (12 = chromatic), one value or one per
     recording.  The recordings are zero-padded to a common length (tune_length).  Returns float32 [2][len] per recording (the corrected
@@ -444,14 +457,16 @@ def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, w
     keeps the spectral envelope apart from the pitch (StftRoundTrip.autotune(formant_semitones=...); 1024-point frames) -- 0 leaves the
     singer's formants where they were; lifter: the cepstral lifter, 4 .. 64 samples; run then also receives formant and lifter.
     locked: the correction runs through the peak-locked call (StftRoundTrip.autotune(locked=True); 1024-point frames, not together with
-    formant); run then also receives locked=True."""
+    formant); run then also receives locked=True.  subbin (with locked only): the locked call with sub-bin region offsets; run then also
+    receives subbin=True."""
     keys = _check_tune(voices, fs, key, formant, lifter)
     if formant is not None and int(F) != 1024:
         raise ValueError("pvtune --formant: 1024-point frames expected (the formant kernels are not built for 2048)")
     _check_locked(locked, formant, F)
+    _check_subbin(subbin, locked)
     lens = _lengths(voices)
     p = processor if processor is not None else _AutotuneRunner(F, hop, device)
-    return _tune(p, voices, lens, tune_length(max(lens), fs, F, hop), fs, keys, _mode_kw(formant, lifter, locked), 0, with_track)
+    return _tune(p, voices, lens, tune_length(max(lens), fs, F, hop), fs, keys, _mode_kw(formant, lifter, locked, subbin=subbin), 0, with_track)
 
 
 class _StreamTuneRunner:
@@ -461,10 +476,10 @@ class _StreamTuneRunner:
     def __init__(self, N, hop, F, hold, glide, device, blocks_per_call=16):
         self.N, self.hop, self.F, self.hold, self.glide, self.device, self.k = int(N), int(hop), int(F), int(hold), float(glide), device, int(blocks_per_call)
 
-    def run(self, x, fs, keys, formant=None, lifter=32, locked=False):
+    def run(self, x, fs, keys, formant=None, lifter=32, locked=False, subbin=False):
         import torch
         from . import PhaseVocoderStream, StreamingPitchTracker
-        lk = _mode_kw(None, 0, locked)
+        lk = _mode_kw(None, 0, locked, subbin=subbin)
         S, N = x.shape[0], self.N
         nb = x.shape[1] // N
         dev = torch.device("cuda", self.device)
@@ -493,17 +508,18 @@ def stream_tune_length(max_len, N, hop):
 
 
 def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glide=1.0, device=0, processor=None, with_track=False, formant=None,
-                       lifter=32, locked=False):
+                       lifter=32, locked=False, subbin=False):
     """pv_autotune block by block, as a live caller would run it: the streaming tracker (StreamingPitchTracker, analysis length F) decides
     one ratio per block of N samples from the audio received so far, holds the last voiced ratio for `hold` unvoiced blocks and moves the
     fraction `glide` of the way to its target per block; the streaming phase vocoder (1024-point frames) shifts along that table.  The
     recordings are zero-padded to whole blocks that also hold the shifter's latency, which is taken off the front.  Returns float32
     [2][len] per recording; with_track: also period int32 [n_blocks][S] and ratio float64 [n_blocks][S] of the padded batch.  A decision
     costs the same at every N: N = 64 costs 16 times as much per second of audio as N = 1024.  `processor` (tests): an object with
-    run(x, fs, keys) to use instead of the GPU.  formant, lifter, locked: as pv_autotune's (the shifter's frames are 1024 points whatever
-    F)."""
+    run(x, fs, keys) to use instead of the GPU.  formant, lifter, locked, subbin: as pv_autotune's (the shifter's frames are 1024 points
+    whatever F)."""
     keys = _check_tune(voices, fs, key, formant, lifter)
     _check_locked(locked, formant)
+    _check_subbin(subbin, locked)
     if int(N) < 1 or int(F) not in (1024, 2048):
         raise ValueError("pvtune --stream: a block of at least one sample and a tracker frame of 1024 or 2048 expected")
     if not (0 <= int(hold) <= 1 << 20 and 0.0 < float(glide) <= 1.0):
@@ -511,7 +527,7 @@ def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glid
     lens = _lengths(voices)
     T, lat = stream_tune_length(max(lens), N, hop)
     p = processor if processor is not None else _StreamTuneRunner(N, hop, F, hold, glide, device)
-    return _tune(p, voices, lens, T, fs, keys, _mode_kw(formant, lifter, locked), lat, with_track)
+    return _tune(p, voices, lens, T, fs, keys, _mode_kw(formant, lifter, locked, subbin=subbin), lat, with_track)
 
 
 class _CrossRunner:
@@ -611,6 +627,9 @@ def main(argv=None):
     ap.add_argument("--locked", action="store_true",
                     help="pvshift (--shift or --glide), pvtune [--stream], stretch: the peak-locked phase vocoder -- a spectral peak's whole region moves "
                          "and turns as one, so tones keep their level (1024-point frames; not together with --formant)")
+    ap.add_argument("--subbin", action="store_true",
+                    help="pvshift, pvtune [--stream], together with --locked: a peak's region moves by the real-valued offset of its interpolated "
+                         "centre and the spectrum is interpolated (six taps), so shifted tones keep their level at every interval")
     ap.add_argument("--depth", type=float, default=1.0, help="pvcross: 0 (the carrier unchanged) to 1 (the voice's spectral envelope in full)")
     ap.add_argument("--lifter", type=int, default=32, help="--formant, pvcross: length of the cepstral lifter in samples, 4 to 64 (short: a smoother envelope)")
     ap.add_argument("--hold", type=int, default=0, help="pvtune --stream: unvoiced blocks over which the last voiced ratio is kept")
@@ -631,7 +650,7 @@ def main(argv=None):
             break
     a = ap.parse_args(argv)
     if a.flow == "pvcross":
-        for flag, given in (("--formant", a.formant is not None), ("--locked", a.locked), ("--shift", a.shift is not None), ("--glide", a.glide is not None),
+        for flag, given in (("--formant", a.formant is not None), ("--locked", a.locked), ("--subbin", a.subbin), ("--shift", a.shift is not None), ("--glide", a.glide is not None),
                             ("--stretch", a.stretch is not None)):
             if given:
                 raise SystemExit(f"{flag}: pvcross does not take it (the cross-synthesis moves neither pitch nor time)")
@@ -641,9 +660,17 @@ def main(argv=None):
         raise SystemExit("--locked: pvshift, pvtune and stretch take it")
     if a.locked and a.formant is not None:
         raise SystemExit("--locked and --formant exclude each other: formant correction on top of peak locking is not built")
+    if a.subbin and a.flow == "stretch":
+        raise SystemExit("--subbin: stretch does not take it (the locked time stretch keeps integer offsets)")
+    if a.subbin and a.flow not in ("pvshift", "pvtune"):
+        raise SystemExit("--subbin: pvshift and pvtune take it")
+    if a.subbin and not a.locked:
+        raise SystemExit("--subbin: valid only together with --locked (the sub-bin region offsets are a variant of the peak-locked call)")
     fkw = {} if a.formant is None else dict(formant=a.formant, lifter=a.lifter)
     if a.locked:
         fkw["locked"] = True
+    if a.subbin:
+        fkw["subbin"] = True
 
     recs = [read_wav(f) for f in a.inputs]
     fs = recs[0][0]
@@ -708,7 +735,7 @@ def main(argv=None):
                 raise SystemExit(str(e))
         elif a.locked:
             try:
-                outs = pv_shift_locked(voices, a.shift, N=a.block, hop=a.hop, device=a.device)
+                outs = pv_shift_locked(voices, a.shift, N=a.block, hop=a.hop, device=a.device, **({"subbin": True} if a.subbin else {}))
             except ValueError as e:
                 raise SystemExit(str(e))
         elif a.formant is not None:

@@ -138,6 +138,9 @@ def load_library():
     if hasattr(L, "vp_stft_pitch_shift_locked"):       # (the peak-locked entries; absent from older libraries loaded through VP_AMD_LIB)
         L.vp_stft_pitch_shift_locked.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p]
         L.vp_pv_process_blocks_locked_device.argtypes = [vp, fp, fp, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "vp_stft_pitch_shift_locked_subbin"):   # (the sub-bin locked entries; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_stft_pitch_shift_locked_subbin.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p]
+        L.vp_pv_process_blocks_locked_subbin_device.argtypes = [vp, fp, fp, C.c_void_p, C.c_int, C.c_void_p]
     if hasattr(L, "vp_stft_time_stretch"):             # (the time stretch; absent from older libraries loaded through VP_AMD_LIB)
         L.vp_stft_time_stretch.argtypes = [vp, fp, C.c_int, C.c_void_p, fp, C.c_double, C.c_void_p]
         L.vp_stretch_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]
@@ -574,6 +577,12 @@ def _not_formant_on_locked(formant_semitones, d_formant=None):
         raise ValueError("locked and formant_semitones exclude each other: formant correction on top of locking is not built")
 
 
+def _subbin_needs_locked(locked):
+    """subbin=True is a variant of the locked call (callers test `subbin` themselves)."""
+    if not locked:
+        raise ValueError("subbin=True needs locked=True: the sub-bin region offsets are a variant of the peak-locked call")
+
+
 def _upload_ratios(tables, semitones, dev):
     """The ratios of a table of intervals (already in the kernel's layout) in a device table of that shape, allocated once per shape in
     the caller's `tables`; the copy goes on torch's current stream."""
@@ -750,14 +759,17 @@ class StftRoundTrip:
         d_ratio = self._ratio_table(semitones, d_ratio, d_in.device)
         self._chk(self.L.vp_stft_pitch_shift_curve(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), _stream_of(stream, d_in)))
 
-    def pitch_shift_locked(self, d_in, d_out, semitones=None, stream=None, d_ratio=None):
+    def pitch_shift_locked(self, d_in, d_out, semitones=None, stream=None, d_ratio=None, subbin=False):
         """pitch_shift_curve with peak locking (vp_stft_pitch_shift_locked; 1024-point frames): every frame's spectral peaks are found and a
         peak's whole region of bins moves by one integer offset and turns by one accumulated angle, so a sinusoid's main lobe stays one
         windowed sinusoid (the definition is tests/pv_lock_reference.py).  `semitones`, `d_ratio` and `stream` as in pitch_shift_curve --
-        the same table-building path.  A 2048-point handle raises VpError (VP_ERR_GEOMETRY)."""
+        the same table-building path.  A 2048-point handle raises VpError (VP_ERR_GEOMETRY).
+        subbin=True: vp_stft_pitch_shift_locked_subbin -- a region is translated by the real-valued offset of its peak's interpolated
+        centre and the spectrum interpolated with six taps, so a shifted tone keeps its level (tests/pv_lockf_reference.py)."""
         self._io(d_in, d_out)
         d_ratio = self._ratio_table(semitones, d_ratio, d_in.device)
-        self._track_chk(self.L.vp_stft_pitch_shift_locked(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), _stream_of(stream, d_in)))
+        call = self.L.vp_stft_pitch_shift_locked_subbin if subbin else self.L.vp_stft_pitch_shift_locked
+        self._track_chk(call(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), _stream_of(stream, d_in)))
 
     def pitch_shift_formant(self, d_in, d_out, semitones=None, stream=None, d_ratio=None, formant_semitones=0.0, lifter=FORMANT_LIFTER, d_formant=None):
         """pitch_shift_curve with the spectral envelope kept apart from the pitch (vp_stft_pitch_shift_formant; 1024-point frames): the
@@ -861,18 +873,22 @@ class StftRoundTrip:
                                                    _stream_of(stream, d_in)))
         return period, ratio
 
-    def autotune(self, d_in, d_out, sample_rate, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False):
+    def autotune(self, d_in, d_out, sample_rate, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False, subbin=False):
         """Automatic pitch correction (vp_stft_autotune): track_pitch, then pitch_shift_curve along its ratios, on one stream; d_out has
         the bits of those two calls.  Returns track_pitch's (period, ratio).
         formant_semitones (a scalar or [S]; None: the call above, unchanged): the correction runs through pitch_shift_formant instead
         (vp_stft_autotune_formant) -- 0 keeps the formants where the singer had them.
         locked=True: track_pitch followed by pitch_shift_locked along its ratios, on the same stream (not together with
-        formant_semitones: ValueError before any launch)."""
+        formant_semitones: ValueError before any launch).  subbin=True (with locked=True only: ValueError otherwise, before any launch):
+        the locked call is pitch_shift_locked(subbin=True)."""
         self._io(d_in, d_out)
         if locked:
             _not_formant_on_locked(formant_semitones)
+        if subbin:
+            _subbin_needs_locked(locked)
+        if locked:
             period, ratio = self.track_pitch(d_in, sample_rate, keys=keys, stream=stream)
-            self.pitch_shift_locked(d_in, d_out, stream=stream, d_ratio=ratio)
+            self.pitch_shift_locked(d_in, d_out, stream=stream, d_ratio=ratio, **({"subbin": True} if subbin else {}))
             return period, ratio
         d_key, period, ratio = self._track_tables(keys, d_in.device)
         head = (self.h, d_in.data_ptr(), d_out.data_ptr(), float(sample_rate), _ptr(d_key), period.data_ptr(), ratio.data_ptr())
@@ -949,7 +965,7 @@ class PhaseVocoderStream:
         return _upload_ratios(self._curve_tables, np.broadcast_to(held, (n_blocks, self.S)), dev)
 
     def process_device(self, d_in, d_out, n_blocks=1, stream=None, semitones_per_block=None, d_ratio=None, formant_semitones=None, lifter=FORMANT_LIFTER,
-                       d_formant=None, locked=False):
+                       d_formant=None, locked=False, subbin=False):
         """n_blocks blocks on the device: torch float32 [n_blocks][S][N] (or [S][N] for one block), enqueued on `stream`
         (default: the current torch stream) without synchronising.
         semitones_per_block: array-like [n_blocks] or [n_blocks][S], |value| <= 12 -- this call's frames take the interval of the block in
@@ -963,12 +979,16 @@ class PhaseVocoderStream:
         locked=True: the curve call with peak locking (vp_pv_process_blocks_locked_device); without a table of its own it takes the
         intervals set_semitones holds, like a formant call.  Not together with formant_semitones / d_formant: ValueError before any
         launch.  The kinds of call share the stream's state: after a change of kind the output is finite but carries a phase jump
-        (reset() the stream at the change to avoid it)."""
+        (reset() the stream at the change to avoid it).
+        subbin=True (with locked=True only: ValueError otherwise, before any launch): the locked call with sub-bin region offsets
+        (vp_pv_process_blocks_locked_subbin_device); it shares the locked call's state."""
         # (the asserts and the stream's default are written out here and in autotune_device: a helper's call would be most of what a
         # call of one small block costs the host)
         import torch
         if locked:
             _not_formant_on_locked(formant_semitones, d_formant)
+        if subbin:
+            _subbin_needs_locked(locked)
         n = int(n_blocks)
         shape = (self.S, self.N) if n == 1 and d_in.dim() == 2 else (n, self.S, self.N)
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
@@ -988,14 +1008,16 @@ class PhaseVocoderStream:
             d_ratio = self._held_table(n, d_in.device)
         assert d_ratio.is_cuda and d_ratio.dtype == torch.float64 and tuple(d_ratio.shape) == (n, self.S) and d_ratio.is_contiguous()
         if locked:
-            self._chk(self.L.vp_pv_process_blocks_locked_device(*io, d_ratio.data_ptr(), n, st))
+            call = self.L.vp_pv_process_blocks_locked_subbin_device if subbin else self.L.vp_pv_process_blocks_locked_device
+            self._chk(call(*io, d_ratio.data_ptr(), n, st))
         elif formant:
             d_formant = _device_formants(self, formant_semitones, d_formant, d_in.device)
             self._chk(self.L.vp_pv_process_blocks_formant_device(*io, d_ratio.data_ptr(), d_formant.data_ptr(), int(lifter), n, st))
         else:
             self._chk(self.L.vp_pv_process_blocks_curve_device(*io, d_ratio.data_ptr(), n, st))
 
-    def autotune_device(self, tracker, d_in, d_out, n_blocks=1, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False):
+    def autotune_device(self, tracker, d_in, d_out, n_blocks=1, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False,
+                        subbin=False):
         """Automatic pitch correction block by block (vp_pv_autotune_blocks_device): `tracker` (a StreamingPitchTracker of the same
         streams, block size and device) decides one ratio per block and stream from the audio received so far, this stream shifts along
         that table, both on `stream`; d_out has the bits of tracker.process_device followed by process_device(d_ratio=...).  Returns the
@@ -1003,11 +1025,15 @@ class PhaseVocoderStream:
         formant_semitones (a scalar or [S]; None: the call above, unchanged): the shift runs through the formant call instead
         (vp_pv_autotune_blocks_formant_device).
         locked=True: tracker.process_device followed by process_device(d_ratio=..., locked=True) on the same stream (not together with
-        formant_semitones: ValueError before any launch)."""
+        formant_semitones: ValueError before any launch).  subbin=True (with locked=True only): the locked call is
+        process_device(d_ratio=..., locked=True, subbin=True)."""
         if locked:
             _not_formant_on_locked(formant_semitones)
+        if subbin:
+            _subbin_needs_locked(locked)
+        if locked:
             period, ratio = tracker.process_device(d_in, n_blocks=n_blocks, keys=keys, stream=stream)
-            self.process_device(d_in, d_out, n_blocks=n_blocks, stream=stream, d_ratio=ratio, locked=True)
+            self.process_device(d_in, d_out, n_blocks=n_blocks, stream=stream, d_ratio=ratio, locked=True, **({"subbin": True} if subbin else {}))
             return period, ratio
         import torch
         n = int(n_blocks)
@@ -1025,7 +1051,7 @@ class PhaseVocoderStream:
             self._chk(self.L.vp_pv_autotune_blocks_device(*head, n, C.c_void_p(stream)))
         return period, ratio
 
-    def run(self, x, blocks_per_call=8, curve=None, autotune=None, keys=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False):
+    def run(self, x, blocks_per_call=8, curve=None, autotune=None, keys=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False, subbin=False):
         """Whole signals float [S][T] -> output aligned with the input, [S][T]: the input padded with `latency` zeros (and up to
         whole blocks), streamed through the device entry point `blocks_per_call` blocks at a time, the first `latency` samples
         dropped.  Continues from the handle's state (reset() first for a fresh start).
@@ -1034,11 +1060,14 @@ class PhaseVocoderStream:
         autotune: a StreamingPitchTracker instead -- every call goes through autotune_device(autotune, ..., keys=keys), and the result is
         (output, period, ratio) with the tracker's tables as numpy arrays [n_blocks][S] (the padding blocks included).
         formant_semitones (a scalar or [S]; None: as above, unchanged): every call is a formant call (process_device / autotune_device).
-        locked=True: every call is a peak-locked call (process_device / autotune_device with locked=True; not with formant_semitones)."""
+        locked=True: every call is a peak-locked call (process_device / autotune_device with locked=True; not with formant_semitones).
+        subbin=True (with locked=True only): every call also takes subbin=True."""
         assert curve is None or autotune is None, "one of curve and autotune"
         if locked:
             _not_formant_on_locked(formant_semitones)
-        lk = {"locked": True} if locked else {}                     # (without the flag: exactly the calls made before it existed)
+        if subbin:
+            _subbin_needs_locked(locked)
+        lk = {"locked": True, **({"subbin": True} if subbin else {})} if locked else {}                     # (without the flag: exactly the calls made before it existed)
         import torch
         x = np.asarray(x, dtype=np.float32)
         assert x.ndim == 2 and x.shape[0] == self.S, x.shape
