@@ -366,8 +366,8 @@ int vp_stft_pitch_shift_curve(vp_stft *p, const float *d_in, float *d_out, const
  *   theta[k] = th[own[k]] for every k.  A frame without peaks (all zeros) gives Y = 0 and leaves theta.
  * A region is translated whole: at r > 1 the gaps stay empty, at r < 1 neighbouring regions are cut where they meet, not added.  At
  * r = 1 the stage is the identity.  1024-point frames, every hop, always double, one workgroup per stream, no allocation.
- * Out of scope: 2048-point frames; formant correction on top of locking; adding overlapping regions; several voices per call.  The
- * integer offset costs level (a 0.5 tone leaves at 0.38 at -12 and at +7 semitones): vp_stft_pitch_shift_locked_subbin interpolates.
+ * Out of scope: 2048-point frames; formant correction on top of locking; adding overlapping regions.  Several voices per call are
+ * vp_stft_harmonize.  The integer offset costs level (a 0.5 tone leaves at 0.38 at -12 and at +7 semitones): vp_stft_pitch_shift_locked_subbin interpolates.
  * Locking in the time stretch is vp_stft_time_stretch_locked.
  * VP_ERR_INVALID_ARG (null handle, input, output or ratio table) and VP_ERR_GEOMETRY (a 2048-point handle) are reported before the
  * device is touched and vp_stft_last_error says which; VP_ERR_HIP as vp_stft_pitch_shift. */
@@ -385,6 +385,28 @@ int vp_stft_pitch_shift_locked(vp_stft *p, const float *d_in, float *d_out, cons
  * scope: the locked time stretch (it keeps integer offsets), 2048-point frames, formant correction on top, adding overlapping regions,
  * single precision.  Arguments, checks, their order and codes as vp_stft_pitch_shift_locked's; the texts begin "locked subbin: ". */
 int vp_stft_pitch_shift_locked_subbin(vp_stft *p, const float *d_in, float *d_out, const double *d_ratio, void *hip_stream);
+/* The HARMONIZER: n_voices peak-locked copies of the voice, each shifted along its own ratio curve and mixed by its own gain, beside the
+ * dry signal, from ONE analysis of every frame (kernel vp_k_stft_harm; the definition is tests/pv_harm_reference.py).  The inverse
+ * transform and the overlap-add are linear and the locked stage's analysis does not depend on the ratio, so in exact arithmetic
+ *   out = dry[s] roundtrip(x) + sum_v gain[s][v] locked(x, ratio[s][v]),   roundtrip and locked the two calls of those names above;
+ * the kernel reads the input, transforms, finds peaks and owners, transforms back and overlap-adds once per frame instead of
+ * n_voices + 1 times, and runs only the shifted peaks, the gather and one angle array theta per voice n_voices times.  Per frame the sum
+ * is dry X + gain[0] Y_0 + ... in this order, X the analysis spectrum, Y_v the locked stage's synthesis spectrum for voice v (bins 0 and
+ * 512 real).  One voice with gain 1 and no dry part has the locked call's bits; all gains 0 with dry 1 has the double round trip's.  A
+ * voice with gain 0 still turns its angles, so it can be faded in later.  A frame without a peak contributes its dry term alone.
+ * d_ratio: device double [n_streams][n_voices][vp_stft_num_frames(p)], clamped to [0.5, 2] as in the curve call;  d_gain: device double
+ * [n_streams][n_voices] or NULL = every gain 1;  d_dry: device double [n_streams] or NULL = 0.  A gain or dry value that is NaN or
+ * infinite counts as 0, a finite one is clamped to [-4, 4].  n_voices: 1 .. VP_HARM_MAX_VOICES.  A caller composes a tracker's ratio
+ * with an interval on the table.  1024-point frames, every hop, always double, one workgroup per stream, no allocation; the runs setting
+ * and output aliasing as in the locked call.
+ * Out of scope: sub-bin region offsets per voice; formant correction per voice; 2048-point frames; single precision; intervals chosen
+ * from a key (diatonic harmony); gains per block or per frame.
+ * VP_ERR_INVALID_ARG (null handle, input, output or ratio table; n_voices outside 1 .. 4) and VP_ERR_GEOMETRY (a 2048-point handle:
+ * "harmonize: 2048-point frames are not built ...") are reported before the device is touched, in that order, and vp_stft_last_error
+ * says which; VP_ERR_HIP as vp_stft_pitch_shift. */
+#define VP_HARM_MAX_VOICES 4
+int vp_stft_harmonize(vp_stft *p, const float *d_in, float *d_out, int n_voices, const double *d_ratio, const double *d_gain, const double *d_dry,
+                      void *hip_stream);
 /* vp_stft_pitch_shift_curve with the spectral envelope kept apart from the pitch (kernel vp_k_stft_pv_formant): the formants stay where
  * they were, or move by a ratio of their own, while the pitch follows d_ratio.  The definition is tests/pv_formant_reference.py.  Per
  * frame, with m the analysis magnitudes, r the frame's pitch ratio and phi the stream's formant ratio (both clamped to [0.5, 2] as in
@@ -575,6 +597,29 @@ int vp_xs_reset(vp_xs *x, int stream);                                  /* strea
 int vp_xs_process_blocks_device(vp_xs *x, const float *d_voice, const float *d_carrier, float *d_out, const double *d_depth, int lifter,
                                 int n_blocks, void *hip_stream);
 long vp_xs_debug_alloc_count(const vp_xs *x);                           /* constant across process calls; -1 on NULL */
+
+/* Streaming harmonizer: vp_stft_harmonize driven block by block (kernel vp_k_hz_stream).  One handle holds S independent streams of
+ * n_voices voices each (1 .. VP_HARM_MAX_VOICES, fixed at create), frame length 1024 (VP_ERR_GEOMETRY otherwise, also for a hop
+ * vp_stft_supported(1024, hop) refuses), block size N >= 1 fixed at create.  Frame grid, latency L = F - gcd(N, hop) and call
+ * bookkeeping are the streaming phase vocoder's: output sample t of a stream is sample t - L of the one-shot result on everything received
+ * -- the dry part included, which therefore needs no delay line of the caller's --, the first L samples are 0, and the concatenated
+ * outputs are BIT-IDENTICAL to vp_stft_harmonize over every sample emitted however the blocks are grouped into calls.  A frame takes the
+ * ratios of the block in which its last sample arrives; gains and dry are the call's.  A reset takes effect at the next process call and
+ * travels in its arguments; a reset stream behaves like a fresh one, the others are untouched.  Per stream the handle keeps 28 KB of
+ * state: the previous frame's phases, samples received (int64), input history and overlap-add carry (1024 floats each) and four angle
+ * arrays.  Device memory is allocated at create only.  It is a handle of its own: the streaming phase vocoder's record is not touched.
+ * d_in, d_out: device float [n_blocks][S][N]; d_ratio: device double [n_blocks][S][n_voices]; d_gain: device double [S][n_voices] or
+ * NULL = 1; d_dry: device double [S] or NULL = 0; values treated as in vp_stft_harmonize.  VP_ERR_INVALID_ARG (null handle, input,
+ * output or ratio table, n_blocks <= 0, n_voices outside 1 .. 4 at create, stream out of range) is reported before the device is
+ * touched. */
+typedef struct vp_hz vp_hz;
+int vp_hz_create(int device, int n_streams, int block_size, int frame_len, int hop, int n_voices, vp_hz **out);
+int vp_hz_destroy(vp_hz *h);
+int vp_hz_get_latency(const vp_hz *h);                                  /* F - gcd(N, hop) */
+int vp_hz_reset(vp_hz *h, int stream);                                  /* stream -1 = all; takes effect at the next call */
+int vp_hz_process_blocks_device(vp_hz *h, const float *d_in, float *d_out, const double *d_ratio, const double *d_gain, const double *d_dry,
+                                int n_blocks, void *hip_stream);
+long vp_hz_debug_alloc_count(const vp_hz *h);                           /* constant across process calls; -1 on NULL */
 
 /* Streaming pitch tracker and automatic correction for the stream above (kernels vp_k_yin_track_stream and vp_k_track_follow,
  * csrc/vp_track.hip): vp_stft_track_pitch's decision once per block and stream, from the audio received so far, followed across unvoiced

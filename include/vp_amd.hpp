@@ -495,4 +495,41 @@ private:
     vp_xs *x_ = nullptr;
 };
 
+// vp::StreamingHarmonizer -- the streaming phase-vocoder harmonizer (vp_hz_*, vp_amd.h): S streams, blocks of N samples, nVoices
+// peak-locked voices per stream beside the dry signal, state kept across calls.  Output sample t of a stream is sample t - latency() of
+// the one-shot vp_stft_harmonize on everything the stream received; the dry part is delayed with the voices.
+//
+//     vp::StreamingHarmonizer hz(/*device*/ 0, /*streams*/ 256, /*block*/ 1024, /*voices*/ 3);      // hop 256
+//     hz.processBlocksDevice(dIn, dOut, dRatio, /*dGain*/ nullptr, dDry, 16);   // float [16][256][1024]; double [16][256][3], -, [256]
+class StreamingHarmonizer {
+public:
+    StreamingHarmonizer(int device, int nStreams, int blockSize, int nVoices, int hop = 256, int frameLen = 1024)
+    {
+        check(vp_hz_create(device, nStreams, blockSize, frameLen, hop, nVoices, &h_), "vp_hz_create");
+    }
+    ~StreamingHarmonizer() { if (h_) vp_hz_destroy(h_); }
+    StreamingHarmonizer(const StreamingHarmonizer &) = delete;
+    StreamingHarmonizer &operator=(const StreamingHarmonizer &) = delete;
+
+    int latency() const { return vp_hz_get_latency(h_); }
+    // takes effect at the next process call; stream = -1: all streams
+    void reset(int stream = -1) { check(vp_hz_reset(h_, stream), "reset"); }
+    // dIn, dOut: device float [nBlocks][S][N]; dRatio: device double [nBlocks][S][nVoices], pitch ratios in [0.5, 2]; dGain: device double
+    // [S][nVoices] or null = 1; dDry: device double [S] or null = 0; enqueued on hipStream without synchronising
+    void processBlocksDevice(const float *dIn, float *dOut, const double *dRatio, const double *dGain, const double *dDry, int nBlocks,
+                             void *hipStream = nullptr)
+    {
+        check(vp_hz_process_blocks_device(h_, dIn, dOut, dRatio, dGain, dDry, nBlocks, hipStream), "processBlocksDevice");
+    }
+    long debugAllocCount() const { return vp_hz_debug_alloc_count(h_); }
+    vp_hz *handle() const { return h_; }
+
+private:
+    static void check(int rc, const std::string &what)
+    {
+        if (rc != VP_OK) throw Error(rc, what + ": " + vp_error_string(rc));
+    }
+    vp_hz *h_ = nullptr;
+};
+
 }  // namespace vp

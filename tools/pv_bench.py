@@ -10,6 +10,7 @@
     [VP_AMD_LIB=...] python tools/pv_bench.py --stretch-locked [--reps 7] [--out profiles/pv_stretch_lock_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --locked-subbin [--reps 7] [--out profiles/pv_lockf_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --cross [--reps 7] [--out profiles/pv_cross_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --harm [--reps 7] [--out profiles/pv_harm_bench.txt]
 
 --curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
 "steps" curve, fixed, ...): 256 streams x 65 536 samples at 1024 points / hop 256 and 2048 points / hop 512 (vp_stft_pitch_shift against
@@ -56,6 +57,13 @@ process: 256 streams x 65 536 samples, 1024 points / hop 256, voiced voices over
 of the carrier (two transforms per frame), the formant kernel on the voice (four, and the phase-vocoder stage), the cross-synthesis (seven),
 and the streaming cross-synthesis, 16 blocks of 1024 per call.  The cross-synthesis's mean over the round trip's and over the formant
 kernel's from the same run are the comparisons; the kernels' resource listings follow.
+
+--harm: the harmonizer (vp_stft_harmonize, vp_hz_process_blocks_device) beside the composition it replaces, alternating in one process:
+256 streams x 65 536 samples, 1024 points / hop 256, three voices (+4, +7, -5 semitones) plus the dry signal, on noise and on voiced input.
+The legs: the harmonizer; three vp_stft_pitch_shift_locked calls, one double-precision vp_stft_roundtrip and the mix as one fused torch
+expression on the device (a matrix-vector product over the stacked parts: one read of each, one write); one locked call alone.  Rates are input frames per second (a frame counts once however many voices it gets).
+Streaming, 16 blocks of 1024 per call: the streaming harmonizer against three locked streaming handles plus the mix (the composition's dry
+part is the undelayed input there: a caller's delay line is not timed).  The kernels' resource listings follow.
 """
 import argparse
 import os
@@ -411,6 +419,60 @@ def cross_legs(reps, emit):
     xs.close()
 
 
+def harm_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import HarmonizerStream, PhaseVocoderStream, StftRoundTrip, semitones_to_ratios
+    S, T, F, hop, fs, V = 256, 65536, 1024, 256, 44100.0, 3
+    semis = np.array([4.0, 7.0, -5.0])
+    gains, dry = (1.0, 0.7, 0.7), 1.0
+    st = StftRoundTrip(S, T, F, hop)
+    nF = st.n_frames
+    ratio = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(semitones_to_ratios(semis)[None, :, None], (S, V, nF)))).cuda()
+    per = [ratio[:, v, :].contiguous() for v in range(V)]
+    d_gain = torch.from_numpy(np.tile(np.array(gains), (S, 1))).cuda()
+    d_dry = torch.from_numpy(np.full(S, dry)).cuda()
+    new, base, one = "harmonizer, 3 voices + dry", "3 locked + round trip + mix", "one locked call"
+    inputs = (("noise", torch.randn(S, T, device="cuda", dtype=torch.float32) * 0.1), ("voiced signals", torch.from_numpy(voiced_rows(S, T, fs)).cuda()))
+    w = torch.tensor([list(gains) + [dry]], dtype=torch.float32, device="cuda")
+    for what, x in inputs:
+        y = torch.empty_like(x)
+        parts = torch.empty((V + 1, S, T), dtype=torch.float32, device="cuda")
+
+        def composed(x=x, y=y, parts=parts):
+            for v in range(V):
+                st.pitch_shift_locked(x, parts[v], d_ratio=per[v])
+            st(x, parts[V])
+            torch.mm(w, parts.view(V + 1, -1), out=y.view(1, -1))          # the mix: one pass over the four parts, one write
+        legs = {new: lambda x=x, y=y: st.harmonize(x, y, d_ratio=ratio, gains=d_gain, dry=d_dry),
+                base: composed,
+                one: lambda x=x, y=y: st.pitch_shift_locked(x, y, d_ratio=per[0])}
+        report(f"one-shot, {S} streams x {T} samples of {what}, F = {F}, hop = {hop}", alternate(legs, reps, 40), S * nF, base, emit)
+    st.close()
+    N, K = 1024, 16
+    hz = HarmonizerStream(S, N, V, hop=hop)
+    ps = [PhaseVocoderStream(S, N, hop=hop) for _ in range(V)]
+    tab = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(semitones_to_ratios(semis), (K, S, V)))).cuda()
+    tabs = [tab[:, :, v].contiguous() for v in range(V)]
+    for what, x in inputs:
+        xb = x[:, :K * N].reshape(S, K, N).transpose(0, 1).contiguous()
+        yb = torch.empty_like(xb)
+        parts = torch.empty((V + 1, K, S, N), dtype=torch.float32, device="cuda")
+        parts[V].copy_(xb)                                     # (the dry part: the input as it is)
+
+        def composed(xb=xb, yb=yb, parts=parts):
+            for v in range(V):
+                ps[v].process_device(xb, parts[v], n_blocks=K, d_ratio=tabs[v], locked=True)
+            torch.mm(w, parts.view(V + 1, -1), out=yb.view(1, -1))
+        legs = {"streaming harmonizer": lambda xb=xb, yb=yb: hz.process_device(xb, yb, n_blocks=K, d_ratio=tab, gains=d_gain, dry=d_dry),
+                "3 locked streams + mix": composed}
+        report(f"streaming, {S} streams, {K} blocks of {N} per call of {what}, hop = {hop}", alternate(legs, reps, 150), S * K * N // hop,
+               "3 locked streams + mix", emit)
+    hz.close()
+    for p in ps:
+        p.close()
+
+
 def resource_listing(emit, kernels=("vp_k_stft_fused<true, false>", "vp_k_stft_pv_stretch", "vp_k_stft_pv2k", "vp_k_stft_pv2k_stretch")):
     try:
         import kernel_resources
@@ -434,10 +496,11 @@ def main():
     ap.add_argument("--locked-subbin", action="store_true", help="the sub-bin peak-locked legs instead of the fixed intervals")
     ap.add_argument("--stretch-locked", action="store_true", help="the locked time-stretch legs instead of the fixed intervals")
     ap.add_argument("--cross", action="store_true", help="the cross-synthesis legs instead of the fixed intervals")
+    ap.add_argument("--harm", action="store_true", help="the harmonizer legs instead of the fixed intervals")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="--curve / --stretch / --track: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.locked_subbin and not a.stretch_locked and not a.cross:
+    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.locked_subbin and not a.stretch_locked and not a.cross and not a.harm:
         return fixed_intervals()
     lines = []
 
@@ -467,6 +530,9 @@ def main():
     if a.cross:
         cross_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_stft_fused<false, false>", "vp_k_stft_pv_formant", "vp_k_stft_cross", "vp_k_xs_stream"))
+    if a.harm:
+        harm_legs(max(5, a.reps), emit)
+        resource_listing(emit, ("vp_k_stft_pv_lock", "vp_k_stft_harm", "vp_k_pv_stream_lock", "vp_k_hz_stream"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

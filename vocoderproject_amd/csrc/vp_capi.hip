@@ -1906,7 +1906,7 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     // that a later hipGetLastError() behind a launch does not report this one.
     p->pvOk = vp_stft_prepare_device() == hipSuccess && vp_stft_curve_prepare_device() == hipSuccess && vp_stft_stretch_prepare_device() == hipSuccess
         && vp_stft_formant_prepare_device() == hipSuccess && vp_stft_lock_prepare_device() == hipSuccess && vp_stft_stretch_lock_prepare_device() == hipSuccess
-        && vp_stft_lockf_prepare_device() == hipSuccess;
+        && vp_stft_lockf_prepare_device() == hipSuccess && vp_stft_harm_prepare_device() == hipSuccess;
     if (!p->pvOk) (void)hipGetLastError();
     p->device = device; p->F = frame_len; p->hop = hop; p->S = n_streams; p->T = n_samples;
     p->nFrames = (n_samples - frame_len) / hop + 1;
@@ -2121,6 +2121,24 @@ extern "C" int vp_stft_pitch_shift_locked_subbin(vp_stft *p, const float *d_in, 
 {
     const PvMode m = PvMode::lock_subbin(d_ratio);
     return stft_call(p, stft_check(p, "locked subbin", d_in && d_out && d_ratio, "null input, output or ratio table", &m), d_in, d_out, nullptr, &m, hip_stream);
+}
+
+// the harmonizer (vp_k_stft_harm; 1024-point frames): n_voices peak-locked voices, each along its own ratio curve and with its own gain,
+// and the dry signal, from one analysis of every frame.  Checked before the device is touched, in stft_check's order: handle, pointers,
+// voice count, frame length, the device's verdict at create.  One run per stream, as in the locked call (vp_stft_set_runs has no say)
+extern "C" int vp_stft_harmonize(vp_stft *p, const float *d_in, float *d_out, int n_voices, const double *d_ratio, const double *d_gain, const double *d_dry,
+                                 void *hip_stream)
+{
+    int rc = stft_check(p, "harmonize", d_in && d_out && d_ratio, "null input, output or ratio table", nullptr);
+    if (rc) return rc;
+    if (n_voices < 1 || n_voices > VP_HARM_MAX_VOICES) { p->lastError = "harmonize: the number of voices is outside 1 .. 4"; return VP_ERR_INVALID_ARG; }
+    const PvMode m = PvMode::lock(d_ratio);
+    rc = stft_check(p, "harmonize", true, nullptr, &m);                        // (the locked stage's frame length; the LDS ceiling)
+    if (rc) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    int nRuns;
+    const VpStftArgs a = stft_args(p, d_in, d_out, nullptr, &m, &nRuns);
+    return vp_stft_launch_harm(a, d_ratio, d_gain, d_dry, n_voices, p->S, (hipStream_t)hip_stream) == hipSuccess ? VP_OK : VP_ERR_HIP;
 }
 
 // vp_stft_pitch_shift_curve with the cepstral formant correction: d_formant [S] formant ratios or NULL (1.0: the envelope stays where it
@@ -2542,6 +2560,104 @@ extern "C" int vp_xs_process_blocks_device(vp_xs *x, const float *d_voice, const
     if (vp_xs_launch(a, st) != hipSuccess) return VP_ERR_HIP;
     x->allReset = false;
     std::fill(x->resetPend.begin(), x->resetPend.end(), 0);
+    return VP_OK;
+}
+
+// ---- streaming harmonizer (no reference counterpart): vp_k_hz_stream of vp_stft_harm.inc, vp_stft_harmonize block by block ---------------
+struct vp_hz {
+    int device = 0, S = 0, N = 0, F = 0, hop = 0, L = 0, V = 0;
+    double *win = nullptr, *tw1 = nullptr, *tw2 = nullptr, *tws = nullptr;
+    double c = 0;
+    unsigned char *state = nullptr;             // [S][VP_HZ_REC_BYTES] (vp_stft.h)
+    long nAllocs = 0;
+    // resets made since the last process call, as the updates it carries (an all-stream reset clears the per-stream ones)
+    bool allReset = false;
+    std::vector<char> resetPend;                // [S]
+    std::vector<VpPvUpdate> upd;                // staging of the updates (capacity S + 1, reserved at create)
+};
+
+static void hz_free(vp_hz *h)
+{
+    (void)hipFree(h->win); (void)hipFree(h->tw1); (void)hipFree(h->tw2); (void)hipFree(h->tws); (void)hipFree(h->state);
+}
+
+extern "C" int vp_hz_create(int device, int n_streams, int block_size, int frame_len, int hop, int n_voices, vp_hz **out)
+{
+    if (!out || n_streams <= 0 || block_size <= 0 || frame_len <= 0 || hop <= 0 || n_voices < 1 || n_voices > VP_HARM_MAX_VOICES) return VP_ERR_INVALID_ARG;
+    if ((long long)n_streams * block_size > (1LL << 28) || (long long)block_size > (1 << 24)) return VP_ERR_INVALID_ARG;
+    if (frame_len != 1024 || !vp_stft_supported(frame_len, hop)) return VP_ERR_GEOMETRY;
+    if (select_device(device)) return VP_ERR_NO_DEVICE;
+    if (vp_hz_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
+    vp_hz *h = new vp_hz();
+    h->device = device; h->S = n_streams; h->N = block_size; h->F = frame_len; h->hop = hop; h->V = n_voices;
+    int g = block_size, b = hop;
+    while (b) { const int t = g % b; g = b; b = t; }
+    h->L = frame_len - g;
+    std::vector<double> w, t1, t2, ts, tt;
+    const float scale = stft_host_tables(frame_len, hop, w, t1, t2, ts, tt);
+    h->c = (double)scale / (double)(frame_len / 2);                      // (as stft_fused)
+    h->resetPend.assign(n_streams, 0);
+    h->upd.reserve(n_streams + 1);
+    // every stream starts with no samples received, zero phases, angles, history and carry
+    std::vector<unsigned char> rec((size_t)n_streams * VP_HZ_REC_BYTES, 0);
+    long *n = &h->nAllocs;
+    const bool ok = put(&h->win, w, n) && put(&h->tw1, t1, n) && put(&h->tw2, t2, n) && put(&h->tws, ts, n)
+        && put((void **)&h->state, rec.data(), rec.size(), n);
+    if (!ok) { hz_free(h); delete h; (void)hipGetLastError(); return VP_ERR_OOM; }
+    *out = h;
+    return VP_OK;
+}
+
+extern "C" int vp_hz_destroy(vp_hz *h)
+{
+    if (!h) return VP_ERR_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    hz_free(h);
+    delete h;
+    return VP_OK;
+}
+
+extern "C" int vp_hz_get_latency(const vp_hz *h) { return h ? h->L : VP_ERR_INVALID_ARG; }
+extern "C" long vp_hz_debug_alloc_count(const vp_hz *h) { return h ? h->nAllocs : VP_ERR_INVALID_ARG; }
+
+extern "C" int vp_hz_reset(vp_hz *h, int stream)
+{
+    if (!h || stream < -1 || stream >= h->S) return VP_ERR_INVALID_ARG;
+    if (stream < 0) {
+        h->allReset = true;
+        std::fill(h->resetPend.begin(), h->resetPend.end(), 0);
+    } else h->resetPend[stream] = 1;
+    return VP_OK;
+}
+
+// the pending resets travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update launches in front of it), as pv_run's do
+extern "C" int vp_hz_process_blocks_device(vp_hz *h, const float *d_in, float *d_out, const double *d_ratio, const double *d_gain, const double *d_dry,
+                                           int n_blocks, void *hip_stream)
+{
+    if (!h || !d_in || !d_out || !d_ratio || n_blocks <= 0 || (long long)n_blocks * h->N > (1 << 28)) return VP_ERR_INVALID_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    h->upd.clear();
+    if (h->allReset) h->upd.push_back(VpPvUpdate{-1, 1, 0.0});
+    for (int s = 0; s < h->S; s++)
+        if (h->resetPend[s]) h->upd.push_back(VpPvUpdate{s, 1, 0.0});
+    VpPvArgs a;
+    memset(&a, 0, sizeof a);
+    a.state = h->state; a.win = h->win; a.tw1 = h->tw1; a.tw2 = h->tw2; a.tws = h->tws; a.c = h->c;
+    a.S = h->S; a.N = h->N; a.hop = h->hop; a.O = h->F / h->hop; a.L = h->L;
+    size_t i = 0;
+    while (h->upd.size() - i > VP_PV_MAX_UPDATES) {
+        a.nBlocks = 0; a.nUpd = VP_PV_MAX_UPDATES;
+        for (int k = 0; k < VP_PV_MAX_UPDATES; k++) a.upd[k] = h->upd[i + k];
+        if (vp_hz_launch(a, nullptr, nullptr, nullptr, h->V, st) != hipSuccess) return VP_ERR_HIP;
+        i += VP_PV_MAX_UPDATES;
+    }
+    a.in = d_in; a.out = d_out; a.nBlocks = n_blocks; a.nUpd = (int)(h->upd.size() - i);
+    for (int k = 0; k < a.nUpd; k++) a.upd[k] = h->upd[i + k];
+    if (vp_hz_launch(a, d_ratio, d_gain, d_dry, h->V, st) != hipSuccess) return VP_ERR_HIP;
+    h->allReset = false;
+    std::fill(h->resetPend.begin(), h->resetPend.end(), 0);
     return VP_OK;
 }
 

@@ -137,3 +137,23 @@ struct VpXsArgs {
 size_t vp_xs_lds_bytes();
 // the streaming kernel (grid = S workgroups); nBlocks = 0 launches the small kernel that only applies the resets
 hipError_t vp_xs_launch(const VpXsArgs &a, hipStream_t st);
+
+// ---- the harmonizer (vp_stft_harmonize, vp_hz_*; csrc/vp_stft_harm.inc): V peak-locked voices and the dry signal from one analysis --------
+#define VP_HARM_MAX_VOICES 4
+// the one-shot build (vp_k_stft_harm): d_ratio [nStreams][nVoices][a.nFrames], d_gain [nStreams][nVoices] or nullptr (1), d_dry [nStreams] or
+// nullptr (0); one workgroup per stream, a.F == 1024.  Its dynamic LDS at this hop: the locked build's plus three more angle arrays
+hipError_t vp_stft_launch_harm(const VpStftArgs &a, const double *d_ratio, const double *d_gain, const double *d_dry, int nVoices, int nStreams, hipStream_t st);
+hipError_t vp_stft_harm_prepare_device();
+size_t vp_stft_harm_lds_bytes(int hop);
+// one stream's state of the streaming build, VP_HZ_REC_BYTES each: previous-frame phases [513] | samples received (int64) (doubles) |
+// input history [1024] | overlap-add carry [1024] (floats) | theta [VP_HARM_MAX_VOICES][513] (doubles)
+#define VP_HZ_COUNT VP_PV_NB
+#define VP_HZ_HIST_BYTES ((VP_PV_NB + 1) * 8)
+#define VP_HZ_CARRY_BYTES (VP_HZ_HIST_BYTES + 1024 * 4)
+#define VP_HZ_THETA_BYTES (VP_HZ_CARRY_BYTES + 1024 * 4)
+#define VP_HZ_REC_BYTES (VP_HZ_THETA_BYTES + VP_HARM_MAX_VOICES * VP_PV_NB * 8)
+// the streaming kernel (vp_k_hz_stream; grid = a.S workgroups): a.state holds VP_HZ records, a.upd resets only; d_ratio [a.nBlocks][a.S][nVoices],
+// d_gain and d_dry as above; a.nBlocks = 0 launches the small kernel that only applies the resets
+hipError_t vp_hz_launch(const VpPvArgs &a, const double *d_ratio, const double *d_gain, const double *d_dry, int nVoices, hipStream_t st);
+hipError_t vp_hz_prepare_device();
+size_t vp_hz_lds_bytes();

@@ -482,3 +482,7 @@ hipError_t vp_pv_launch_lockf(const VpPvArgs &a, const double *d_ratio, hipStrea
     hipLaunchKernelGGL(vp_k_pv_stream_lockf, dim3(a.S), dim3(64 * NWV), vp_pv_lockf_lds_bytes(), st, a, d_ratio);
     return hipGetLastError();
 }
+
+// ---- the harmonizer: several peak-locked voices and the dry signal from one analysis (vp_stft_harmonize, vp_hz_process_blocks_device): a
+// part of this family, entered here as this file is entered from vp_stft_lock.inc (the header of vp_stft_harm.inc says why)
+#include "vp_stft_harm.inc"

@@ -19,6 +19,7 @@ There is no CPU path here either: without a GPU the processor raises.
     python -m vocoderproject_amd.offline pvtune a.wav b.wav --key 0 --out-dir out/ [--track-csv]        (pitch tracker + phase-vocoder correction)
     python -m vocoderproject_amd.offline pvtune a.wav --stream [--block 256 --hold 8 --glide 0.5] --out-dir out/   (... block by block: the streaming tracker)
     python -m vocoderproject_amd.offline pvcross voice.wav [more.wav] --carrier synth.wav [--depth D] [--lifter N] [--stream --block N] [--hop H] --out-dir out/   (STFT cross-synthesis)
+    python -m vocoderproject_amd.offline harmonize a.wav [b.wav] --voices 4,7,-5 [--gains 1,1,0.7] [--dry 1] [--stream --block N] [--hop H] --out-dir out/   (peak-locked harmonizer)
 """
 import argparse
 import os
@@ -593,6 +594,66 @@ def pv_cross(voices, carriers, depth=1.0, lifter=32, F=1024, hop=256, N=1024, st
     return _both_channels(y, lens)
 
 
+class _HarmRunner:
+    """StftRoundTrip.harmonize from host arrays: x float32 [S][T], semitones [S][V][n_frames], gains [S][V], dry [S] -> float32 [S][T]."""
+
+    def __init__(self, F, hop, device):
+        self.F, self.hop, self.device = int(F), int(hop), device
+
+    def run(self, x, semitones, gains, dry):
+        def call(st, d_in, d_out):
+            st.harmonize(d_in, d_out, semitones=semitones, gains=gains, dry=dry)
+        return _one_shot(x, x.shape[1], self.F, self.hop, self.device, call)[0]
+
+
+HARM_MAX_VOICES = 4
+
+
+def pv_harmonize(voices, intervals, gains=None, dry=1.0, F=1024, hop=256, N=1024, stream=False, blocks_per_call=16, device=0, processor=None):
+    """The phase-vocoder harmonizer on a batch (one stream per recording): beside every recording, `dry` times itself, V = 1 .. 4
+    peak-locked copies shifted by `intervals` semitones (each within +-12) and mixed by `gains` (V values within [-4, 4]; None: 1 each).
+    dry: one value or one per recording, within [-4, 4].  Batch (default): the one-shot call StftRoundTrip.harmonize on the recordings
+    padded to a common length under the full overlap of 1024-point frames; stream: block by block through HarmonizerStream.run, its
+    latency taken off.  Returns float32 [2][len] per recording (the signal on both channels).  `processor` (tests): an object with
+    run(x, semitones [S][V][n_frames], gains [S][V], dry [S]) (batch) or latency and run(x, semitones [n_blocks][S][V], blocks_per_call,
+    gains, dry) (stream) to use instead of the GPU."""
+    S = _batch_size(voices)
+    many = isinstance(intervals, (list, tuple)) or (isinstance(intervals, np.ndarray) and intervals.ndim == 1)
+    iv = [float(v) for v in intervals] if many else []
+    if not 1 <= len(iv) <= HARM_MAX_VOICES:
+        raise ValueError("voices: 1 to 4 intervals expected")
+    if not all(-12.0 <= v <= 12.0 for v in iv):
+        raise ValueError("voices: intervals within +-12 semitones expected")
+    V = len(iv)
+    g = [1.0] * V if gains is None else [float(v) for v in gains]
+    if len(g) != V:
+        raise ValueError("gains: one gain per voice expected")
+    if not all(-4.0 <= v <= 4.0 for v in g):
+        raise ValueError("gains: values within [-4, 4] expected")
+    per = _per_recording(dry, S, "dry", float, -4.0, 4.0, "dry: values within [-4, 4] expected")
+    if int(F) != 1024:
+        raise ValueError("harmonize: 1024-point frames expected (the harmonizer kernels are not built for 2048)")
+    hop, N = int(hop), int(N)
+    lens = _lengths(voices)
+    gtab = np.tile(np.array(g, np.float64), (S, 1))
+    if stream:
+        x = _pack_mono(voices, lens, max(lens))
+        if processor is None:
+            from . import HarmonizerStream
+            processor = HarmonizerStream(S, N, V, hop=hop, device=device)
+        nb = -(-(max(lens) + int(processor.latency)) // N)
+        st = np.tile(np.array(iv, np.float64), (nb, S, 1))
+        y = processor.run(x, semitones=st, blocks_per_call=int(blocks_per_call), gains=gtab, dry=per)
+    else:
+        T = 1024 + -(-max(lens) // hop) * hop                                  # (every sample under the full overlap of frames)
+        x = _pack_mono(voices, lens, T)
+        nF = (T - 1024) // hop + 1
+        st = np.tile(np.array(iv, np.float64)[None, :, None], (S, 1, nF))
+        p = processor if processor is not None else _HarmRunner(F, hop, device)
+        y = p.run(x, st, gtab, per)
+    return _both_channels(y, lens)
+
+
 def write_track_csv(path, fs, hop, period, ratio, n_samples=None):
     """One recording's track: a line per frame with its start time in seconds, the period in samples (0 = unvoiced) and the correction in
     semitones (12 log2 ratio); n_samples: only the frames that start inside the recording."""
@@ -608,7 +669,7 @@ def write_track_csv(path, fs, hop, period, ratio, n_samples=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m vocoderproject_amd.offline", description=__doc__.split("\n\n")[0])
-    ap.add_argument("flow", choices=["pitch", "vocode", "both", "pvshift", "stretch", "pvtune", "pvcross"])
+    ap.add_argument("flow", choices=["pitch", "vocode", "both", "pvshift", "stretch", "pvtune", "pvcross", "harmonize"])
     ap.add_argument("inputs", nargs="+", help="voice recordings (WAV; channel 0 is used, like the notebook)")
     ap.add_argument("--carrier", action="append", default=None,
                     help="side-chain recording(s) for vocode/both, carrier(s) for pvcross (channel 0): one for all voices or one per voice")
@@ -632,6 +693,10 @@ def main(argv=None):
                          "centre and the spectrum is interpolated (six taps), so shifted tones keep their level at every interval")
     ap.add_argument("--depth", type=float, default=1.0, help="pvcross: 0 (the carrier unchanged) to 1 (the voice's spectral envelope in full)")
     ap.add_argument("--lifter", type=int, default=32, help="--formant, pvcross: length of the cepstral lifter in samples, 4 to 64 (short: a smoother envelope)")
+    ap.add_argument("--voices", default=None, metavar="ST[,ST..]",
+                    help="harmonize: 1 to 4 intervals in semitones, each within +-12, comma-separated (a list that starts below zero as --voices=-5,4)")
+    ap.add_argument("--gains", default=None, metavar="G[,G..]", help="harmonize: one gain per voice within [-4, 4] (default: 1 each)")
+    ap.add_argument("--dry", type=float, default=1.0, help="harmonize: gain of the unshifted signal beside the voices, within [-4, 4] (default 1)")
     ap.add_argument("--hold", type=int, default=0, help="pvtune --stream: unvoiced blocks over which the last voiced ratio is kept")
     ap.add_argument("--stretch", type=float, default=None, help="stretch: output duration / input duration, 0.25 to 4 (--shift: semitones on top)")
     ap.add_argument("--frame", type=int, default=1024, help="stretch, pvtune: frame length (1024 or 2048)")
@@ -654,6 +719,15 @@ def main(argv=None):
                             ("--stretch", a.stretch is not None)):
             if given:
                 raise SystemExit(f"{flag}: pvcross does not take it (the cross-synthesis moves neither pitch nor time)")
+    if a.flow == "harmonize":
+        for flag, given in (("--formant", a.formant is not None), ("--locked", a.locked), ("--subbin", a.subbin), ("--shift", a.shift is not None), ("--glide", a.glide is not None),
+                            ("--stretch", a.stretch is not None), ("--carrier", a.carrier is not None), ("--track-csv", a.track_csv), ("--hold", a.hold != 0)):
+            if given:
+                raise SystemExit(f"{flag}: harmonize does not take it (its voices are peak-locked copies at the fixed intervals of --voices)")
+        if a.voices is None:
+            raise SystemExit("harmonize needs --voices ST[,ST..]")
+    elif a.voices is not None or a.gains is not None:
+        raise SystemExit("--voices, --gains: harmonize takes them")
     if a.formant is not None and a.flow not in ("pvshift", "pvtune"):
         raise SystemExit("--formant: pvshift and pvtune take it")
     if a.locked and a.flow not in ("pvshift", "pvtune", "stretch"):
@@ -687,6 +761,17 @@ def main(argv=None):
             raise SystemExit("--carrier: give one, or one per voice")
         try:
             outs = pv_cross(voices, [c[1][0] for c in cs], depth=a.depth, lifter=a.lifter, hop=a.hop, N=a.block, stream=a.stream, device=a.device)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        return _write_outputs(a, fs, outs)
+    if a.flow == "harmonize":
+        try:
+            iv = [float(v) for v in a.voices.split(",")]
+            gains = None if a.gains is None else [float(v) for v in a.gains.split(",")]
+        except ValueError:
+            raise SystemExit("--voices, --gains: comma-separated numbers expected")
+        try:
+            outs = pv_harmonize(voices, iv, gains=gains, dry=a.dry, hop=a.hop, N=a.block, stream=a.stream, device=a.device)
         except ValueError as e:
             raise SystemExit(str(e))
         return _write_outputs(a, fs, outs)

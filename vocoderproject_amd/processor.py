@@ -189,6 +189,15 @@ def load_library():
         L.vp_xs_process_blocks_device.argtypes = [vp, fp, fp, fp, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.vp_xs_debug_alloc_count.argtypes = [vp]
         L.vp_xs_debug_alloc_count.restype = C.c_long
+    if hasattr(L, "vp_stft_harmonize"):                # (the harmonizer entries; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_stft_harmonize.argtypes = [vp, fp, fp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_hz_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.vp_hz_destroy.argtypes = [vp]
+        L.vp_hz_get_latency.argtypes = [vp]
+        L.vp_hz_reset.argtypes = [vp, C.c_int]
+        L.vp_hz_process_blocks_device.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.vp_hz_debug_alloc_count.argtypes = [vp]
+        L.vp_hz_debug_alloc_count.restype = C.c_long
     L.vp_error_string.argtypes = [C.c_int]
     L.vp_error_string.restype = C.c_char_p
     L.vp_last_error.argtypes = [vp]
@@ -671,6 +680,45 @@ def _device_depths(owner, depth, d_depth, dev):
     return owner._depth_table
 
 
+HARM_MAX_VOICES = 4                     # VP_HARM_MAX_VOICES
+
+
+def _harm_io(d_in, d_out, shape):
+    """The contract of a harmonizer call's input and output, before anything is launched: float32 device tensors of `shape`, contiguous.
+    ValueError otherwise."""
+    torch = _T or _torch()
+    for name, t in (("input", d_in), ("output", d_out)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError(f"harmonize: {name}: a contiguous float32 tensor on the GPU expected")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"harmonize: {name}: shape {tuple(shape)} expected, got {tuple(t.shape)}")
+
+
+def _harm_levels(owner, V, gains, dry, dev):
+    """The gain and dry tables of a harmonizer call as device float64 tensors [S][V] and [S], or None for the library's NULL (every gain
+    1; no dry part).  A device tensor is used as it is; host values -- gains [V] or [S][V], dry a scalar or [S] -- go into tables kept on
+    `owner`, rewritten on torch's current stream.  The kernel clamps to [-4, 4] and takes a NaN or an infinity as 0."""
+    torch = _T or _torch()
+    S = owner.S
+
+    def table(x, name, shape, admitted, slot):
+        if x is None:
+            return None
+        if isinstance(x, torch.Tensor):
+            if not _is(x, torch.float64, shape):
+                raise ValueError(f"harmonize: {name}: a contiguous float64 tensor {list(shape)} on the GPU expected")
+            return x
+        a = np.asarray(x, dtype=np.float64)
+        if a.shape not in admitted:
+            raise ValueError(f"harmonize: {name}: shape {a.shape}, one of {admitted} expected")
+        tabs = owner.__dict__.setdefault("_harm_tables", {})
+        if (slot, shape) not in tabs:
+            tabs[(slot, shape)] = torch.empty(shape, dtype=torch.float64, device=dev)
+        tabs[(slot, shape)].copy_(torch.from_numpy(np.array(np.broadcast_to(a, shape))))
+        return tabs[(slot, shape)]
+    return table(gains, "gains", (S, V), [(V,), (S, V)], "gain"), table(dry, "dry", (S,), [(), (S,)], "dry")
+
+
 class StftRoundTrip:
     """Standalone batched STFT -> iSTFT (no reference counterpart; see include/vp_amd.h vp_stft_*)."""
 
@@ -782,6 +830,39 @@ class StftRoundTrip:
         d_formant = _device_formants(self, formant_semitones, d_formant, d_in.device)
         self._track_chk(self.L.vp_stft_pitch_shift_formant(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), d_formant.data_ptr(), int(lifter),
                                                            _stream_of(stream, d_in)))
+
+    def harmonize(self, d_in, d_out, semitones=None, d_ratio=None, gains=None, dry=None, stream=None):
+        """The harmonizer (vp_stft_harmonize; 1024-point frames): V = 1 .. 4 peak-locked voices, each shifted by its own interval and mixed
+        by its own gain, beside the dry signal, from one analysis of every frame -- dry roundtrip(x) + sum_v gains[v] pitch_shift_locked(x,
+        semitones[v]) (the definition is tests/pv_harm_reference.py).  `semitones`: [V] fixed intervals, [V][n_frames] one curve per voice
+        for every stream, or [S][V][n_frames], each |value| <= 12; they become ratios through semitones_to_ratios in a device table the
+        handle keeps per shape.  d_ratio instead: a device float64 tensor [S][V][n_frames], used as it is (the kernel clamps to [0.5, 2]).
+        gains: None (every gain 1), [V], [S][V] or a device float64 tensor [S][V]; dry: None (no dry part), a scalar, [S] or a device
+        float64 tensor [S].  One voice with gain 1 and no dry part has pitch_shift_locked's bits.  Wrong dtypes or shapes raise ValueError
+        before any launch; a 2048-point handle raises VpError."""
+        torch = _T or _torch()
+        _harm_io(d_in, d_out, (self.S, self.T))
+        if (semitones is None) == (d_ratio is None):
+            raise ValueError("harmonize: one of semitones and d_ratio expected")
+        nF = self.n_frames
+        if d_ratio is None:
+            st = np.asarray(semitones, dtype=np.float64)
+            if st.ndim == 1:
+                st = st[:, None]
+            elif st.ndim == 3 and st.shape[0] != self.S:
+                raise ValueError(f"harmonize: semitones: [{self.S}][V][{nF}] expected, got {st.shape}")
+            if st.ndim not in (2, 3) or not 1 <= st.shape[-2] <= HARM_MAX_VOICES or st.shape[-1] not in (1, nF):
+                raise ValueError(f"harmonize: semitones: [V], [V][{nF}] or [{self.S}][V][{nF}] with V = 1 .. {HARM_MAX_VOICES} expected, got {np.shape(semitones)}")
+            V = st.shape[-2]
+            d_ratio = _upload_ratios(self._curve_tables, np.broadcast_to(st, (self.S, V, nF)), d_in.device)
+        else:
+            if not (d_ratio.is_cuda and d_ratio.dtype == torch.float64 and d_ratio.dim() == 3 and d_ratio.is_contiguous()
+                    and 1 <= d_ratio.shape[1] <= HARM_MAX_VOICES and tuple(d_ratio.shape) == (self.S, d_ratio.shape[1], nF)):
+                raise ValueError(f"harmonize: d_ratio: a contiguous float64 tensor [{self.S}][V][{nF}] on the GPU with V = 1 .. {HARM_MAX_VOICES} expected")
+            V = int(d_ratio.shape[1])
+        d_gain, d_dry = _harm_levels(self, V, gains, dry, d_in.device)
+        self._track_chk(self.L.vp_stft_harmonize(self.h, d_in.data_ptr(), d_out.data_ptr(), V, d_ratio.data_ptr(), _ptr(d_gain), _ptr(d_dry),
+                                                 _stream_of(stream, d_in)))
 
     def cross_synth(self, d_voice, d_carrier, d_out, depth=1.0, lifter=FORMANT_LIFTER, stream=None, d_depth=None):
         """STFT cross-synthesis (vp_stft_cross_synth; 1024-point frames): the spectral envelope of d_voice imposed on d_carrier, frame by
@@ -1192,6 +1273,103 @@ class CrossSynthStream:
     def close(self):
         if getattr(self, "h", None):
             self.L.vp_xs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HarmonizerStream:
+    """Streaming harmonizer: `n_streams` independent streams of `n_voices` peak-locked voices each beside the dry signal, blocks of
+    `block_size` samples, state kept across calls (include/vp_amd.h vp_hz_*).  Output sample t of a stream is sample t - latency of what
+    StftRoundTrip.harmonize gives on everything the stream has received, bit for bit -- the dry part delayed with the voices --; the
+    first `latency` samples are 0."""
+
+    def __init__(self, n_streams, block_size, n_voices, hop=256, frame_len=1024, device=0):
+        try:
+            import torch  # noqa: F401  (run() and process_device() use torch: load its HIP runtime before the library loads one)
+        except ImportError:
+            pass
+        self.L = load_library()
+        h = C.c_void_p()
+        rc = self.L.vp_hz_create(int(device), int(n_streams), int(block_size), int(frame_len), int(hop), int(n_voices), C.byref(h))
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+        self.h, self.S, self.N, self.V, self.hop, self.F, self.device = h, int(n_streams), int(block_size), int(n_voices), int(hop), int(frame_len), device
+        self._tables = {}
+
+    def _chk(self, rc):
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+
+    @property
+    def latency(self):
+        """F - gcd(N, hop) samples."""
+        return self.L.vp_hz_get_latency(self.h)
+
+    def reset(self, stream=-1):
+        """The stream (-1: all) starts again like a fresh one at the next process call."""
+        self._chk(self.L.vp_hz_reset(self.h, int(stream)))
+
+    def process_device(self, d_in, d_out, n_blocks=1, semitones=None, d_ratio=None, gains=None, dry=None, stream=None):
+        """n_blocks blocks on the device: torch float32 [n_blocks][S][N] each (or [S][N] for one block), enqueued on `stream` (default: the
+        current torch stream) without synchronising.  `semitones`: [V] fixed intervals, [S][V], or [n_blocks][S][V] (a frame takes the
+        block its last sample arrives in); d_ratio instead: a device float64 tensor [n_blocks][S][V].  gains, dry: as
+        StftRoundTrip.harmonize's, for the frames this call completes.  Wrong dtypes or shapes raise ValueError before any launch."""
+        torch = _T or _torch()
+        n = int(n_blocks)
+        if n < 1:
+            raise ValueError("harmonize: at least one block expected")
+        _harm_io(d_in, d_out, (self.S, self.N) if n == 1 and d_in.dim() == 2 else (n, self.S, self.N))
+        if (semitones is None) == (d_ratio is None):
+            raise ValueError("harmonize: one of semitones and d_ratio expected")
+        if d_ratio is None:
+            st = np.asarray(semitones, dtype=np.float64)
+            if st.shape not in ((self.V,), (self.S, self.V), (n, self.S, self.V)):
+                raise ValueError(f"harmonize: semitones: [{self.V}], [{self.S}][{self.V}] or [{n}][{self.S}][{self.V}] expected, got {st.shape}")
+            d_ratio = _upload_ratios(self._tables, np.broadcast_to(st, (n, self.S, self.V)), d_in.device)
+        elif not _is(d_ratio, torch.float64, (n, self.S, self.V)):
+            raise ValueError(f"harmonize: d_ratio: a contiguous float64 tensor [{n}][{self.S}][{self.V}] on the GPU expected")
+        d_gain, d_dry = _harm_levels(self, self.V, gains, dry, d_in.device)
+        self._chk(self.L.vp_hz_process_blocks_device(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), _ptr(d_gain), _ptr(d_dry), n,
+                                                     _stream_of(stream, d_in)))
+
+    def run(self, x, semitones, blocks_per_call=8, gains=None, dry=None):
+        """Whole signals float [S][T] -> output aligned with the input, [S][T]: the input padded with `latency` zeros (and up to whole
+        blocks), streamed through process_device `blocks_per_call` blocks at a time, the first `latency` samples dropped.  `semitones`:
+        [V], [S][V] or [n_blocks_total][S][V] with n_blocks_total = ceil((T + latency) / N).  Continues from the handle's state (reset()
+        first for a fresh start)."""
+        import torch
+        x = np.asarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[0] != self.S:
+            raise ValueError(f"harmonize: input {x.shape}: an array [{self.S}][T] expected")
+        T, Lat, N = x.shape[1], self.latency, self.N
+        nb = -(-(T + Lat) // N)
+        st = np.asarray(semitones, dtype=np.float64)
+        if st.shape not in ((self.V,), (self.S, self.V), (nb, self.S, self.V)):
+            raise ValueError(f"harmonize: semitones: [{self.V}], [{self.S}][{self.V}] or [{nb}][{self.S}][{self.V}] expected, got {st.shape}")
+        st = np.broadcast_to(st, (nb, self.S, self.V))
+        dev = torch.device("cuda", self.device)
+        xp = np.zeros((self.S, nb * N), np.float32)
+        xp[:, :T] = x
+        d_x = torch.from_numpy(np.ascontiguousarray(xp.reshape(self.S, nb, N).transpose(1, 0, 2))).to(dev)
+        d_out = torch.empty_like(d_x)
+        for b in range(0, nb, int(blocks_per_call)):
+            k = min(int(blocks_per_call), nb - b)
+            self.process_device(d_x[b:b + k], d_out[b:b + k], n_blocks=k, semitones=st[b:b + k], gains=gains, dry=dry)
+        torch.cuda.synchronize(dev)
+        y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, nb * N)
+        return np.ascontiguousarray(y[:, Lat:Lat + T])
+
+    def debug_alloc_count(self):
+        return self.L.vp_hz_debug_alloc_count(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vp_hz_destroy(self.h)
             self.h = None
 
     def __del__(self):
