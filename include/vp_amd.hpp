@@ -34,6 +34,14 @@ struct Error : std::runtime_error {
     Error(int c, const std::string &what) : std::runtime_error(what), code(c) {}
 };
 
+namespace detail {
+// what the streaming classes do with a return code (their handles keep no message of their own)
+inline void check(int rc, const std::string &what)
+{
+    if (rc != VP_OK) throw Error(rc, what + ": " + vp_error_string(rc));
+}
+}  // namespace detail
+
 // MyBuffer.h:37-43
 struct BufferView {
     int geom[12];
@@ -349,29 +357,25 @@ class StreamingPitchTracker {
 public:
     StreamingPitchTracker(int device, int nStreams, int blockSize, double sampleRate, int frameLen = 1024)
     {
-        check(vp_pv_tracker_create(device, nStreams, blockSize, frameLen, sampleRate, &t_), "vp_pv_tracker_create");
+        detail::check(vp_pv_tracker_create(device, nStreams, blockSize, frameLen, sampleRate, &t_), "vp_pv_tracker_create");
     }
     ~StreamingPitchTracker() { if (t_) vp_pv_tracker_destroy(t_); }
     StreamingPitchTracker(const StreamingPitchTracker &) = delete;
     StreamingPitchTracker &operator=(const StreamingPitchTracker &) = delete;
 
     // every stream, from the next process call on; 0 <= holdBlocks <= 2^20, 0 < glide <= 1 (defaults 0 and 1: the raw ratio)
-    void setFollow(int holdBlocks, double glide) { check(vp_pv_tracker_set_follow(t_, holdBlocks, glide), "setFollow"); }
+    void setFollow(int holdBlocks, double glide) { detail::check(vp_pv_tracker_set_follow(t_, holdBlocks, glide), "setFollow"); }
     // takes effect at the next process call; stream = -1: all streams.  The shifter has its own reset.
-    void reset(int stream = -1) { check(vp_pv_tracker_reset(t_, stream), "reset"); }
+    void reset(int stream = -1) { detail::check(vp_pv_tracker_reset(t_, stream), "reset"); }
     // device float [nBlocks][S][N] -> period int [nBlocks][S] and/or ratio double [nBlocks][S] (one may be null); dKey: device int [S] or
     // null (chromatic); enqueued on hipStream without synchronising
     void processBlocksDevice(const float *dIn, const int *dKey, int *dPeriod, double *dRatio, int nBlocks, void *hipStream = nullptr)
     {
-        check(vp_pv_tracker_process_blocks_device(t_, dIn, dKey, dPeriod, dRatio, nBlocks, hipStream), "processBlocksDevice");
+        detail::check(vp_pv_tracker_process_blocks_device(t_, dIn, dKey, dPeriod, dRatio, nBlocks, hipStream), "processBlocksDevice");
     }
     vp_pv_tracker *handle() const { return t_; }
 
 private:
-    static void check(int rc, const std::string &what)
-    {
-        if (rc != VP_OK) throw Error(rc, what + ": " + vp_error_string(rc));
-    }
     vp_pv_tracker *t_ = nullptr;
 };
 
@@ -385,7 +389,7 @@ class StreamingPitchShifter {
 public:
     StreamingPitchShifter(int device, int nStreams, int blockSize, int hop = 256, int frameLen = 1024)
     {
-        check(vp_pv_create(device, nStreams, blockSize, frameLen, hop, &p_), "vp_pv_create");
+        detail::check(vp_pv_create(device, nStreams, blockSize, frameLen, hop, &p_), "vp_pv_create");
     }
     ~StreamingPitchShifter() { if (p_) vp_pv_destroy(p_); }
     StreamingPitchShifter(const StreamingPitchShifter &) = delete;
@@ -393,45 +397,45 @@ public:
 
     int latency() const { return vp_pv_get_latency(p_); }
     // takes effect at the next process call; stream = -1: all streams
-    void setSemitones(double semitones, int stream = -1) { check(vp_pv_set_semitones(p_, stream, semitones), "setSemitones"); }
+    void setSemitones(double semitones, int stream = -1) { detail::check(vp_pv_set_semitones(p_, stream, semitones), "setSemitones"); }
     double semitones(int stream) const
     {
         double v = 0;
-        check(vp_pv_get_semitones(p_, stream, &v), "semitones");
+        detail::check(vp_pv_get_semitones(p_, stream, &v), "semitones");
         return v;
     }
-    void reset(int stream = -1) { check(vp_pv_reset(p_, stream), "reset"); }
-    void processBlock(const float *in, float *out) { check(vp_pv_process_block(p_, in, out), "processBlock"); }
+    void reset(int stream = -1) { detail::check(vp_pv_reset(p_, stream), "reset"); }
+    void processBlock(const float *in, float *out) { detail::check(vp_pv_process_block(p_, in, out), "processBlock"); }
     // device float [nBlocks][S][N], enqueued on hipStream without synchronising
     void processBlocksDevice(const float *dIn, float *dOut, int nBlocks, void *hipStream = nullptr)
     {
-        check(vp_pv_process_blocks_device(p_, dIn, dOut, nBlocks, hipStream), "processBlocksDevice");
+        detail::check(vp_pv_process_blocks_device(p_, dIn, dOut, nBlocks, hipStream), "processBlocksDevice");
     }
     // the same with one pitch RATIO per block and stream, device double [nBlocks][S] (vp_semitones_to_ratios converts intervals): a frame
     // takes the ratio of the block in which its last sample arrives; setSemitones' interval is neither used nor changed
     void processBlocksCurve(const float *dIn, float *dOut, const double *dRatio, int nBlocks, void *hipStream = nullptr)
     {
-        check(vp_pv_process_blocks_curve_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksCurve");
+        detail::check(vp_pv_process_blocks_curve_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksCurve");
     }
     // processBlocksCurve with peak locking (vp_pv_process_blocks_locked_device): a spectral peak's whole region of bins moves by one
     // integer offset and turns by one accumulated angle.  The kinds of call share the stream's state: after a change of kind the output
     // is finite but carries a phase jump -- reset() the stream at the change to avoid it
     void processBlocksLocked(const float *dIn, float *dOut, const double *dRatio, int nBlocks, void *hipStream = nullptr)
     {
-        check(vp_pv_process_blocks_locked_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksLocked");
+        detail::check(vp_pv_process_blocks_locked_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksLocked");
     }
     // processBlocksLocked with sub-bin region offsets (vp_pv_process_blocks_locked_subbin_device): a region is translated by the
     // real-valued offset of its peak's interpolated centre and the spectrum interpolated, so a shifted tone keeps its level
     void processBlocksLockedSubbin(const float *dIn, float *dOut, const double *dRatio, int nBlocks, void *hipStream = nullptr)
     {
-        check(vp_pv_process_blocks_locked_subbin_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksLockedSubbin");
+        detail::check(vp_pv_process_blocks_locked_subbin_device(p_, dIn, dOut, dRatio, nBlocks, hipStream), "processBlocksLockedSubbin");
     }
     // automatic correction: the tracker's call, then processBlocksCurve along its table (dRatio: result and scratch, required; dPeriod
     // may be null), on one stream.  The tracker must have this shifter's streams, block size and device.  reset() does not reach it.
     void autotuneBlocks(StreamingPitchTracker &tracker, const float *dIn, float *dOut, const int *dKey, int *dPeriod, double *dRatio, int nBlocks,
                         void *hipStream = nullptr)
     {
-        check(vp_pv_autotune_blocks_device(p_, tracker.handle(), dIn, dOut, dKey, dPeriod, dRatio, nBlocks, hipStream), "autotuneBlocks");
+        detail::check(vp_pv_autotune_blocks_device(p_, tracker.handle(), dIn, dOut, dKey, dPeriod, dRatio, nBlocks, hipStream), "autotuneBlocks");
     }
     // processBlocksCurve with the spectral envelope kept apart from the pitch (vp_pv_process_blocks_formant_device): dFormant device double
     // [S] of formant ratios, or null = 1.0 (the formants stay where they were); lifter: the cepstral lifter's length, 4 .. 64 samples.
@@ -439,22 +443,19 @@ public:
     void processBlocksFormant(const float *dIn, float *dOut, const double *dRatio, const double *dFormant, int nBlocks, int lifter = 32,
                               void *hipStream = nullptr)
     {
-        check(vp_pv_process_blocks_formant_device(p_, dIn, dOut, dRatio, dFormant, lifter, nBlocks, hipStream), "processBlocksFormant");
+        detail::check(vp_pv_process_blocks_formant_device(p_, dIn, dOut, dRatio, dFormant, lifter, nBlocks, hipStream), "processBlocksFormant");
     }
     // automatic correction that keeps the formants: the tracker's call, then processBlocksFormant along its table
     void autotuneBlocks(StreamingPitchTracker &tracker, const float *dIn, float *dOut, const int *dKey, int *dPeriod, double *dRatio,
                         const double *dFormant, int lifter, int nBlocks, void *hipStream = nullptr)
     {
-        check(vp_pv_autotune_blocks_formant_device(p_, tracker.handle(), dIn, dOut, dKey, dPeriod, dRatio, dFormant, lifter, nBlocks, hipStream),
-              "autotuneBlocks (formant)");
+        detail::check(vp_pv_autotune_blocks_formant_device(p_, tracker.handle(), dIn, dOut, dKey, dPeriod, dRatio, dFormant, lifter, nBlocks,
+                                                           hipStream),
+                      "autotuneBlocks (formant)");
     }
     vp_pv *handle() const { return p_; }
 
 private:
-    static void check(int rc, const std::string &what)
-    {
-        if (rc != VP_OK) throw Error(rc, what + ": " + vp_error_string(rc));
-    }
     vp_pv *p_ = nullptr;
 };
 
@@ -468,7 +469,7 @@ class StreamingCrossSynth {
 public:
     StreamingCrossSynth(int device, int nStreams, int blockSize, int hop = 256, int frameLen = 1024)
     {
-        check(vp_xs_create(device, nStreams, blockSize, frameLen, hop, &x_), "vp_xs_create");
+        detail::check(vp_xs_create(device, nStreams, blockSize, frameLen, hop, &x_), "vp_xs_create");
     }
     ~StreamingCrossSynth() { if (x_) vp_xs_destroy(x_); }
     StreamingCrossSynth(const StreamingCrossSynth &) = delete;
@@ -476,22 +477,18 @@ public:
 
     int latency() const { return vp_xs_get_latency(x_); }
     // takes effect at the next process call; stream = -1: all streams
-    void reset(int stream = -1) { check(vp_xs_reset(x_, stream), "reset"); }
+    void reset(int stream = -1) { detail::check(vp_xs_reset(x_, stream), "reset"); }
     // device float [nBlocks][S][N] each, dOut no alias of an input; dDepth: device double [S] in [0, 1] or null = 1 (0: the carrier's
     // plain round trip); lifter: the cepstral lifter's length, 4 .. 64 samples; enqueued on hipStream without synchronising
     void processBlocksDevice(const float *dVoice, const float *dCarrier, float *dOut, const double *dDepth, int nBlocks, int lifter = 32,
                              void *hipStream = nullptr)
     {
-        check(vp_xs_process_blocks_device(x_, dVoice, dCarrier, dOut, dDepth, lifter, nBlocks, hipStream), "processBlocksDevice");
+        detail::check(vp_xs_process_blocks_device(x_, dVoice, dCarrier, dOut, dDepth, lifter, nBlocks, hipStream), "processBlocksDevice");
     }
     long debugAllocCount() const { return vp_xs_debug_alloc_count(x_); }
     vp_xs *handle() const { return x_; }
 
 private:
-    static void check(int rc, const std::string &what)
-    {
-        if (rc != VP_OK) throw Error(rc, what + ": " + vp_error_string(rc));
-    }
     vp_xs *x_ = nullptr;
 };
 
@@ -505,7 +502,7 @@ class StreamingHarmonizer {
 public:
     StreamingHarmonizer(int device, int nStreams, int blockSize, int nVoices, int hop = 256, int frameLen = 1024)
     {
-        check(vp_hz_create(device, nStreams, blockSize, frameLen, hop, nVoices, &h_), "vp_hz_create");
+        detail::check(vp_hz_create(device, nStreams, blockSize, frameLen, hop, nVoices, &h_), "vp_hz_create");
     }
     ~StreamingHarmonizer() { if (h_) vp_hz_destroy(h_); }
     StreamingHarmonizer(const StreamingHarmonizer &) = delete;
@@ -513,22 +510,18 @@ public:
 
     int latency() const { return vp_hz_get_latency(h_); }
     // takes effect at the next process call; stream = -1: all streams
-    void reset(int stream = -1) { check(vp_hz_reset(h_, stream), "reset"); }
+    void reset(int stream = -1) { detail::check(vp_hz_reset(h_, stream), "reset"); }
     // dIn, dOut: device float [nBlocks][S][N]; dRatio: device double [nBlocks][S][nVoices], pitch ratios in [0.5, 2]; dGain: device double
     // [S][nVoices] or null = 1; dDry: device double [S] or null = 0; enqueued on hipStream without synchronising
     void processBlocksDevice(const float *dIn, float *dOut, const double *dRatio, const double *dGain, const double *dDry, int nBlocks,
                              void *hipStream = nullptr)
     {
-        check(vp_hz_process_blocks_device(h_, dIn, dOut, dRatio, dGain, dDry, nBlocks, hipStream), "processBlocksDevice");
+        detail::check(vp_hz_process_blocks_device(h_, dIn, dOut, dRatio, dGain, dDry, nBlocks, hipStream), "processBlocksDevice");
     }
     long debugAllocCount() const { return vp_hz_debug_alloc_count(h_); }
     vp_hz *handle() const { return h_; }
 
 private:
-    static void check(int rc, const std::string &what)
-    {
-        if (rc != VP_OK) throw Error(rc, what + ": " + vp_error_string(rc));
-    }
     vp_hz *h_ = nullptr;
 };
 

@@ -1980,13 +1980,15 @@ extern "C" int vp_stft_get_precision(const vp_stft *p) { return p ? (p->f32 ? VP
 // are the only places that fill one, and there is none for a combination that no kernel serves (a formant correction on a locked call,
 // a position table on a formant call).
 struct PvMode {
-    enum Kind { FIXED, CURVE, LOCKED, LOCKED_SUBBIN, FORMANT, STRETCH, STRETCH_LOCKED } kind = FIXED;
+    enum Kind { FIXED, CURVE, LOCKED, LOCKED_SUBBIN, FORMANT, STRETCH, STRETCH_LOCKED, CROSS } kind = FIXED;
     double semitones = 0.0, ratio = 1.0;   // FIXED, STRETCH: the caller's interval and its ratio (a streaming call reads the ratios its records hold)
     const double *ratioTab = nullptr;   // every other kind: one-shot [S][nFrames], streaming [n_blocks][S]
     const int *posTab = nullptr;        // STRETCH, STRETCH_LOCKED: frame f of stream s is read at input sample posTab[s][f] ...
     int nIn = 0;                        // ... of rows of nIn samples
     const double *formant = nullptr;    // FORMANT: [S] formant ratios or null (1.0)
-    int lifter = 0;                     // FORMANT: the cepstral lifter's length in samples
+    int lifter = 0;                     // FORMANT, CROSS: the cepstral lifter's length in samples
+    const float *voice = nullptr;       // CROSS: [S][T], whose envelope the call's input -- the carrier -- takes ...
+    const double *depth = nullptr;      // ... to the depth [S], or null (1)
 
     static PvMode held() { return PvMode(); }                                     // (streaming: the intervals vp_pv_set_semitones left)
     static PvMode fixed(double semitones) { PvMode m; m.semitones = semitones; m.ratio = std::pow(2.0, semitones / 12.0); return m; }
@@ -1996,18 +1998,21 @@ struct PvMode {
     static PvMode form(const double *tab, const double *formant, int lifter) { PvMode m; m.kind = FORMANT; m.ratioTab = tab; m.formant = formant; m.lifter = lifter; return m; }
     static PvMode stretch(double semitones, const int *pos, int nIn) { PvMode m = fixed(semitones); m.kind = STRETCH; m.posTab = pos; m.nIn = nIn; return m; }
     static PvMode stretch_lock(const double *tab, const int *pos, int nIn) { PvMode m; m.kind = STRETCH_LOCKED; m.ratioTab = tab; m.posTab = pos; m.nIn = nIn; return m; }
+    static PvMode cross(const float *voice, const double *depth, int lifter) { PvMode m; m.kind = CROSS; m.voice = voice; m.depth = depth; m.lifter = lifter; return m; }
     bool locked() const { return kind == LOCKED || kind == LOCKED_SUBBIN || kind == STRETCH_LOCKED; }
+    bool enveloped() const { return kind == FORMANT || kind == CROSS; }
 };
 
-// the kernel's arguments from the handle; m null: the plain round trip, whose frames split into *nRuns runs per stream (f64: in double
-// whatever vp_stft_set_precision says -- the cross-synthesis, which splits the same way)
-static VpStftArgs stft_args(const vp_stft *p, const float *d_in, float *d_out, float *d_mag, const PvMode *m, int *nRuns, bool f64 = false)
+// the kernel's arguments from the handle; m null: the plain round trip, whose frames split into *nRuns runs per stream.  The
+// cross-synthesis has no phase-vocoder stage and splits the same way, in double whatever vp_stft_set_precision says
+static VpStftArgs stft_args(const vp_stft *p, const float *d_in, float *d_out, float *d_mag, const PvMode *m, int *nRuns)
 {
+    const bool pv = m && m->kind != PvMode::CROSS;
     VpStftArgs a;
     memset(&a, 0, sizeof a);
     a.in = d_in; a.out = d_out; a.mag = d_mag; a.win = p->win; a.tw1 = p->tw1; a.tw2 = p->tw2; a.tws = p->tws; a.twTop = p->twTop;
-    a.pvRatio = m ? m->ratio : 1.0; a.pv = m ? 1 : 0;
-    a.f32 = (p->f32 && !m && !f64) ? 1 : 0;                    // (the phase-vocoder stage keeps double: its phases accumulate over the stream; f64: so does the cross-synthesis)
+    a.pvRatio = m ? m->ratio : 1.0; a.pv = pv ? 1 : 0;
+    a.f32 = (p->f32 && !m) ? 1 : 0;                            // (the phase-vocoder stage keeps double: its phases accumulate over the stream)
     a.c = (double)p->scale / (double)(p->F / 2);
     a.T = p->T; a.nFrames = p->nFrames; a.F = p->F; a.hop = p->hop; a.O = p->F / p->hop;
     a.nHops = (p->T + p->hop - 1) / p->hop;
@@ -2015,11 +2020,11 @@ static VpStftArgs stft_args(const vp_stft *p, const float *d_in, float *d_out, f
     a.haloRounds = (a.O - 1 + VP_STFT_WAVES - 1) / VP_STFT_WAVES;
     // (float2 loads per lane at 1024 points, float4 at 2048: rows and hops aligned to the load's width)
     const int al = p->F == 2048 ? 4 : 2;
-    a.aligned = (p->T % al == 0 && p->hop % al == 0 && ((uintptr_t)d_in & (4 * al - 1)) == 0) ? 1 : 0;
+    a.aligned = (p->T % al == 0 && p->hop % al == 0 && (((uintptr_t)d_in | (uintptr_t)(m ? m->voice : nullptr)) & (4 * al - 1)) == 0) ? 1 : 0;   // (one flag for both inputs' loads)
     // runs: enough workgroups for two per CU (the kernel's register budget), but runs of at least four rounds per recomputed one;
     // the phase-vocoder stage carries a recurrence over the frames of a stream: one run
     int runs = 1;
-    if (!m) {
+    if (!pv) {
         // (four workgroups per CU in the single-precision build -- half the registers --, three at 2048 points)
         runs = p->runsPerStream > 0 ? p->runsPerStream : ((a.f32 ? (p->F == 2048 ? 3 : 4) : 2) * 256 + p->S - 1) / p->S;
         runs = std::max(1, std::min(runs, a.nRounds / (4 * a.haloRounds)));
@@ -2043,18 +2048,19 @@ static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
     case PvMode::FORMANT: e = vp_stft_launch_formant(a, m->ratioTab, m->formant, m->lifter, p->S, st); break;
     case PvMode::STRETCH: e = vp_stft_launch_stretch(a, m->posTab, m->nIn, p->S, st); break;
     case PvMode::STRETCH_LOCKED: e = vp_stft_launch_stretch_lock(a, m->ratioTab, m->posTab, m->nIn, p->S, st); break;
+    case PvMode::CROSS: e = vp_stft_launch_cross(a, m->voice, m->depth, m->lifter, p->S, nRuns, st); break;
     }
     return e == hipSuccess ? VP_OK : VP_ERR_HIP;
 }
 
 static bool lifter_ok(int lifter) { return lifter >= VP_FORMANT_LIFTER_MIN && lifter <= VP_FORMANT_LIFTER_MAX; }
 
-// every argument of a formant call that the curve call does not have
-static int formant_check(vp_stft *p, int lifter)
+// what a call that takes a cepstral envelope adds to the checks; who: "formant" (the autotune entries' texts say so too) or "cross"
+static int formant_check(vp_stft *p, const char *who, int lifter)
 {
-    if (!lifter_ok(lifter)) { p->lastError = "formant: lifter outside 4 .. 64 samples"; return VP_ERR_INVALID_ARG; }
+    if (!lifter_ok(lifter)) { p->lastError = std::string(who) + ": lifter outside 4 .. 64 samples"; return VP_ERR_INVALID_ARG; }
     if (p->F != 1024) {
-        p->lastError = "formant: 2048-point frames are not built (the envelope needs a wavefront's exchange buffer to hold the frame's 1025 bins; it holds 1024 doubles)";
+        p->lastError = std::string(who) + ": 2048-point frames are not built (the envelope needs a wavefront's exchange buffer to hold the frame's 1025 bins; it holds 1024 doubles)";
         return VP_ERR_GEOMETRY;
     }
     return VP_OK;
@@ -2073,8 +2079,9 @@ static int stft_check(vp_stft *p, const char *who, bool ptrs, const char *what, 
     if (!m) return VP_OK;
     if (m->posTab && m->nIn < p->F) return fail(VP_ERR_INVALID_ARG, "the input row is shorter than one frame");
     if (!(m->semitones >= -12.0 && m->semitones <= 12.0)) return VP_ERR_INVALID_ARG;
-    if (m->kind == PvMode::FORMANT) { const int rc = formant_check(p, m->lifter); if (rc) return rc; }
+    if (m->enveloped()) { const int rc = formant_check(p, m->kind == PvMode::CROSS ? "cross" : "formant", m->lifter); if (rc) return rc; }
     if (m->locked() && p->F != 1024) return fail(VP_ERR_GEOMETRY, "2048-point frames are not built (the peak-locked stage exists for 1024-point frames only)");
+    if (m->kind == PvMode::CROSS) return VP_OK;                // (its kernel needs no more than the default 64 KB of LDS: the device has no verdict to give)
     // (the builds' dynamic-LDS ceiling could not be raised on this device: vp_stft_create)
     if (!p->pvOk) return fail(VP_ERR_HIP, "the device refused the phase-vocoder kernels' LDS size at create");
     return VP_OK;
@@ -2094,7 +2101,7 @@ extern "C" int vp_stft_roundtrip(vp_stft *p, const float *d_in, float *d_out, fl
     return stft_call(p, stft_check(p, nullptr, d_in && d_out, nullptr, nullptr), d_in, d_out, d_mag, nullptr, hip_stream);
 }
 
-// the same round trip with the phase-vocoder pitch shift between the transforms (1024- and 2048-point frames: vp_stft_launch picks the build)
+// the same round trip with the phase-vocoder pitch shift between the transforms (1024- and 2048-point frames: the launcher picks the build)
 extern "C" int vp_stft_pitch_shift(vp_stft *p, const float *d_in, float *d_out, double semitones, void *hip_stream)
 {
     const PvMode m = PvMode::fixed(semitones);
@@ -2125,7 +2132,8 @@ extern "C" int vp_stft_pitch_shift_locked_subbin(vp_stft *p, const float *d_in, 
 
 // the harmonizer (vp_k_stft_harm; 1024-point frames): n_voices peak-locked voices, each along its own ratio curve and with its own gain,
 // and the dry signal, from one analysis of every frame.  Checked before the device is touched, in stft_check's order: handle, pointers,
-// voice count, frame length, the device's verdict at create.  One run per stream, as in the locked call (vp_stft_set_runs has no say)
+// voice count, frame length, the device's verdict at create.  One run per stream, as in the locked call (vp_stft_set_runs has no say).
+// Written out, not a PvMode kind: as a kind its host cost did not stay inside the written-out call's spread (docs/HISTORY.md)
 extern "C" int vp_stft_harmonize(vp_stft *p, const float *d_in, float *d_out, int n_voices, const double *d_ratio, const double *d_gain, const double *d_dry,
                                  void *hip_stream)
 {
@@ -2168,22 +2176,11 @@ extern "C" int vp_stft_time_stretch_locked(vp_stft *p, const float *d_in, int n_
 }
 
 // cross-synthesis (vp_k_stft_cross; 1024-point frames): the carrier takes the plain round trip's path -- its runs included, always in
-// double -- with the voice's envelope imposed between the transforms.  Checked before the device is touched, in stft_check's order: handle,
-// pointers, lifter, frame length (the kernel needs no more than the default 64 KB of LDS: the device has no verdict to give)
+// double -- with the voice's envelope imposed between the transforms
 extern "C" int vp_stft_cross_synth(vp_stft *p, const float *d_voice, const float *d_carrier, float *d_out, const double *d_depth, int lifter, void *hip_stream)
 {
-    const int rc = stft_check(p, "cross", d_voice && d_carrier && d_out, "null voice, carrier or output", nullptr);
-    if (rc) return rc;
-    if (!lifter_ok(lifter)) { p->lastError = "cross: lifter outside 4 .. 64 samples"; return VP_ERR_INVALID_ARG; }
-    if (p->F != 1024) {
-        p->lastError = "cross: 2048-point frames are not built (the envelope needs a wavefront's exchange buffer to hold the frame's 1025 bins; it holds 1024 doubles)";
-        return VP_ERR_GEOMETRY;
-    }
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    int nRuns;
-    VpStftArgs a = stft_args(p, d_carrier, d_out, nullptr, nullptr, &nRuns, true);
-    if (((uintptr_t)d_voice & 7) != 0) a.aligned = 0;                          // (one flag for both inputs' float2 loads)
-    return vp_stft_launch_cross(a, d_voice, d_depth, lifter, p->S, nRuns, (hipStream_t)hip_stream) == hipSuccess ? VP_OK : VP_ERR_HIP;
+    const PvMode m = PvMode::cross(d_voice, d_depth, lifter);
+    return stft_call(p, stft_check(p, "cross", d_voice && d_carrier && d_out, "null voice, carrier or output", &m), d_carrier, d_out, nullptr, &m, hip_stream);
 }
 
 extern "C" int vp_stretch_positions(int *pos, int n_frames, int hop, double stretch, int n_in, int frame_len)
@@ -2274,76 +2271,152 @@ extern "C" int vp_stft_autotune_formant(vp_stft *p, const float *d_in, float *d_
     return stft_autotune(p, d_in, d_out, sample_rate, d_key, d_period, d_ratio, PvMode::form(d_ratio, d_formant, lifter), hip_stream);
 }
 
-// ---- streaming phase vocoder (no reference counterpart): vp_k_pv_stream of vp_stft.hip, the one-shot stage block by block -----------
-struct vp_pv {
+// ---- what the three streaming handles share (vp_pv, vp_xs, vp_hz): the one-shot stage block by block, one state record per stream -------
+struct vp_stream {
     int device = 0, S = 0, N = 0, F = 0, hop = 0, L = 0;
     double *win = nullptr, *tw1 = nullptr, *tw2 = nullptr, *tws = nullptr;
     double c = 0;
-    unsigned char *state = nullptr;             // [S][VP_PV_REC_BYTES] (vp_stft.h)
-    float *stageIn = nullptr, *stageOut = nullptr;   // [S][N]: the host-pointer call's staging
-    hipStream_t ownStream = nullptr;
+    unsigned char *state = nullptr;             // [S][the kind's record] (vp_stft.h)
     long nAllocs = 0;
-    std::vector<double> semi;                   // [S] the interval the next call uses
     // changes made since the last process call, as the updates it carries: the all-stream ones first, then the per-stream ones (a
-    // per-stream change is always newer than a pending all-stream one: an all-stream change clears them)
+    // per-stream change is always newer than a pending all-stream one: an all-stream change clears them).  Only vp_pv has ratios to change
     double allRatio = 0; bool allReset = false;
     std::vector<double> ratioPend;              // [S] 0: none
     std::vector<char> resetPend;                // [S]
-    std::vector<VpPvUpdate> upd;                // staging of the updates (capacity S + 1, reserved at create)
+    std::vector<VpPvUpdate> upd;                // staging of the updates (capacity S + 1, reserved at create: a process call allocates nothing)
+
+    ~vp_stream() { (void)hipFree(win); (void)hipFree(tw1); (void)hipFree(tw2); (void)hipFree(tws); (void)hipFree(state); }
 };
 
-static void pv_free(vp_pv *p)
+// every argument of a create call, in the order a caller can observe (args: what the kind adds to the invalid ones), then the device
+static int stream_create_check(bool args, int device, int n_streams, int block_size, int frame_len, int hop)
 {
-    (void)hipFree(p->win); (void)hipFree(p->tw1); (void)hipFree(p->tw2); (void)hipFree(p->tws);
-    (void)hipFree(p->state); (void)hipFree(p->stageIn); (void)hipFree(p->stageOut);
-    if (p->ownStream) (void)hipStreamDestroy(p->ownStream);
+    if (!args || n_streams <= 0 || block_size <= 0 || frame_len <= 0 || hop <= 0) return VP_ERR_INVALID_ARG;
+    if ((long long)n_streams * block_size > (1LL << 28) || (long long)block_size > (1 << 24)) return VP_ERR_INVALID_ARG;
+    if (frame_len != 1024 || !vp_stft_supported(frame_len, hop)) return VP_ERR_GEOMETRY;
+    return select_device(device);
 }
+
+// the handle of kind H on the selected device: geometry, latency, tables and every stream's record, `rec` bytes of zeros each (no samples
+// received, zero phases, histories and carry) with `ratio` in the double at index ratioAt when there is one; null when memory ran out
+template <class H>
+static H *stream_new(int device, int n_streams, int block_size, int frame_len, int hop, size_t rec, int ratioAt = -1, double ratio = 0.0)
+{
+    H *h = new H();
+    h->device = device; h->S = n_streams; h->N = block_size; h->F = frame_len; h->hop = hop;
+    int g = block_size, b = hop;
+    while (b) { const int t = g % b; g = b; b = t; }
+    h->L = frame_len - g;
+    std::vector<double> w, t1, t2, ts, tt;
+    const float scale = stft_host_tables(frame_len, hop, w, t1, t2, ts, tt);
+    h->c = (double)scale / (double)(frame_len / 2);                      // (as stft_fused)
+    h->ratioPend.assign(n_streams, 0.0);
+    h->resetPend.assign(n_streams, 0);
+    h->upd.reserve(n_streams + 1);
+    std::vector<unsigned char> recs((size_t)n_streams * rec, 0);
+    for (int s = 0; s < n_streams && ratioAt >= 0; s++) memcpy(&recs[(size_t)s * rec + (size_t)ratioAt * 8], &ratio, 8);
+    long *n = &h->nAllocs;
+    if (put(&h->win, w, n) && put(&h->tw1, t1, n) && put(&h->tw2, t2, n) && put(&h->tws, ts, n) && put((void **)&h->state, recs.data(), recs.size(), n)) return h;
+    delete h;
+    return nullptr;
+}
+
+template <class H>
+static int stream_destroy(H *h)
+{
+    if (!h) return VP_ERR_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    delete h;
+    return VP_OK;
+}
+
+static int stream_latency(const vp_stream *h) { return h ? h->L : VP_ERR_INVALID_ARG; }
+static long stream_alloc_count(const vp_stream *h) { return h ? h->nAllocs : VP_ERR_INVALID_ARG; }
+
+static int stream_reset(vp_stream *h, int stream)
+{
+    if (!h || stream < -1 || stream >= h->S) return VP_ERR_INVALID_ARG;
+    if (stream < 0) {
+        h->allReset = true;
+        std::fill(h->resetPend.begin(), h->resetPend.end(), 0);
+    } else h->resetPend[stream] = 1;
+    return VP_OK;
+}
+
+// every argument the process calls share (ok: the kind's pointers and scalars), then the handle's device
+static int stream_enter(const vp_stream *h, bool ok, int n_blocks)
+{
+    if (!h || !ok || n_blocks <= 0 || (long long)n_blocks * h->N > (1 << 28)) return VP_ERR_INVALID_ARG;
+    return hipSetDevice(h->device) == hipSuccess ? VP_OK : VP_ERR_NO_DEVICE;
+}
+
+// the launch arguments every kind takes from the handle (VpPvArgs, VpXsArgs): no blocks, no data, no updates yet
+template <class Args>
+static Args stream_args(const vp_stream *h)
+{
+    Args a;
+    memset(&a, 0, sizeof a);
+    a.state = h->state; a.win = h->win; a.tw1 = h->tw1; a.tw2 = h->tw2; a.tws = h->tws; a.c = h->c;
+    a.S = h->S; a.N = h->N; a.hop = h->hop; a.L = h->L;
+    return a;
+}
+
+// The pending changes travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update-only launches in front of it: no blocks,
+// no data): ordered on the caller's stream, no host memory the device reads later, no allocation.  a: stream_args' and what the kind adds;
+// launch(a, last) launches it, and when `last` first adds the call's data.  A launch that fails leaves the changes pending
+template <class Args, class Launch>
+static int stream_ship(vp_stream *h, Args &a, int n_blocks, Launch launch)
+{
+    h->upd.clear();
+    if (h->allRatio > 0.0 || h->allReset) h->upd.push_back(VpPvUpdate{-1, h->allReset ? 1 : 0, h->allRatio});
+    for (int s = 0; s < h->S; s++)
+        if (h->ratioPend[s] > 0.0 || h->resetPend[s]) h->upd.push_back(VpPvUpdate{s, h->resetPend[s] ? 1 : 0, h->ratioPend[s]});
+    size_t i = 0;
+    while (h->upd.size() - i > VP_PV_MAX_UPDATES) {
+        a.nBlocks = 0; a.nUpd = VP_PV_MAX_UPDATES;
+        std::copy_n(h->upd.data() + i, a.nUpd, a.upd);
+        if (launch(a, false) != hipSuccess) return VP_ERR_HIP;
+        i += a.nUpd;
+    }
+    a.nBlocks = n_blocks; a.nUpd = (int)(h->upd.size() - i);
+    std::copy_n(h->upd.data() + i, a.nUpd, a.upd);
+    if (launch(a, true) != hipSuccess) return VP_ERR_HIP;
+    h->allRatio = 0.0; h->allReset = false;
+    std::fill(h->ratioPend.begin(), h->ratioPend.end(), 0.0);
+    std::fill(h->resetPend.begin(), h->resetPend.end(), 0);
+    return VP_OK;
+}
+
+// ---- streaming phase vocoder (no reference counterpart): vp_k_pv_stream of vp_stft.hip, the one-shot stage block by block -----------
+struct vp_pv : vp_stream {
+    float *stageIn = nullptr, *stageOut = nullptr;   // [S][N]: the host-pointer call's staging
+    hipStream_t ownStream = nullptr;
+    std::vector<double> semi;                   // [S] the interval the next call uses
+
+    ~vp_pv() { (void)hipFree(stageIn); (void)hipFree(stageOut); if (ownStream) (void)hipStreamDestroy(ownStream); }
+};
 
 extern "C" int vp_pv_create(int device, int n_streams, int block_size, int frame_len, int hop, vp_pv **out)
 {
-    if (!out || n_streams <= 0 || block_size <= 0 || frame_len <= 0 || hop <= 0) return VP_ERR_INVALID_ARG;
-    if ((long long)n_streams * block_size > (1LL << 28) || (long long)block_size > (1 << 24)) return VP_ERR_INVALID_ARG;
-    if (frame_len != 1024 || !vp_stft_supported(frame_len, hop)) return VP_ERR_GEOMETRY;
-    if (select_device(device)) return VP_ERR_NO_DEVICE;
+    const int rc = stream_create_check(out != nullptr, device, n_streams, block_size, frame_len, hop);
+    if (rc) return rc;
     if (vp_pv_prepare_device() != hipSuccess || vp_pv_curve_prepare_device() != hipSuccess || vp_pv_formant_prepare_device() != hipSuccess
         || vp_pv_lock_prepare_device() != hipSuccess || vp_pv_lockf_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
-    vp_pv *p = new vp_pv();
-    p->device = device; p->S = n_streams; p->N = block_size; p->F = frame_len; p->hop = hop;
-    int g = block_size, b = hop;
-    while (b) { const int t = g % b; g = b; b = t; }
-    p->L = frame_len - g;
-    std::vector<double> w, t1, t2, ts, tt;
-    const float scale = stft_host_tables(frame_len, hop, w, t1, t2, ts, tt);
-    p->c = (double)scale / (double)(frame_len / 2);                      // (as stft_fused)
-    p->semi.assign(n_streams, 0.0);
-    p->ratioPend.assign(n_streams, 0.0);
-    p->resetPend.assign(n_streams, 0);
-    p->upd.reserve(n_streams + 1);
-    // every stream starts with zero phases, history and carry, ratio 1
-    std::vector<unsigned char> rec((size_t)n_streams * VP_PV_REC_BYTES, 0);
-    for (int s = 0; s < n_streams; s++) { const double one = 1.0; memcpy(&rec[(size_t)s * VP_PV_REC_BYTES + VP_PV_RATIO * 8], &one, 8); }
+    // every stream starts with ratio 1
+    vp_pv *p = stream_new<vp_pv>(device, n_streams, block_size, frame_len, hop, VP_PV_REC_BYTES, VP_PV_RATIO, 1.0);
     const size_t blk = (size_t)n_streams * block_size * sizeof(float);
-    long *n = &p->nAllocs;
-    const bool ok = put(&p->win, w, n) && put(&p->tw1, t1, n) && put(&p->tw2, t2, n) && put(&p->tws, ts, n)
-        && put((void **)&p->state, rec.data(), rec.size(), n) && put((void **)&p->stageIn, nullptr, blk, n) && put((void **)&p->stageOut, nullptr, blk, n)
-        && hipStreamCreateWithFlags(&p->ownStream, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) { pv_free(p); delete p; (void)hipGetLastError(); return VP_ERR_OOM; }
+    if (p && !(put((void **)&p->stageIn, nullptr, blk, &p->nAllocs) && put((void **)&p->stageOut, nullptr, blk, &p->nAllocs)
+               && hipStreamCreateWithFlags(&p->ownStream, hipStreamNonBlocking) == hipSuccess)) { delete p; p = nullptr; }
+    if (!p) { (void)hipGetLastError(); return VP_ERR_OOM; }
+    p->semi.assign(n_streams, 0.0);
     *out = p;
     return VP_OK;
 }
 
-extern "C" int vp_pv_destroy(vp_pv *p)
-{
-    if (!p) return VP_ERR_INVALID_ARG;
-    (void)hipSetDevice(p->device);
-    (void)hipDeviceSynchronize();
-    pv_free(p);
-    delete p;
-    return VP_OK;
-}
-
-extern "C" int vp_pv_get_latency(const vp_pv *p) { return p ? p->L : VP_ERR_INVALID_ARG; }
-extern "C" long vp_pv_debug_alloc_count(const vp_pv *p) { return p ? p->nAllocs : VP_ERR_INVALID_ARG; }
+extern "C" int vp_pv_destroy(vp_pv *p) { return stream_destroy(p); }
+extern "C" int vp_pv_get_latency(const vp_pv *p) { return stream_latency(p); }
+extern "C" long vp_pv_debug_alloc_count(const vp_pv *p) { return stream_alloc_count(p); }
 
 extern "C" int vp_pv_set_semitones(vp_pv *p, int stream, double semitones)
 {
@@ -2367,62 +2440,35 @@ extern "C" int vp_pv_get_semitones(const vp_pv *p, int stream, double *semitones
     return VP_OK;
 }
 
-extern "C" int vp_pv_reset(vp_pv *p, int stream)
-{
-    if (!p || stream < -1 || stream >= p->S) return VP_ERR_INVALID_ARG;
-    if (stream < 0) {
-        p->allReset = true;
-        std::fill(p->resetPend.begin(), p->resetPend.end(), 0);
-    } else p->resetPend[stream] = 1;
-    return VP_OK;
-}
+extern "C" int vp_pv_reset(vp_pv *p, int stream) { return stream_reset(p, stream); }
 
-// the pending changes travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update launches in front of it): ordered on
-// the caller's stream, no host memory the device reads later, no allocation
-// (m: this call's mode -- a table holds one ratio per block and stream, [n_blocks][S]; the pending changes travel and are stored as in
-// any call.  The stream has no position table: the stretch modes do not exist here)
+// one call of mode m on the handle's device, the pending changes with it (stream_ship).  A table holds one ratio per block and stream,
+// [n_blocks][S].  The stream has no position table and the cross-synthesis a stream of its own: no entry makes one of those kinds
 static int pv_run(vp_pv *p, const float *d_in, float *d_out, int n_blocks, hipStream_t st, const PvMode &m)
 {
-    p->upd.clear();
-    if (p->allRatio > 0.0 || p->allReset) p->upd.push_back(VpPvUpdate{-1, p->allReset ? 1 : 0, p->allRatio});
-    for (int s = 0; s < p->S; s++)
-        if (p->ratioPend[s] > 0.0 || p->resetPend[s]) p->upd.push_back(VpPvUpdate{s, p->resetPend[s] ? 1 : 0, p->ratioPend[s]});
-    VpPvArgs a;
-    memset(&a, 0, sizeof a);
-    a.state = p->state; a.win = p->win; a.tw1 = p->tw1; a.tw2 = p->tw2; a.tws = p->tws; a.c = p->c;
-    a.S = p->S; a.N = p->N; a.hop = p->hop; a.O = p->F / p->hop; a.L = p->L;
-    size_t i = 0;
-    while (p->upd.size() - i > VP_PV_MAX_UPDATES) {
-        a.nBlocks = 0; a.nUpd = VP_PV_MAX_UPDATES;
-        for (int k = 0; k < VP_PV_MAX_UPDATES; k++) a.upd[k] = p->upd[i + k];
-        if (vp_pv_launch(a, st) != hipSuccess) return VP_ERR_HIP;
-        i += VP_PV_MAX_UPDATES;
-    }
-    a.in = d_in; a.out = d_out; a.nBlocks = n_blocks; a.nUpd = (int)(p->upd.size() - i);
-    for (int k = 0; k < a.nUpd; k++) a.upd[k] = p->upd[i + k];
-    hipError_t e = hipErrorInvalidValue;
-    switch (m.kind) {
-    case PvMode::FIXED: e = vp_pv_launch(a, st); break;
-    case PvMode::CURVE: e = vp_pv_launch_curve(a, m.ratioTab, st); break;
-    case PvMode::LOCKED: e = vp_pv_launch_lock(a, m.ratioTab, st); break;
-    case PvMode::LOCKED_SUBBIN: e = vp_pv_launch_lockf(a, m.ratioTab, st); break;
-    case PvMode::FORMANT: e = vp_pv_launch_formant(a, m.ratioTab, m.formant, m.lifter, st); break;
-    case PvMode::STRETCH: case PvMode::STRETCH_LOCKED: return VP_ERR_INVALID_ARG;          // (no entry makes one: the stream has no time stretch)
-    }
-    if (e != hipSuccess) return VP_ERR_HIP;
-    p->allRatio = 0.0; p->allReset = false;
-    std::fill(p->ratioPend.begin(), p->ratioPend.end(), 0.0);
-    std::fill(p->resetPend.begin(), p->resetPend.end(), 0);
-    return VP_OK;
+    if (m.kind == PvMode::STRETCH || m.kind == PvMode::STRETCH_LOCKED || m.kind == PvMode::CROSS) return VP_ERR_INVALID_ARG;
+    VpPvArgs a = stream_args<VpPvArgs>(p);
+    a.O = p->F / p->hop;
+    return stream_ship(p, a, n_blocks, [&](VpPvArgs &call, bool last) {
+        if (!last) return vp_pv_launch(call, st);
+        call.in = d_in; call.out = d_out;
+        switch (m.kind) {
+        case PvMode::FIXED: return vp_pv_launch(call, st);                                 // (the ratios the records hold)
+        case PvMode::CURVE: return vp_pv_launch_curve(call, m.ratioTab, st);
+        case PvMode::LOCKED: return vp_pv_launch_lock(call, m.ratioTab, st);
+        case PvMode::LOCKED_SUBBIN: return vp_pv_launch_lockf(call, m.ratioTab, st);
+        case PvMode::FORMANT: return vp_pv_launch_formant(call, m.ratioTab, m.formant, m.lifter, st);
+        case PvMode::STRETCH: case PvMode::STRETCH_LOCKED: case PvMode::CROSS: break;      // (refused above)
+        }
+        return hipErrorInvalidValue;
+    });
 }
 
 // every argument of a streaming call, then the handle's device, then the call.  ptrs: every table the mode requires is there
 static int pv_call(vp_pv *p, const float *d_in, float *d_out, bool ptrs, int n_blocks, const PvMode &m, void *hip_stream)
 {
-    if (!p || !d_in || !d_out || !ptrs || n_blocks <= 0 || (long long)n_blocks * p->N > (1 << 28)) return VP_ERR_INVALID_ARG;
-    if (m.kind == PvMode::FORMANT && !lifter_ok(m.lifter)) return VP_ERR_INVALID_ARG;
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, m);
+    const int rc = stream_enter(p, d_in && d_out && ptrs && (m.kind != PvMode::FORMANT || lifter_ok(m.lifter)), n_blocks);
+    return rc ? rc : pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, m);
 }
 
 extern "C" int vp_pv_process_blocks_device(vp_pv *p, const float *d_in, float *d_out, int n_blocks, void *hip_stream)
@@ -2456,84 +2502,36 @@ extern "C" int vp_pv_process_blocks_formant_device(vp_pv *p, const float *d_in, 
 
 extern "C" int vp_pv_process_block(vp_pv *p, const float *in, float *out)
 {
-    if (!p || !in || !out) return VP_ERR_INVALID_ARG;
-    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    int rc = stream_enter(p, in && out, 1);
+    if (rc) return rc;
     const size_t bytes = (size_t)p->S * p->N * sizeof(float);
     if (hipMemcpyAsync(p->stageIn, in, bytes, hipMemcpyHostToDevice, p->ownStream) != hipSuccess) return VP_ERR_HIP;
-    const int rc = pv_run(p, p->stageIn, p->stageOut, 1, p->ownStream, PvMode::held());
+    rc = pv_run(p, p->stageIn, p->stageOut, 1, p->ownStream, PvMode::held());
     if (rc) return rc;
     if (hipMemcpyAsync(out, p->stageOut, bytes, hipMemcpyDeviceToHost, p->ownStream) != hipSuccess) return VP_ERR_HIP;
     return hipStreamSynchronize(p->ownStream) == hipSuccess ? VP_OK : VP_ERR_HIP;
 }
 
 // ---- streaming cross-synthesis (no reference counterpart): vp_k_xs_stream of vp_stft_cross.inc, the one-shot stage block by block ------
-struct vp_xs {
-    int device = 0, S = 0, N = 0, F = 0, hop = 0, L = 0;
-    double *win = nullptr, *tw1 = nullptr, *tw2 = nullptr, *tws = nullptr;
-    double c = 0;
-    unsigned char *state = nullptr;             // [S][VP_XS_REC_BYTES] (vp_stft.h)
-    long nAllocs = 0;
-    // resets made since the last process call, as the updates it carries (an all-stream reset clears the per-stream ones)
-    bool allReset = false;
-    std::vector<char> resetPend;                // [S]
-    std::vector<VpPvUpdate> upd;                // staging of the updates (capacity S + 1, reserved at create)
-};
-
-static void xs_free(vp_xs *x)
-{
-    (void)hipFree(x->win); (void)hipFree(x->tw1); (void)hipFree(x->tw2); (void)hipFree(x->tws); (void)hipFree(x->state);
-}
+struct vp_xs : vp_stream {};
 
 extern "C" int vp_xs_create(int device, int n_streams, int block_size, int frame_len, int hop, vp_xs **out)
 {
-    if (!out || n_streams <= 0 || block_size <= 0 || frame_len <= 0 || hop <= 0) return VP_ERR_INVALID_ARG;
-    if ((long long)n_streams * block_size > (1LL << 28) || (long long)block_size > (1 << 24)) return VP_ERR_INVALID_ARG;
-    if (frame_len != 1024 || !vp_stft_supported(frame_len, hop)) return VP_ERR_GEOMETRY;
-    if (select_device(device)) return VP_ERR_NO_DEVICE;
-    vp_xs *x = new vp_xs();
-    x->device = device; x->S = n_streams; x->N = block_size; x->F = frame_len; x->hop = hop;
-    int g = block_size, b = hop;
-    while (b) { const int t = g % b; g = b; b = t; }
-    x->L = frame_len - g;
-    std::vector<double> w, t1, t2, ts, tt;
-    const float scale = stft_host_tables(frame_len, hop, w, t1, t2, ts, tt);
-    x->c = (double)scale / (double)(frame_len / 2);                      // (as stft_fused)
-    x->resetPend.assign(n_streams, 0);
-    x->upd.reserve(n_streams + 1);
-    // every stream starts with no samples received, zero histories and carry
-    std::vector<unsigned char> rec((size_t)n_streams * VP_XS_REC_BYTES, 0);
-    long *n = &x->nAllocs;
-    const bool ok = put(&x->win, w, n) && put(&x->tw1, t1, n) && put(&x->tw2, t2, n) && put(&x->tws, ts, n)
-        && put((void **)&x->state, rec.data(), rec.size(), n);
-    if (!ok) { xs_free(x); delete x; (void)hipGetLastError(); return VP_ERR_OOM; }
+    const int rc = stream_create_check(out != nullptr, device, n_streams, block_size, frame_len, hop);
+    if (rc) return rc;
+    vp_xs *x = stream_new<vp_xs>(device, n_streams, block_size, frame_len, hop, VP_XS_REC_BYTES);
+    if (!x) { (void)hipGetLastError(); return VP_ERR_OOM; }
     *out = x;
     return VP_OK;
 }
 
-extern "C" int vp_xs_destroy(vp_xs *x)
-{
-    if (!x) return VP_ERR_INVALID_ARG;
-    (void)hipSetDevice(x->device);
-    (void)hipDeviceSynchronize();
-    xs_free(x);
-    delete x;
-    return VP_OK;
-}
+extern "C" int vp_xs_destroy(vp_xs *x) { return stream_destroy(x); }
+extern "C" int vp_xs_get_latency(const vp_xs *x) { return stream_latency(x); }
+extern "C" long vp_xs_debug_alloc_count(const vp_xs *x) { return stream_alloc_count(x); }
+extern "C" int vp_xs_reset(vp_xs *x, int stream) { return stream_reset(x, stream); }
 
-extern "C" int vp_xs_get_latency(const vp_xs *x) { return x ? x->L : VP_ERR_INVALID_ARG; }
-extern "C" long vp_xs_debug_alloc_count(const vp_xs *x) { return x ? x->nAllocs : VP_ERR_INVALID_ARG; }
-
-extern "C" int vp_xs_reset(vp_xs *x, int stream)
-{
-    if (!x || stream < -1 || stream >= x->S) return VP_ERR_INVALID_ARG;
-    if (stream < 0) {
-        x->allReset = true;
-        std::fill(x->resetPend.begin(), x->resetPend.end(), 0);
-    } else x->resetPend[stream] = 1;
-    return VP_OK;
-}
-
-// the pending resets travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update launches in front of it), as pv_run's do
+// Written out, not through stream_enter / stream_ship: through them the call cost the host 0.05-0.2 us more (docs/HISTORY.md).  The
+// pending resets travel as stream_ship's do; this handle has no ratios to change
 extern "C" int vp_xs_process_blocks_device(vp_xs *x, const float *d_voice, const float *d_carrier, float *d_out, const double *d_depth, int lifter,
                                            int n_blocks, void *hip_stream)
 {
@@ -2551,12 +2549,12 @@ extern "C" int vp_xs_process_blocks_device(vp_xs *x, const float *d_voice, const
     size_t i = 0;
     while (x->upd.size() - i > VP_PV_MAX_UPDATES) {
         a.nBlocks = 0; a.nUpd = VP_PV_MAX_UPDATES;
-        for (int k = 0; k < VP_PV_MAX_UPDATES; k++) a.upd[k] = x->upd[i + k];
+        std::copy_n(x->upd.data() + i, a.nUpd, a.upd);
         if (vp_xs_launch(a, st) != hipSuccess) return VP_ERR_HIP;
-        i += VP_PV_MAX_UPDATES;
+        i += a.nUpd;
     }
     a.voice = d_voice; a.carrier = d_carrier; a.out = d_out; a.depth = d_depth; a.nBlocks = n_blocks; a.nUpd = (int)(x->upd.size() - i);
-    for (int k = 0; k < a.nUpd; k++) a.upd[k] = x->upd[i + k];
+    std::copy_n(x->upd.data() + i, a.nUpd, a.upd);
     if (vp_xs_launch(a, st) != hipSuccess) return VP_ERR_HIP;
     x->allReset = false;
     std::fill(x->resetPend.begin(), x->resetPend.end(), 0);
@@ -2564,101 +2562,40 @@ extern "C" int vp_xs_process_blocks_device(vp_xs *x, const float *d_voice, const
 }
 
 // ---- streaming harmonizer (no reference counterpart): vp_k_hz_stream of vp_stft_harm.inc, vp_stft_harmonize block by block ---------------
-struct vp_hz {
-    int device = 0, S = 0, N = 0, F = 0, hop = 0, L = 0, V = 0;
-    double *win = nullptr, *tw1 = nullptr, *tw2 = nullptr, *tws = nullptr;
-    double c = 0;
-    unsigned char *state = nullptr;             // [S][VP_HZ_REC_BYTES] (vp_stft.h)
-    long nAllocs = 0;
-    // resets made since the last process call, as the updates it carries (an all-stream reset clears the per-stream ones)
-    bool allReset = false;
-    std::vector<char> resetPend;                // [S]
-    std::vector<VpPvUpdate> upd;                // staging of the updates (capacity S + 1, reserved at create)
+struct vp_hz : vp_stream {
+    int V = 0;
 };
-
-static void hz_free(vp_hz *h)
-{
-    (void)hipFree(h->win); (void)hipFree(h->tw1); (void)hipFree(h->tw2); (void)hipFree(h->tws); (void)hipFree(h->state);
-}
 
 extern "C" int vp_hz_create(int device, int n_streams, int block_size, int frame_len, int hop, int n_voices, vp_hz **out)
 {
-    if (!out || n_streams <= 0 || block_size <= 0 || frame_len <= 0 || hop <= 0 || n_voices < 1 || n_voices > VP_HARM_MAX_VOICES) return VP_ERR_INVALID_ARG;
-    if ((long long)n_streams * block_size > (1LL << 28) || (long long)block_size > (1 << 24)) return VP_ERR_INVALID_ARG;
-    if (frame_len != 1024 || !vp_stft_supported(frame_len, hop)) return VP_ERR_GEOMETRY;
-    if (select_device(device)) return VP_ERR_NO_DEVICE;
+    const int rc = stream_create_check(out && n_voices >= 1 && n_voices <= VP_HARM_MAX_VOICES, device, n_streams, block_size, frame_len, hop);
+    if (rc) return rc;
     if (vp_hz_prepare_device() != hipSuccess) { (void)hipGetLastError(); return VP_ERR_HIP; }
-    vp_hz *h = new vp_hz();
-    h->device = device; h->S = n_streams; h->N = block_size; h->F = frame_len; h->hop = hop; h->V = n_voices;
-    int g = block_size, b = hop;
-    while (b) { const int t = g % b; g = b; b = t; }
-    h->L = frame_len - g;
-    std::vector<double> w, t1, t2, ts, tt;
-    const float scale = stft_host_tables(frame_len, hop, w, t1, t2, ts, tt);
-    h->c = (double)scale / (double)(frame_len / 2);                      // (as stft_fused)
-    h->resetPend.assign(n_streams, 0);
-    h->upd.reserve(n_streams + 1);
-    // every stream starts with no samples received, zero phases, angles, history and carry
-    std::vector<unsigned char> rec((size_t)n_streams * VP_HZ_REC_BYTES, 0);
-    long *n = &h->nAllocs;
-    const bool ok = put(&h->win, w, n) && put(&h->tw1, t1, n) && put(&h->tw2, t2, n) && put(&h->tws, ts, n)
-        && put((void **)&h->state, rec.data(), rec.size(), n);
-    if (!ok) { hz_free(h); delete h; (void)hipGetLastError(); return VP_ERR_OOM; }
+    vp_hz *h = stream_new<vp_hz>(device, n_streams, block_size, frame_len, hop, VP_HZ_REC_BYTES);
+    if (!h) { (void)hipGetLastError(); return VP_ERR_OOM; }
+    h->V = n_voices;
     *out = h;
     return VP_OK;
 }
 
-extern "C" int vp_hz_destroy(vp_hz *h)
-{
-    if (!h) return VP_ERR_INVALID_ARG;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    hz_free(h);
-    delete h;
-    return VP_OK;
-}
+extern "C" int vp_hz_destroy(vp_hz *h) { return stream_destroy(h); }
+extern "C" int vp_hz_get_latency(const vp_hz *h) { return stream_latency(h); }
+extern "C" long vp_hz_debug_alloc_count(const vp_hz *h) { return stream_alloc_count(h); }
+extern "C" int vp_hz_reset(vp_hz *h, int stream) { return stream_reset(h, stream); }
 
-extern "C" int vp_hz_get_latency(const vp_hz *h) { return h ? h->L : VP_ERR_INVALID_ARG; }
-extern "C" long vp_hz_debug_alloc_count(const vp_hz *h) { return h ? h->nAllocs : VP_ERR_INVALID_ARG; }
-
-extern "C" int vp_hz_reset(vp_hz *h, int stream)
-{
-    if (!h || stream < -1 || stream >= h->S) return VP_ERR_INVALID_ARG;
-    if (stream < 0) {
-        h->allReset = true;
-        std::fill(h->resetPend.begin(), h->resetPend.end(), 0);
-    } else h->resetPend[stream] = 1;
-    return VP_OK;
-}
-
-// the pending resets travel in the call's arguments (beyond VP_PV_MAX_UPDATES of them, in update launches in front of it), as pv_run's do
+// (an update-only launch has no tables either)
 extern "C" int vp_hz_process_blocks_device(vp_hz *h, const float *d_in, float *d_out, const double *d_ratio, const double *d_gain, const double *d_dry,
                                            int n_blocks, void *hip_stream)
 {
-    if (!h || !d_in || !d_out || !d_ratio || n_blocks <= 0 || (long long)n_blocks * h->N > (1 << 28)) return VP_ERR_INVALID_ARG;
-    if (hipSetDevice(h->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    const hipStream_t st = (hipStream_t)hip_stream;
-    h->upd.clear();
-    if (h->allReset) h->upd.push_back(VpPvUpdate{-1, 1, 0.0});
-    for (int s = 0; s < h->S; s++)
-        if (h->resetPend[s]) h->upd.push_back(VpPvUpdate{s, 1, 0.0});
-    VpPvArgs a;
-    memset(&a, 0, sizeof a);
-    a.state = h->state; a.win = h->win; a.tw1 = h->tw1; a.tw2 = h->tw2; a.tws = h->tws; a.c = h->c;
-    a.S = h->S; a.N = h->N; a.hop = h->hop; a.O = h->F / h->hop; a.L = h->L;
-    size_t i = 0;
-    while (h->upd.size() - i > VP_PV_MAX_UPDATES) {
-        a.nBlocks = 0; a.nUpd = VP_PV_MAX_UPDATES;
-        for (int k = 0; k < VP_PV_MAX_UPDATES; k++) a.upd[k] = h->upd[i + k];
-        if (vp_hz_launch(a, nullptr, nullptr, nullptr, h->V, st) != hipSuccess) return VP_ERR_HIP;
-        i += VP_PV_MAX_UPDATES;
-    }
-    a.in = d_in; a.out = d_out; a.nBlocks = n_blocks; a.nUpd = (int)(h->upd.size() - i);
-    for (int k = 0; k < a.nUpd; k++) a.upd[k] = h->upd[i + k];
-    if (vp_hz_launch(a, d_ratio, d_gain, d_dry, h->V, st) != hipSuccess) return VP_ERR_HIP;
-    h->allReset = false;
-    std::fill(h->resetPend.begin(), h->resetPend.end(), 0);
-    return VP_OK;
+    const int rc = stream_enter(h, d_in && d_out && d_ratio, n_blocks);
+    if (rc) return rc;
+    VpPvArgs a = stream_args<VpPvArgs>(h);
+    a.O = h->F / h->hop;
+    return stream_ship(h, a, n_blocks, [&](VpPvArgs &call, bool last) {
+        if (!last) return vp_hz_launch(call, nullptr, nullptr, nullptr, h->V, (hipStream_t)hip_stream);
+        call.in = d_in; call.out = d_out;
+        return vp_hz_launch(call, d_ratio, d_gain, d_dry, h->V, (hipStream_t)hip_stream);
+    });
 }
 
 // ---- streaming pitch tracker of the phase-vocoder stream (csrc/vp_track.hip): vp_k_yin_track_stream, then vp_k_track_follow -----------

@@ -214,11 +214,22 @@ def _both_channels(y, lens, offset=0):
     return [np.ascontiguousarray(np.stack([y[s, offset:offset + n]] * 2)) for s, n in enumerate(lens)]
 
 
-def _check_formant(formant, lifter):
-    if formant is not None and not -12.0 <= float(formant) <= 12.0:
-        raise ValueError("formant: an interval within +-12 semitones expected")
-    if formant is not None and not 4 <= int(lifter) <= 64:
+def _check_lifter(lifter):
+    if not 4 <= int(lifter) <= 64:
         raise ValueError("lifter: 4 to 64 samples expected")
+
+
+def _check_formant(formant, lifter):
+    if formant is None:
+        return
+    if not -12.0 <= float(formant) <= 12.0:
+        raise ValueError("formant: an interval within +-12 semitones expected")
+    _check_lifter(lifter)
+
+
+def _overlapped(n, hop, F=1024):
+    """The length of a one-shot batch whose first n samples all lie under the full overlap of F-point frames."""
+    return F + -(-int(n) // hop) * hop
 
 
 def _check_locked(locked, formant, F=1024):
@@ -246,11 +257,13 @@ def _mode_kw(formant, lifter, locked, formant_name="formant", subbin=False):
 SHIFT_RANGE = (-12.0, 12.0, "shift: intervals within +-12 semitones expected")
 
 
-def _stream(processor, S, N, hop, device):
+def _stream(processor, S, N, hop, device, cls=None, **kw):
+    """`processor` (the tests' double) or a new streaming processor: a PhaseVocoderStream, or `cls` with what else its constructor takes."""
     if processor is not None:
         return processor
-    from . import PhaseVocoderStream
-    return PhaseVocoderStream(S, int(N), hop=int(hop), device=device)
+    if cls is None:
+        from . import PhaseVocoderStream as cls
+    return cls(S, int(N), hop=int(hop), device=device, **kw)
 
 
 def pv_shift(voices, shift, N=1024, hop=256, device=0, processor=None):
@@ -366,7 +379,7 @@ def pv_shift_formant(voices, shift, formant=0.0, lifter=32, N=1024, hop=256, dev
         y = p.run(_pack_mono(voices, lens, max(lens)), blocks_per_call=int(blocks_per_call), curve=np.array([per]), formant_semitones=float(formant),
                   lifter=int(lifter))
     else:
-        x = _pack_mono(voices, lens, 1024 + -(-max(lens) // hop) * hop)        # every sample under the full overlap of frames
+        x = _pack_mono(voices, lens, _overlapped(max(lens), hop))
         p = processor if processor is not None else _FormantShiftRunner(hop, device)
         y = p.run(x, per, float(formant), int(lifter))
     return _both_channels(y, lens)
@@ -402,7 +415,7 @@ def pv_stretch(voices, stretch, shift=0.0, F=1024, hop=256, device=0, processor=
     lens = _lengths(voices)
     outs = [int(np.ceil(n * a)) for n, a in zip(lens, per)]
     x = _pack_mono(voices, lens, max(max(lens), F))
-    T = F + -(-max(outs) // hop) * hop                                         # every output sample under the full overlap of frames
+    T = _overlapped(max(outs), hop, F)
     nF = (T - F) // hop + 1
     # (the formula of vp_stretch_positions, against each recording's own length: behind its end a recording repeats its last frame)
     pos = np.stack([np.minimum(np.floor(np.arange(nF, dtype=np.int64) * hop / a), max(n, F) - F) for n, a in zip(lens, per)]).astype(np.int32)
@@ -429,7 +442,7 @@ def tune_length(max_len, fs, F, hop):
     """Common row length of a pvtune batch: every sample of the longest recording under the full overlap of frames, and never shorter than
     the tracker's window of F + ceil(fs / 100) samples."""
     F, hop = int(F), int(hop)
-    return max(F + -(-int(max_len) // hop) * hop, F + int(np.ceil(float(fs) / 100.0)))
+    return max(_overlapped(max_len, hop, F), F + int(np.ceil(float(fs) / 100.0)))
 
 
 def _check_tune(voices, fs, key, formant, lifter):
@@ -574,20 +587,17 @@ def pv_cross(voices, carriers, depth=1.0, lifter=32, F=1024, hop=256, N=1024, st
     run(voice, carrier, blocks_per_call, depth, lifter) (stream) to use instead of the GPU."""
     S = _batch_size(voices)
     per = _per_recording(depth, S, "depth", float, 0.0, 1.0, "depth: values within [0, 1] expected")
-    if not 4 <= int(lifter) <= 64:
-        raise ValueError("lifter: 4 to 64 samples expected")
+    _check_lifter(lifter)
     if int(F) != 1024:
         raise ValueError("pvcross: 1024-point frames expected (the cross-synthesis kernels are not built for 2048)")
     hop = int(hop)
     lens = _lengths(voices)
-    T = max(lens) if stream else 1024 + -(-max(lens) // hop) * hop             # (batch: every sample under the full overlap of frames)
+    T = max(lens) if stream else _overlapped(max(lens), hop)
     v = _pack_mono(voices, lens, T)
     c = _pack_carriers(carriers, S, lens, T)
     if stream:
-        if processor is None:
-            from . import CrossSynthStream
-            processor = CrossSynthStream(S, int(N), hop=hop, device=device)
-        y = processor.run(v, c, blocks_per_call=int(blocks_per_call), depth=per, lifter=int(lifter))
+        from . import CrossSynthStream
+        y = _stream(processor, S, N, hop, device, CrossSynthStream).run(v, c, blocks_per_call=int(blocks_per_call), depth=per, lifter=int(lifter))
     else:
         p = processor if processor is not None else _CrossRunner(F, hop, device)
         y = p.run(v, c, per, int(lifter))
@@ -638,14 +648,13 @@ def pv_harmonize(voices, intervals, gains=None, dry=1.0, F=1024, hop=256, N=1024
     gtab = np.tile(np.array(g, np.float64), (S, 1))
     if stream:
         x = _pack_mono(voices, lens, max(lens))
-        if processor is None:
-            from . import HarmonizerStream
-            processor = HarmonizerStream(S, N, V, hop=hop, device=device)
+        from . import HarmonizerStream
+        processor = _stream(processor, S, N, hop, device, HarmonizerStream, n_voices=V)
         nb = -(-(max(lens) + int(processor.latency)) // N)
         st = np.tile(np.array(iv, np.float64), (nb, S, 1))
         y = processor.run(x, semitones=st, blocks_per_call=int(blocks_per_call), gains=gtab, dry=per)
     else:
-        T = 1024 + -(-max(lens) // hop) * hop                                  # (every sample under the full overlap of frames)
+        T = _overlapped(max(lens), hop)
         x = _pack_mono(voices, lens, T)
         nF = (T - 1024) // hop + 1
         st = np.tile(np.array(iv, np.float64)[None, :, None], (S, 1, nF))

@@ -719,17 +719,86 @@ def _harm_levels(owner, V, gains, dry, dev):
     return table(gains, "gains", (S, V), [(V,), (S, V)], "gain"), table(dry, "dry", (S,), [(), (S,)], "dry")
 
 
-class StftRoundTrip:
-    """Standalone batched STFT -> iSTFT (no reference counterpart; see include/vp_amd.h vp_stft_*)."""
+class _Handle:
+    """The lifecycle of a library handle: <_prefix>_create or VpError, _chk for every later call, close() and __del__ through
+    <_prefix>_destroy."""
+    _prefix = None
 
-    def __init__(self, n_streams, n_samples, frame_len=1024, hop=256, device=0):
+    def _open(self, *args):
         self.L = load_library()
+        self._destroy = getattr(self.L, self._prefix + "_destroy")
         h = C.c_void_p()
-        rc = self.L.vp_stft_create(int(device), int(n_streams), int(n_samples), int(frame_len), int(hop), C.byref(h))
+        self._chk(getattr(self.L, self._prefix + "_create")(*args, C.byref(h)))
+        self.h = h
+
+    def _chk(self, rc):
         if rc:
             raise VpError(rc, self.L.vp_error_string(rc).decode())
-        self.h, self.S, self.T, self.F, self.hop = h, n_streams, n_samples, frame_len, hop
-        self.n_frames = self.L.vp_stft_num_frames(h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _StreamHandle(_Handle):
+    """... of a handle that keeps per-stream state across process calls: reset() and the allocation count too."""
+
+    def _open(self, *args):
+        try:
+            import torch  # noqa: F401  (run() and process_device() use torch: load its HIP runtime before the library loads one)
+        except ImportError:
+            pass
+        super()._open(*args)
+        self._reset, self._alloc_count = getattr(self.L, self._prefix + "_reset"), getattr(self.L, self._prefix + "_debug_alloc_count")
+
+    def reset(self, stream=-1):
+        """The stream (-1: all) starts again like a fresh one at the next process call (a PhaseVocoderStream's interval stays; a tracker
+        has no history and no held ratio)."""
+        self._chk(self._reset(self.h, int(stream)))
+
+    def debug_alloc_count(self):
+        return self._alloc_count(self.h)
+
+
+class _BlockStream(_StreamHandle):
+    """... of a stream of audio blocks [S][N] in and out: what the run() methods share.  Each kind has its `latency`."""
+
+    def _n_blocks(self, T):
+        """(n_blocks, latency) of a run over T samples: the input padded with `latency` zeros and up to whole blocks."""
+        lat = self.latency
+        return -(-(T + lat) // self.N), lat
+
+    def _slab(self, x, nb):
+        """The host array [S][T], zero-padded to nb blocks, as the device slab [nb][S][N]."""
+        import torch
+        xp = np.zeros((self.S, nb * self.N), np.float32)
+        xp[:, :x.shape[1]] = x
+        return torch.from_numpy(np.ascontiguousarray(xp.reshape(self.S, nb, self.N).transpose(1, 0, 2))).to(torch.device("cuda", self.device))
+
+    def _trimmed(self, d_out, T, lat):
+        """The device slab [nb][S][N], once its stream's work is done, as the host array [S][T] aligned with the input: the first `lat`
+        samples dropped."""
+        import torch
+        torch.cuda.synchronize(d_out.device)
+        y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, -1)
+        return np.ascontiguousarray(y[:, lat:lat + T])
+
+
+class StftRoundTrip(_Handle):
+    """Standalone batched STFT -> iSTFT (no reference counterpart; see include/vp_amd.h vp_stft_*)."""
+    _prefix = "vp_stft"
+
+    def __init__(self, n_streams, n_samples, frame_len=1024, hop=256, device=0):
+        self._open(int(device), int(n_streams), int(n_samples), int(frame_len), int(hop))
+        self.S, self.T, self.F, self.hop = n_streams, n_samples, frame_len, hop
+        self.n_frames = self.L.vp_stft_num_frames(self.h)
         self._curve_tables, self._stretch_tables = {}, {}      # device ratio / position tables, one per shape, allocated at first use
 
     def __call__(self, d_in, d_out, d_mag=None, stream=None):
@@ -743,23 +812,15 @@ class StftRoundTrip:
 
     def set_runs(self, runs_per_stream):
         """Diagnostic: runs of frames (workgroups) per stream, 0 = automatic; the output does not depend on it."""
-        rc = self.L.vp_stft_set_runs(self.h, int(runs_per_stream))
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
+        self._chk(self.L.vp_stft_set_runs(self.h, int(runs_per_stream)))
 
     def set_precision(self, precision):
         """"f64" (default) or "f32": arithmetic of the round trip's transforms (vp_stft_set_precision)."""
-        rc = self.L.vp_stft_set_precision(self.h, {"f64": 0, "f32": 1}[precision])
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
+        self._chk(self.L.vp_stft_set_precision(self.h, {"f64": 0, "f32": 1}[precision]))
 
     @property
     def precision(self):
         return "f32" if self.L.vp_stft_get_precision(self.h) == 1 else "f64"
-
-    def _chk(self, rc):
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
 
     def _io(self, d_in, d_out, any_length=False):
         """The contract of a call's input and output: device float32 [S][n_samples], contiguous (any_length: the input is [S][n_in] with
@@ -980,44 +1041,18 @@ class StftRoundTrip:
             self._track_chk(self.L.vp_stft_autotune(*head, _stream_of(stream, d_in)))
         return period, ratio
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.vp_stft_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PhaseVocoderStream:
+class PhaseVocoderStream(_BlockStream):
     """Streaming phase-vocoder pitch shifter: `n_streams` independent streams, blocks of `block_size` samples, state kept across
     calls (include/vp_amd.h vp_pv_*).  Output sample t of a stream is sample t - latency of what StftRoundTrip.pitch_shift gives on
     everything the stream has received, bit for bit; the first `latency` samples are 0."""
+    _prefix = "vp_pv"
+    latency = property(lambda self: self.L.vp_pv_get_latency(self.h), doc="F - gcd(N, hop) samples.")
 
     def __init__(self, n_streams, block_size, hop=256, frame_len=1024, device=0):
-        try:
-            import torch  # noqa: F401  (run() and process_device() use torch: load its HIP runtime before the library loads one)
-        except ImportError:
-            pass
-        self.L = load_library()
-        h = C.c_void_p()
-        rc = self.L.vp_pv_create(int(device), int(n_streams), int(block_size), int(frame_len), int(hop), C.byref(h))
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
-        self.h, self.S, self.N, self.hop, self.F, self.device = h, int(n_streams), int(block_size), int(hop), int(frame_len), device
+        self._open(int(device), int(n_streams), int(block_size), int(frame_len), int(hop))
+        self.S, self.N, self.hop, self.F, self.device = int(n_streams), int(block_size), int(hop), int(frame_len), device
         self._curve_tables = {}                                # device ratio tables, one per n_blocks, allocated at first use
-
-    def _chk(self, rc):
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
-
-    @property
-    def latency(self):
-        """F - gcd(N, hop) samples."""
-        return self.L.vp_pv_get_latency(self.h)
 
     def set_semitones(self, v, stream=-1):
         """Interval in [-12, 12] for one stream or (-1) all; takes effect at the next process call."""
@@ -1027,10 +1062,6 @@ class PhaseVocoderStream:
         v = C.c_double()
         self._chk(self.L.vp_pv_get_semitones(self.h, int(stream), C.byref(v)))
         return v.value
-
-    def reset(self, stream=-1):
-        """The stream (-1: all) starts again like a fresh one at the next process call; its interval stays."""
-        self._chk(self.L.vp_pv_reset(self.h, int(stream)))
 
     def process(self, x):
         """One block from host memory: float32 [S][N] -> [S][N] (synchronous)."""
@@ -1152,16 +1183,13 @@ class PhaseVocoderStream:
         import torch
         x = np.asarray(x, dtype=np.float32)
         assert x.ndim == 2 and x.shape[0] == self.S, x.shape
-        T, Lat, N = x.shape[1], self.latency, self.N
-        nb = -(-(T + Lat) // N)
-        xp = np.zeros((self.S, nb * N), np.float32)
-        xp[:, :T] = x
+        T = x.shape[1]
+        nb, lat = self._n_blocks(T)
         if curve is not None:
             curve = np.asarray(curve, dtype=np.float64)
             assert curve.ndim in (1, 2) and curve.shape[0] >= 1 and (curve.ndim == 1 or curve.shape[1] == self.S), curve.shape
             curve = curve[np.minimum(np.arange(nb), curve.shape[0] - 1)]
-        dev = torch.device("cuda", self.device)
-        d_in = torch.from_numpy(np.ascontiguousarray(xp.reshape(self.S, nb, N).transpose(1, 0, 2))).to(dev)
+        d_in = self._slab(x, nb)
         d_out = torch.empty_like(d_in)
         b, tables = 0, []
         while b < nb:
@@ -1175,57 +1203,22 @@ class PhaseVocoderStream:
                 self.process_device(d_in[b:b + k], d_out[b:b + k], n_blocks=k, semitones_per_block=curve[b:b + k], formant_semitones=formant_semitones,
                                     lifter=lifter, **lk)
             b += k
-        torch.cuda.synchronize(dev)
-        y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, nb * N)
-        y = np.ascontiguousarray(y[:, Lat:Lat + T])
+        y = self._trimmed(d_out, T, lat)
         if autotune is not None:
             return y, torch.cat([p for p, _ in tables]).cpu().numpy(), torch.cat([r for _, r in tables]).cpu().numpy()
         return y
 
-    def debug_alloc_count(self):
-        return self.L.vp_pv_debug_alloc_count(self.h)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.vp_pv_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class CrossSynthStream:
+class CrossSynthStream(_BlockStream):
     """Streaming STFT cross-synthesis: `n_streams` independent pairs of voice and carrier, blocks of `block_size` samples, state kept
     across calls (include/vp_amd.h vp_xs_*).  Output sample t of a stream is sample t - latency of what StftRoundTrip.cross_synth gives
     on everything the stream has received, bit for bit; the first `latency` samples are 0."""
+    _prefix = "vp_xs"
+    latency = property(lambda self: self.L.vp_xs_get_latency(self.h), doc="F - gcd(N, hop) samples.")
 
     def __init__(self, n_streams, block_size, hop=256, frame_len=1024, device=0):
-        try:
-            import torch  # noqa: F401  (run() and process_device() use torch: load its HIP runtime before the library loads one)
-        except ImportError:
-            pass
-        self.L = load_library()
-        h = C.c_void_p()
-        rc = self.L.vp_xs_create(int(device), int(n_streams), int(block_size), int(frame_len), int(hop), C.byref(h))
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
-        self.h, self.S, self.N, self.hop, self.F, self.device = h, int(n_streams), int(block_size), int(hop), int(frame_len), device
-
-    def _chk(self, rc):
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
-
-    @property
-    def latency(self):
-        """F - gcd(N, hop) samples."""
-        return self.L.vp_xs_get_latency(self.h)
-
-    def reset(self, stream=-1):
-        """The stream (-1: all) starts again like a fresh one at the next process call."""
-        self._chk(self.L.vp_xs_reset(self.h, int(stream)))
+        self._open(int(device), int(n_streams), int(block_size), int(frame_len), int(hop))
+        self.S, self.N, self.hop, self.F, self.device = int(n_streams), int(block_size), int(hop), int(frame_len), device
 
     def process_device(self, d_voice, d_carrier, d_out, n_blocks=1, depth=1.0, lifter=FORMANT_LIFTER, stream=None, d_depth=None):
         """n_blocks blocks on the device: torch float32 [n_blocks][S][N] each (or [S][N] for one block), enqueued on `stream` (default: the
@@ -1250,69 +1243,28 @@ class CrossSynthStream:
             raise ValueError(f"cross_synth: voice {v.shape} and carrier {c.shape}: two arrays [{self.S}][T] expected")
         if not 4 <= int(lifter) <= 64:
             raise ValueError("cross_synth: lifter: 4 to 64 samples expected")
-        T, Lat, N = v.shape[1], self.latency, self.N
-        nb = -(-(T + Lat) // N)
-        dev = torch.device("cuda", self.device)
-
-        def slab(x):
-            xp = np.zeros((self.S, nb * N), np.float32)
-            xp[:, :T] = x
-            return torch.from_numpy(np.ascontiguousarray(xp.reshape(self.S, nb, N).transpose(1, 0, 2))).to(dev)
-        d_v, d_c = slab(v), slab(c)
+        T = v.shape[1]
+        nb, lat = self._n_blocks(T)
+        d_v, d_c = self._slab(v, nb), self._slab(c, nb)
         d_out = torch.empty_like(d_v)
         for b in range(0, nb, int(blocks_per_call)):
             k = min(int(blocks_per_call), nb - b)
             self.process_device(d_v[b:b + k], d_c[b:b + k], d_out[b:b + k], n_blocks=k, depth=depth, lifter=lifter)
-        torch.cuda.synchronize(dev)
-        y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, nb * N)
-        return np.ascontiguousarray(y[:, Lat:Lat + T])
-
-    def debug_alloc_count(self):
-        return self.L.vp_xs_debug_alloc_count(self.h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.vp_xs_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._trimmed(d_out, T, lat)
 
 
-class HarmonizerStream:
+class HarmonizerStream(_BlockStream):
     """Streaming harmonizer: `n_streams` independent streams of `n_voices` peak-locked voices each beside the dry signal, blocks of
     `block_size` samples, state kept across calls (include/vp_amd.h vp_hz_*).  Output sample t of a stream is sample t - latency of what
     StftRoundTrip.harmonize gives on everything the stream has received, bit for bit -- the dry part delayed with the voices --; the
     first `latency` samples are 0."""
+    _prefix = "vp_hz"
+    latency = property(lambda self: self.L.vp_hz_get_latency(self.h), doc="F - gcd(N, hop) samples.")
 
     def __init__(self, n_streams, block_size, n_voices, hop=256, frame_len=1024, device=0):
-        try:
-            import torch  # noqa: F401  (run() and process_device() use torch: load its HIP runtime before the library loads one)
-        except ImportError:
-            pass
-        self.L = load_library()
-        h = C.c_void_p()
-        rc = self.L.vp_hz_create(int(device), int(n_streams), int(block_size), int(frame_len), int(hop), int(n_voices), C.byref(h))
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
-        self.h, self.S, self.N, self.V, self.hop, self.F, self.device = h, int(n_streams), int(block_size), int(n_voices), int(hop), int(frame_len), device
+        self._open(int(device), int(n_streams), int(block_size), int(frame_len), int(hop), int(n_voices))
+        self.S, self.N, self.V, self.hop, self.F, self.device = int(n_streams), int(block_size), int(n_voices), int(hop), int(frame_len), device
         self._tables = {}
-
-    def _chk(self, rc):
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
-
-    @property
-    def latency(self):
-        """F - gcd(N, hop) samples."""
-        return self.L.vp_hz_get_latency(self.h)
-
-    def reset(self, stream=-1):
-        """The stream (-1: all) starts again like a fresh one at the next process call."""
-        self._chk(self.L.vp_hz_reset(self.h, int(stream)))
 
     def process_device(self, d_in, d_out, n_blocks=1, semitones=None, d_ratio=None, gains=None, dry=None, stream=None):
         """n_blocks blocks on the device: torch float32 [n_blocks][S][N] each (or [S][N] for one block), enqueued on `stream` (default: the
@@ -1346,71 +1298,38 @@ class HarmonizerStream:
         x = np.asarray(x, dtype=np.float32)
         if x.ndim != 2 or x.shape[0] != self.S:
             raise ValueError(f"harmonize: input {x.shape}: an array [{self.S}][T] expected")
-        T, Lat, N = x.shape[1], self.latency, self.N
-        nb = -(-(T + Lat) // N)
+        T = x.shape[1]
+        nb, lat = self._n_blocks(T)
         st = np.asarray(semitones, dtype=np.float64)
         if st.shape not in ((self.V,), (self.S, self.V), (nb, self.S, self.V)):
             raise ValueError(f"harmonize: semitones: [{self.V}], [{self.S}][{self.V}] or [{nb}][{self.S}][{self.V}] expected, got {st.shape}")
         st = np.broadcast_to(st, (nb, self.S, self.V))
-        dev = torch.device("cuda", self.device)
-        xp = np.zeros((self.S, nb * N), np.float32)
-        xp[:, :T] = x
-        d_x = torch.from_numpy(np.ascontiguousarray(xp.reshape(self.S, nb, N).transpose(1, 0, 2))).to(dev)
+        d_x = self._slab(x, nb)
         d_out = torch.empty_like(d_x)
         for b in range(0, nb, int(blocks_per_call)):
             k = min(int(blocks_per_call), nb - b)
             self.process_device(d_x[b:b + k], d_out[b:b + k], n_blocks=k, semitones=st[b:b + k], gains=gains, dry=dry)
-        torch.cuda.synchronize(dev)
-        y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(self.S, nb * N)
-        return np.ascontiguousarray(y[:, Lat:Lat + T])
-
-    def debug_alloc_count(self):
-        return self.L.vp_hz_debug_alloc_count(self.h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.vp_hz_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._trimmed(d_out, T, lat)
 
 
-class StreamingPitchTracker:
+class StreamingPitchTracker(_StreamHandle):
     """Streaming pitch tracker (include/vp_amd.h vp_pv_tracker_*): StftRoundTrip.track_pitch's decision once per block and stream, from the
     last frame_len + ceil(sample_rate / 100) samples the stream has received (period 0, ratio 1.0 until it has that many), then followed:
     the last voiced ratio is held for `hold_blocks` unvoiced blocks before the target returns to 1.0, and the ratio moves the fraction
     `glide` of the way to its target per block (1.0: at once).  frame_len (1024 or 2048) is the tracker's own analysis length.  The ratio
     table is what PhaseVocoderStream.process_device(d_ratio=...) takes; PhaseVocoderStream.autotune_device runs both."""
 
+    _prefix = "vp_pv_tracker"
+
     def __init__(self, n_streams, block_size, sample_rate, frame_len=1024, hold_blocks=0, glide=1.0, device=0):
-        try:
-            import torch  # noqa: F401  (process_device() uses torch: load its HIP runtime before the library loads one)
-        except ImportError:
-            pass
-        self.L = load_library()
-        h = C.c_void_p()
-        rc = self.L.vp_pv_tracker_create(int(device), int(n_streams), int(block_size), int(frame_len), float(sample_rate), C.byref(h))
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
-        self.h, self.S, self.N, self.F, self.fs, self.device = h, int(n_streams), int(block_size), int(frame_len), float(sample_rate), device
+        self._open(int(device), int(n_streams), int(block_size), int(frame_len), float(sample_rate))
+        self.S, self.N, self.F, self.fs, self.device = int(n_streams), int(block_size), int(frame_len), float(sample_rate), device
         if hold_blocks != 0 or glide != 1.0:
             self.set_follow(hold_blocks, glide)
-
-    def _chk(self, rc):
-        if rc:
-            raise VpError(rc, self.L.vp_error_string(rc).decode())
 
     def set_follow(self, hold_blocks, glide):
         """0 <= hold_blocks <= 2^20 unvoiced blocks the last voiced ratio outlives, 0 < glide <= 1; every stream, from the next call on."""
         self._chk(self.L.vp_pv_tracker_set_follow(self.h, int(hold_blocks), float(glide)))
-
-    def reset(self, stream=-1):
-        """The stream (-1: all) starts again like a fresh one at the next process call: no history, no held ratio."""
-        self._chk(self.L.vp_pv_tracker_reset(self.h, int(stream)))
 
     def _tables(self, keys, n_blocks, dev):
         """(d_key or None, period, ratio) of a call of n_blocks blocks: the key table is kept per handle (one device int32 [S], rewritten
@@ -1432,17 +1351,3 @@ class StreamingPitchTracker:
         self._chk(self.L.vp_pv_tracker_process_blocks_device(self.h, d_in.data_ptr(), d_key.data_ptr() if d_key is not None else None,
                                                              period.data_ptr(), ratio.data_ptr(), int(n_blocks), C.c_void_p(stream)))
         return period, ratio
-
-    def debug_alloc_count(self):
-        return self.L.vp_pv_tracker_debug_alloc_count(self.h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.vp_pv_tracker_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
