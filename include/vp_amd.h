@@ -475,6 +475,65 @@ int vp_stft_time_stretch_locked(vp_stft *p, const float *d_in, int n_in, const i
  * duration in [0.25, 4].  VP_ERR_INVALID_ARG outside that range, for a stretch that is not finite, n_in < frame_len or hop <= 0; nothing
  * is written then.  Host array; no device is touched. */
 int vp_stretch_positions(int *pos, int n_frames, int hop, double stretch, int n_in, int frame_len);
+/* TRANSIENT-PRESERVING locked time stretch: do not stretch across an attack, and restart the phases at it.  Four calls, in this order:
+ * vp_stft_onset_flux (device), vp_onset_pick and vp_stretch_positions_transient (host, exact), vp_stft_time_stretch_locked_reset (device).
+ * The definition is tests/pv_transient_reference.py.  1024-point frames, every hop of the locked stretch, always double, one-shot only.
+ * Out of scope: a streaming form, 2048-point frames, sub-bin offsets, single precision, detection on the device end to end, resets in the
+ * pitch-shift-only calls.  Recorded figures: profiles/pv_transient_quality.txt (the definition's, on bursts and plucks),
+ * profiles/pv_onset_errors.txt, profiles/pv_transient_bench.txt (the reset kernel on an all-zero table 0.98 x vp_stft_time_stretch_locked, the
+ * flux kernel 478 M frames/s on one MI355X at 256 streams x 65 536 samples, hop 256).
+ *
+ * vp_onset_num_frames: nG = (n_in - frame_len) / hop + 1, the frames of the INPUT's own grid g hop; VP_ERR_INVALID_ARG for
+ * n_in < frame_len, frame_len <= 0 or hop <= 0. */
+int vp_onset_num_frames(int n_in, int frame_len, int hop);
+/* Onset flux (kernel vp_k_stft_onset_flux): over the grid g hop of every row of d_in [n_streams][n_in], with the handle's window,
+ *   M_g = |rfft(x[g hop : g hop + frame_len] w)| over bins 0 .. 512;  mass[g] = sum_k M_g[k];
+ *   flux[0] = 0,  flux[g] = sum_k max(M_g[k] - M_(g-1)[k], 0)  otherwise (the rectified spectral flux; a NaN stays a NaN).
+ * Sums run in a fixed order, so a row's figures do not depend on its neighbours or on n_streams.  Against the NumPy definition the
+ * difference is rounding: at most 4 513 log2(frame_len) 2^-53 (|x_g w|_2 + |x_(g-1) w|_2) per frame (tested).
+ * d_flux, d_mass: device double [n_streams][vp_onset_num_frames(n_in, frame_len, hop)].  The handle's n_samples plays no part.  No
+ * allocation, no synchronisation: the tables are ready when hip_stream reaches the call's end.
+ * VP_ERR_INVALID_ARG (a null handle or pointer, n_in < frame_len) and VP_ERR_GEOMETRY (a 2048-point handle) are reported before the device
+ * is touched and vp_stft_last_error says which under the name "onset flux"; VP_ERR_HIP as vp_stft_pitch_shift. */
+int vp_stft_onset_flux(vp_stft *p, const float *d_in, int n_in, double *d_flux, double *d_mass, void *hip_stream);
+/* Onsets of one row from its flux and mass tables: onsets[g] = 1 iff ALL of
+ *   flux[g] > 0,   flux[g] >= thr mass[g],   flux[g] > flux[g-1],   flux[g] >= flux[g+1]
+ * hold, else 0; a missing neighbour (g = 0, g = n - 1) counts as -infinity and a NaN anywhere in a comparison is "no".  thr in [0, 1];
+ * VP_DEFAULT_ONSET_THRESHOLD is the offline tool's default.  VP_ERR_INVALID_ARG for a null pointer, n < 0 or thr outside [0, 1] or not
+ * finite; nothing is written then.  Host arrays; no device is touched. */
+#define VP_DEFAULT_ONSET_THRESHOLD 0.2
+int vp_onset_pick(const double *flux, const double *mass, int n, double thr, unsigned char *onsets);
+/* The position table and the reset flags of a constant stretch that leaves the onsets alone, for one row: pos int [n_frames], reset
+ * unsigned char [n_frames], from onsets [nG], nG = vp_onset_num_frames(n_in, frame_len, hop).
+ *   base[f] = min(floor(f hop / stretch), n_in - frame_len)                          (vp_stretch_positions's formula, in double).
+ *   Anchors start as [(0, 0)].  The onsets g in increasing order: fc = floor(g stretch + 0.5), a = fc - K, b = fc + K; g is accepted iff
+ *     g - K >= 0,  g + K <= nG - 1,  a > the last anchor's frame,  b < n_frames - 1,
+ *     (g - K) hop >= the last anchor's position,  (g + K) hop <= base[n_frames - 1];
+ *   then the anchors (a, (g - K) hop) and (b, (g + K) hop) are appended and reset[a] = 1.  The last anchor is
+ *   (n_frames - 1, base[n_frames - 1]).
+ *   Between consecutive anchors (f0, p0), (f1, p1): pos[f] = p0 + ((f - f0) (p1 - p0)) / (f1 - f0) in 64-bit integers (floor).
+ * A span of 2 K + 1 frames around an accepted onset is read exactly hop apart -- no stretch there --, the stretch is made up between the
+ * spans, and the table is non-decreasing.  WITH NO ACCEPTED ONSET THE TABLE IS THE TWO-ANCHOR LINE from (0, 0) to
+ * (n_frames - 1, base[n_frames - 1]), not vp_stretch_positions's table.  K in [VP_ONSET_SPAN_MIN, VP_ONSET_SPAN_MAX] = [1, 8]; the
+ * tools' default is max(frame_len / (2 hop), 1).
+ * VP_ERR_INVALID_ARG for vp_stretch_positions's errors, a null table or K out of range; nothing is written then.  Host arrays. */
+#define VP_ONSET_SPAN_MIN 1
+#define VP_ONSET_SPAN_MAX 8
+int vp_stretch_positions_transient(int *pos, unsigned char *reset, int n_frames, int hop, double stretch, int n_in, int frame_len,
+                                   const unsigned char *onsets, int K);
+/* vp_stft_time_stretch_locked with a PHASE RESET on flagged frames (kernel vp_k_stft_pv_stretch_lock_reset): one change in the rotation
+ * rule -- on a frame with d_reset[s][f] != 0 (any non-zero byte), th[P] = 0 for every peak P instead of theta[P] + the advance.  pprev,
+ * theta[k] = th[own[k]] and the frame without peaks (Y = 0, theta left, flagged or not) are unchanged.  At ratio 1 and frames hop apart
+ * the advance is exactly 0, so from a reset on the stage is the identity: a span planned by vp_stretch_positions_transient leaves with
+ * the input's spectrum -- the attack is neither smeared nor preceded by an echo.  In the definition that is bit for bit; the kernel turns
+ * every region by the angle 0 through the stage's cosine fit, whose value there is 1 + 2^-52, so a bin may be one unit in the last place
+ * of the double off, and the float32 output behind a reset equals vp_stft_roundtrip's on every sample the GPU test compares.  An all-zero
+ * table gives vp_stft_time_stretch_locked's bits (tested).
+ * d_reset: device unsigned char [n_streams][vp_stft_num_frames(p)], read when the kernel runs; every other argument, the geometry and the
+ * errors are vp_stft_time_stretch_locked's, under the name "stretch locked reset", and a null d_reset is VP_ERR_INVALID_ARG.  No
+ * allocation. */
+int vp_stft_time_stretch_locked_reset(vp_stft *p, const float *d_in, int n_in, const int *d_pos, float *d_out, const double *d_ratio,
+                                      const unsigned char *d_reset, void *hip_stream);
 /* Pitch tracker and automatic correction (kernel vp_k_yin_track, csrc/vp_track.hip): PitchProcess's own decision -- YIN, the key's
  * nearest note, beta = closestFreq / pitch, with the plugin's numbers fMin 100, fMax 800, yinTol 0.25 and the Notes tables -- for every
  * frame of the handle at once, one wavefront per frame.  The definition is tests/pv_track_reference.py, and the result equals it

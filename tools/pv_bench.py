@@ -8,6 +8,7 @@
     [VP_AMD_LIB=...] python tools/pv_bench.py --track-stream [--reps 7] [--out profiles/pv_track_stream_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --locked [--reps 7] [--out profiles/pv_lock_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --stretch-locked [--reps 7] [--out profiles/pv_stretch_lock_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --transient [--reps 7] [--out profiles/pv_transient_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --locked-subbin [--reps 7] [--out profiles/pv_lockf_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --cross [--reps 7] [--out profiles/pv_cross_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --harm [--reps 7] [--out profiles/pv_harm_bench.txt]
@@ -51,6 +52,11 @@ streams, 65 536 output samples, 1024 points / hop 256, on noise and on voiced si
 (vp_k_stft_pv_lock) and the new kernel at the identity table f hop on the same input: the ratio is the cost of the positions alone.  Then
 the plain time stretch (vp_k_stft_pv_stretch) and the new kernel at stretch 0.5 and 2, each pair on the same input and table.  The kernels'
 resource listings follow.
+
+--transient: the transient-preserving stretch's two kernels, alternating in one process: 256 streams x 65 536 samples, 1024 points /
+hop 256, on noise and on voiced signals.  The onset flux (vp_stft_onset_flux) alone, in input frames per second; the reset kernel
+(vp_stft_time_stretch_locked_reset) on an ALL-ZERO table beside vp_stft_time_stretch_locked on the same input, ratio table (+7) and
+positions f hop: the ratio is the cost of the flag byte and the turn's select.  The kernels' resource listings follow.
 
 --cross: the cross-synthesis (vp_stft_cross_synth, vp_xs_process_blocks_device) beside the kernels it is made of, alternating in one
 process: 256 streams x 65 536 samples, 1024 points / hop 256, voiced voices over sawtooth carriers.  The plain double-precision round trip
@@ -244,6 +250,28 @@ def stretch_locked_legs(reps, emit):
         mean = {k: sum(v) / len(v) for k, v in times.items()}
         for a in (0.5, 2.0):
             emit(f"  stretch locked {a:g} = {mean[f'plain stretch {a:g}, +7'] / mean[f'stretch locked {a:g}, +7']:.3f} x plain stretch {a:g} (frames/s, the same run)")
+    st.close()
+
+
+def transient_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import StftRoundTrip, semitones_to_ratios
+    S, T, F, hop, fs = 256, 65536, 1024, 256, 44100.0
+    st = StftRoundTrip(S, T, F, hop)
+    nF = st.n_frames
+    y = torch.empty(S, T, device="cuda", dtype=torch.float32)
+    ratio = torch.from_numpy(np.full((S, nF), semitones_to_ratios([7.0])[0])).cuda()
+    pos = torch.from_numpy(np.tile(np.arange(nF, dtype=np.int32) * hop, (S, 1))).cuda()
+    zero = torch.zeros((S, nF), dtype=torch.uint8, device="cuda")
+    flux, mass = torch.empty((S, nF), dtype=torch.float64, device="cuda"), torch.empty((S, nF), dtype=torch.float64, device="cuda")
+    parent, new, fl = "stretch locked, +7 (parent kernel)", "stretch locked reset, all-zero table", "onset flux"
+    for what, x in (("noise", torch.randn(S, T, device="cuda", dtype=torch.float32) * 0.1), ("voiced signals", torch.from_numpy(voiced_rows(S, T, fs)).cuda())):
+        legs = {parent: lambda x=x: st.time_stretch_locked(x, y, d_pos=pos, d_ratio=ratio),
+                new: lambda x=x: st.time_stretch_locked(x, y, d_pos=pos, d_ratio=ratio, d_reset=zero),
+                fl: lambda x=x: st.onset_flux(x, flux, mass)}
+        report(f"transient-preserving stretch, {S} streams x {T} samples of {what}, F = {F}, hop = {hop} (n_in = T: {nF} frames per stream in every leg)",
+               alternate(legs, reps, {parent: 100, new: 100, fl: 400}), S * nF, parent, emit)
     st.close()
 
 
@@ -495,12 +523,13 @@ def main():
     ap.add_argument("--locked", action="store_true", help="the peak-locked legs instead of the fixed intervals")
     ap.add_argument("--locked-subbin", action="store_true", help="the sub-bin peak-locked legs instead of the fixed intervals")
     ap.add_argument("--stretch-locked", action="store_true", help="the locked time-stretch legs instead of the fixed intervals")
+    ap.add_argument("--transient", action="store_true", help="the onset-flux and reset-kernel legs instead of the fixed intervals")
     ap.add_argument("--cross", action="store_true", help="the cross-synthesis legs instead of the fixed intervals")
     ap.add_argument("--harm", action="store_true", help="the harmonizer legs instead of the fixed intervals")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="--curve / --stretch / --track: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.locked_subbin and not a.stretch_locked and not a.cross and not a.harm:
+    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.locked_subbin and not a.stretch_locked and not a.transient and not a.cross and not a.harm:
         return fixed_intervals()
     lines = []
 
@@ -527,6 +556,9 @@ def main():
     if a.stretch_locked:
         stretch_locked_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_stft_pv_lock", "vp_k_stft_pv_stretch", "vp_k_stft_pv_stretch_lock"))
+    if a.transient:
+        transient_legs(max(5, a.reps), emit)
+        resource_listing(emit, ("vp_k_stft_pv_stretch_lock", "vp_k_stft_pv_stretch_lock_reset", "vp_k_stft_onset_flux"))
     if a.cross:
         cross_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_stft_fused<false, false>", "vp_k_stft_pv_formant", "vp_k_stft_cross", "vp_k_xs_stream"))

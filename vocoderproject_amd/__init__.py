@@ -5,4 +5,4 @@ reference's plugin surface), synth.py (synthetic streams), dist.py (stream shard
 offline.py (WAV files in, WAV files out: the notebook's whole-recording flows on the plugin path).
 Nothing here imports oracle/.
 """
-from .processor import BatchVocoderProcessor, StftRoundTrip, PhaseVocoderStream, StreamingPitchTracker, CrossSynthStream, HarmonizerStream, semitones_to_ratios, stretch_positions, VpError, load_library, PARAM_IDS, KEYS  # noqa: F401
+from .processor import BatchVocoderProcessor, StftRoundTrip, PhaseVocoderStream, StreamingPitchTracker, CrossSynthStream, HarmonizerStream, semitones_to_ratios, stretch_positions, pick_onsets, stretch_positions_transient, VpError, load_library, PARAM_IDS, KEYS  # noqa: F401

@@ -21,7 +21,7 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libvp_amd.so")
 SOURCES = ["vp_kernels.hip", "vp_voc2.hip", "vp_stft.hip", "vp_channels.hip", "vp_track.hip", "vp_capi.hip"]
 PARTS = ["vp_fft.inc", "vp_filters.inc", "vp_vocoder_wg.inc", "vp_pitch.inc", "vp_pitch_ws.inc", "vp_pitch_ws_body.inc"]      # included by vp_kernels.hip
-DEPS = SOURCES + PARTS + ["vp_common.h", "vp_kernels.h", "vp_voc2.h", "vp_stft.h", "vp_fft32.inc", "vp_channels.h", "vp_stft_curve.inc", "vp_stft_stretch.inc", "vp_stft_lock.inc", "vp_stft_lockf.inc", "vp_stft_harm.inc", "vp_stft_stretch_lock.inc", "vp_stft_formant.inc", "vp_stft_cross.inc", "vp_track.h", "vp_track_body.inc"]
+DEPS = SOURCES + PARTS + ["vp_common.h", "vp_kernels.h", "vp_voc2.h", "vp_stft.h", "vp_fft32.inc", "vp_channels.h", "vp_stft_curve.inc", "vp_stft_stretch.inc", "vp_stft_lock.inc", "vp_stft_lockf.inc", "vp_stft_harm.inc", "vp_stft_stretch_lock.inc", "vp_stft_formant.inc", "vp_stft_cross.inc", "vp_track.h", "vp_track_body.inc", "vp_pv_transient.inc", "vp_stft_onset.inc", "vp_stft_stretch_reset.inc", "vp_onset_host.inc"]
 ARCH = "gfx950"
 NUM_TUS = 9          # groups of kernels in vp_kernels.hip (VP_TU)
 
@@ -139,11 +139,11 @@ def build(force=False, verbose=False, stamps=False, poison=False):
             hsh = hashlib.sha256((hipcc_version() + " ".join(cmd[:-1]).replace(tmp, "")).encode())
             deps = {"vp_kernels.hip": ["vp_kernels.hip", "vp_common.h"] + PARTS,
                     "vp_voc2.hip": ["vp_voc2.hip", "vp_voc2.h", "vp_kernels.hip", "vp_common.h"] + PARTS,
-                    "vp_stft.hip": ["vp_stft.hip", "vp_stft.h", "vp_fft.inc", "vp_fft32.inc", "vp_stft_curve.inc", "vp_stft_stretch.inc", "vp_stft_lock.inc", "vp_stft_lockf.inc", "vp_stft_harm.inc", "vp_stft_stretch_lock.inc", "vp_stft_formant.inc", "vp_stft_cross.inc"],
+                    "vp_stft.hip": ["vp_stft.hip", "vp_stft.h", "vp_fft.inc", "vp_fft32.inc", "vp_stft_curve.inc", "vp_stft_stretch.inc", "vp_stft_lock.inc", "vp_stft_lockf.inc", "vp_stft_harm.inc", "vp_stft_stretch_lock.inc", "vp_stft_formant.inc", "vp_stft_cross.inc", "vp_pv_transient.inc", "vp_stft_onset.inc", "vp_stft_stretch_reset.inc"],
                     "vp_channels.hip": ["vp_channels.hip", "vp_channels.h"],
                     "vp_track.hip": ["vp_track.hip", "vp_track.h", "vp_track_body.inc", "vp_common.h"]}.get(os.path.basename(src))
             if deps is None:
-                deps = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.basename(src), os.path.join(ROOT, "include", "vp_amd.h")]
+                deps = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.basename(src), "vp_onset_host.inc", os.path.join(ROOT, "include", "vp_amd.h")]
             for dep in deps:
                 with open(dep if os.path.isabs(dep) else os.path.join(CSRC, dep), "rb") as f:
                     hsh.update(f.read())

@@ -1906,7 +1906,8 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     // that a later hipGetLastError() behind a launch does not report this one.
     p->pvOk = vp_stft_prepare_device() == hipSuccess && vp_stft_curve_prepare_device() == hipSuccess && vp_stft_stretch_prepare_device() == hipSuccess
         && vp_stft_formant_prepare_device() == hipSuccess && vp_stft_lock_prepare_device() == hipSuccess && vp_stft_stretch_lock_prepare_device() == hipSuccess
-        && vp_stft_lockf_prepare_device() == hipSuccess && vp_stft_harm_prepare_device() == hipSuccess;
+        && vp_stft_lockf_prepare_device() == hipSuccess && vp_stft_harm_prepare_device() == hipSuccess
+        && vp_stft_onset_prepare_device() == hipSuccess && vp_stft_stretch_reset_prepare_device() == hipSuccess;
     if (!p->pvOk) (void)hipGetLastError();
     p->device = device; p->F = frame_len; p->hop = hop; p->S = n_streams; p->T = n_samples;
     p->nFrames = (n_samples - frame_len) / hop + 1;
@@ -1985,6 +1986,7 @@ struct PvMode {
     const double *ratioTab = nullptr;   // every other kind: one-shot [S][nFrames], streaming [n_blocks][S]
     const int *posTab = nullptr;        // STRETCH, STRETCH_LOCKED: frame f of stream s is read at input sample posTab[s][f] ...
     int nIn = 0;                        // ... of rows of nIn samples
+    const unsigned char *resetTab = nullptr;   // STRETCH_LOCKED: null, or [S][nFrames] flags of the frames that restart the angles
     const double *formant = nullptr;    // FORMANT: [S] formant ratios or null (1.0)
     int lifter = 0;                     // FORMANT, CROSS: the cepstral lifter's length in samples
     const float *voice = nullptr;       // CROSS: [S][T], whose envelope the call's input -- the carrier -- takes ...
@@ -1998,6 +2000,7 @@ struct PvMode {
     static PvMode form(const double *tab, const double *formant, int lifter) { PvMode m; m.kind = FORMANT; m.ratioTab = tab; m.formant = formant; m.lifter = lifter; return m; }
     static PvMode stretch(double semitones, const int *pos, int nIn) { PvMode m = fixed(semitones); m.kind = STRETCH; m.posTab = pos; m.nIn = nIn; return m; }
     static PvMode stretch_lock(const double *tab, const int *pos, int nIn) { PvMode m; m.kind = STRETCH_LOCKED; m.ratioTab = tab; m.posTab = pos; m.nIn = nIn; return m; }
+    static PvMode stretch_lock_reset(const double *tab, const int *pos, int nIn, const unsigned char *reset) { PvMode m = stretch_lock(tab, pos, nIn); m.resetTab = reset; return m; }
     static PvMode cross(const float *voice, const double *depth, int lifter) { PvMode m; m.kind = CROSS; m.voice = voice; m.depth = depth; m.lifter = lifter; return m; }
     bool locked() const { return kind == LOCKED || kind == LOCKED_SUBBIN || kind == STRETCH_LOCKED; }
     bool enveloped() const { return kind == FORMANT || kind == CROSS; }
@@ -2047,7 +2050,10 @@ static int stft_fused(vp_stft *p, const float *d_in, float *d_out, float *d_mag,
     case PvMode::LOCKED_SUBBIN: e = vp_stft_launch_lockf(a, m->ratioTab, p->S, st); break;
     case PvMode::FORMANT: e = vp_stft_launch_formant(a, m->ratioTab, m->formant, m->lifter, p->S, st); break;
     case PvMode::STRETCH: e = vp_stft_launch_stretch(a, m->posTab, m->nIn, p->S, st); break;
-    case PvMode::STRETCH_LOCKED: e = vp_stft_launch_stretch_lock(a, m->ratioTab, m->posTab, m->nIn, p->S, st); break;
+    case PvMode::STRETCH_LOCKED:
+        e = m->resetTab ? vp_stft_launch_stretch_lock_reset(a, m->ratioTab, m->posTab, m->nIn, m->resetTab, p->S, st)
+                        : vp_stft_launch_stretch_lock(a, m->ratioTab, m->posTab, m->nIn, p->S, st);
+        break;
     case PvMode::CROSS: e = vp_stft_launch_cross(a, m->voice, m->depth, m->lifter, p->S, nRuns, st); break;
     }
     return e == hipSuccess ? VP_OK : VP_ERR_HIP;
@@ -2174,6 +2180,35 @@ extern "C" int vp_stft_time_stretch_locked(vp_stft *p, const float *d_in, int n_
     return stft_call(p, stft_check(p, "stretch locked", d_in && d_pos && d_out && d_ratio, "null input, position table, output or ratio table", &m),
                      d_in, d_out, nullptr, &m, hip_stream);
 }
+
+// the locked time stretch with a phase reset on flagged frames (vp_k_stft_pv_stretch_lock_reset): vp_stft_time_stretch_locked's arguments,
+// checks and codes, and d_reset [S][nFrames]
+extern "C" int vp_stft_time_stretch_locked_reset(vp_stft *p, const float *d_in, int n_in, const int *d_pos, float *d_out, const double *d_ratio,
+                                                 const unsigned char *d_reset, void *hip_stream)
+{
+    const PvMode m = PvMode::stretch_lock_reset(d_ratio, d_pos, n_in, d_reset);
+    return stft_call(p, stft_check(p, "stretch locked reset", d_in && d_pos && d_out && d_ratio && d_reset, "null input, position table, output, ratio table or reset table", &m),
+                     d_in, d_out, nullptr, &m, hip_stream);
+}
+
+// the onset flux of the input's own frame grid (vp_k_stft_onset_flux; 1024-point frames): rows of n_in samples, whatever the handle's
+// n_samples; the checks are a locked stretch's (pointers, row length, frame length, the device's verdict at create)
+extern "C" int vp_stft_onset_flux(vp_stft *p, const float *d_in, int n_in, double *d_flux, double *d_mass, void *hip_stream)
+{
+    const PvMode m = PvMode::stretch_lock(nullptr, nullptr, n_in);
+    int rc = stft_check(p, "onset flux", d_in && d_flux && d_mass, "null input, flux table or mass table", nullptr);
+    if (rc) return rc;
+    if (n_in < p->F) { p->lastError = "onset flux: the input row is shorter than one frame"; return VP_ERR_INVALID_ARG; }
+    rc = stft_check(p, "onset flux", true, nullptr, &m);                       // (the frame length; the LDS ceiling)
+    if (rc) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    int nRuns;
+    const VpStftArgs a = stft_args(p, d_in, nullptr, nullptr, &m, &nRuns);
+    return vp_stft_launch_onset(a, n_in, p->S, d_flux, d_mass, (hipStream_t)hip_stream) == hipSuccess ? VP_OK : VP_ERR_HIP;
+}
+
+// the host half of the transient-preserving stretch: vp_onset_num_frames, vp_onset_pick, vp_stretch_positions_transient
+#include "vp_onset_host.inc"
 
 // cross-synthesis (vp_k_stft_cross; 1024-point frames): the carrier takes the plain round trip's path -- its runs included, always in
 // double -- with the voice's envelope imposed between the transforms

@@ -157,3 +157,16 @@ size_t vp_stft_harm_lds_bytes(int hop);
 hipError_t vp_hz_launch(const VpPvArgs &a, const double *d_ratio, const double *d_gain, const double *d_dry, int nVoices, hipStream_t st);
 hipError_t vp_hz_prepare_device();
 size_t vp_hz_lds_bytes();
+
+// ---- the transient-preserving locked time stretch (vp_stft_onset_flux, vp_stft_time_stretch_locked_reset) ---------------------------------
+// the onset flux (vp_k_stft_onset_flux; csrc/vp_stft_onset.inc): a.in rows of nIn samples, d_flux and d_mass double [nStreams][nG],
+// nG = (nIn - a.F) / a.hop + 1; grid = chunks of vp_stft_onset_chunk(nG, nStreams) consecutive frames x streams; a.F == 1024
+hipError_t vp_stft_launch_onset(const VpStftArgs &a, int nIn, int nStreams, double *d_flux, double *d_mass, hipStream_t st);
+hipError_t vp_stft_onset_prepare_device();
+size_t vp_stft_onset_lds_bytes();
+int vp_stft_onset_chunk(int nG, int nStreams);
+// the locked time stretch with a phase reset on the frames d_reset [nStreams][a.nFrames] flags, any non-zero byte
+// (vp_k_stft_pv_stretch_lock_reset; csrc/vp_stft_stretch_reset.inc): everything else as vp_stft_launch_stretch_lock, its dynamic LDS too
+hipError_t vp_stft_launch_stretch_lock_reset(const VpStftArgs &a, const double *d_ratio, const int *d_pos, int nIn, const unsigned char *d_reset, int nStreams,
+                                             hipStream_t st);
+hipError_t vp_stft_stretch_reset_prepare_device();

@@ -1122,5 +1122,9 @@ hipError_t vp_pv_launch(const VpPvArgs &a, hipStream_t st)
 // ---- cross-synthesis: the voice's spectral envelope on the carrier (vp_stft_cross_synth, vp_xs_process_blocks_device) ----
 #include "vp_stft_cross.inc"
 
+// ---- the transient-preserving locked time stretch: the onset flux of the input's grid (vp_stft_onset_flux) and the locked stretch with
+// a phase reset on flagged frames (vp_stft_time_stretch_locked_reset) ----
+#include "vp_pv_transient.inc"
+
 // ---- the ratio-curve kernels with the cepstral formant correction (vp_stft_pitch_shift_formant, vp_pv_process_blocks_formant_device) ----
 #include "vp_stft_formant.inc"

@@ -15,6 +15,7 @@ There is no CPU path here either: without a GPU the processor raises.
     python -m vocoderproject_amd.offline pvshift a.wav b.wav --shift 7 --out-dir out/     (streaming phase vocoder)
     python -m vocoderproject_amd.offline pvshift a.wav --glide -12:12 --out-dir out/      (... along a glide, one interval per block)
     python -m vocoderproject_amd.offline stretch a.wav b.wav --stretch 1.5 [--shift 3] [--locked] --out-dir out/   (time stretch, one-shot phase vocoder)
+    python -m vocoderproject_amd.offline stretch a.wav --stretch 2 --locked --transients [THR] [--span K] --out-dir out/   (attacks kept: no stretch across an onset, phases restart at it)
     python -m vocoderproject_amd.offline pvshift a.wav --shift -12 --locked --subbin --out-dir out/   (peak locking with sub-bin region offsets)
     python -m vocoderproject_amd.offline pvtune a.wav b.wav --key 0 --out-dir out/ [--track-csv]        (pitch tracker + phase-vocoder correction)
     python -m vocoderproject_amd.offline pvtune a.wav --stream [--block 256 --hold 8 --glide 0.5] --out-dir out/   (... block by block: the streaming tracker)
@@ -392,22 +393,63 @@ class _StretchRunner:
     def __init__(self, F, hop, device):
         self.F, self.hop, self.device = int(F), int(hop), device
 
-    def run(self, x, pos, T, semitones, locked=False):
+    def run(self, x, pos, T, semitones, locked=False, reset=None):
         def call(st, d_in, d_out):
-            (st.time_stretch_locked if locked else st.time_stretch)(d_in, d_out, positions=pos, semitones=float(semitones))
+            if reset is not None:
+                import torch
+                st.time_stretch_locked(d_in, d_out, positions=pos, semitones=float(semitones), d_reset=torch.from_numpy(np.ascontiguousarray(reset, dtype=np.uint8)).to(d_in.device))
+            else:
+                (st.time_stretch_locked if locked else st.time_stretch)(d_in, d_out, positions=pos, semitones=float(semitones))
         return _one_shot(x, T, self.F, self.hop, self.device, call)[0]
 
+    def flux(self, x):
+        """StftRoundTrip.onset_flux from the host array x float32 [S][n_in] -> (flux, mass) float64 [S][nG]."""
+        import torch
+        from .processor import StftRoundTrip
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        st = StftRoundTrip(x.shape[0], self.F + self.hop, self.F, self.hop, self.device)
+        try:
+            d_flux, d_mass = st.onset_flux(torch.from_numpy(x).to(torch.device("cuda", self.device)))
+            return d_flux.cpu().numpy(), d_mass.cpu().numpy()
+        finally:
+            st.close()
 
-def pv_stretch(voices, stretch, shift=0.0, F=1024, hop=256, device=0, processor=None, locked=False):
+
+def transient_tables(flux, mass, lens, per, nF, hop, F, thr, span):
+    """The position and reset tables of a batch, int32 and uint8 [S][nF]: recording s is picked and planned against ITS OWN length --
+    the first (max(lens[s], F) - F) // hop + 1 frames of its row of the padded batch's flux and mass tables, its own stretch per[s]."""
+    from .processor import pick_onsets, stretch_positions_transient
+    pos, reset = np.zeros((len(lens), nF), np.int32), np.zeros((len(lens), nF), np.uint8)
+    for s, (n, a) in enumerate(zip(lens, per)):
+        n = max(int(n), F)
+        nG = (n - F) // hop + 1
+        pos[s], reset[s] = stretch_positions_transient(pick_onsets(flux[s][:nG], mass[s][:nG], thr), nF, hop, a, n, F, span)
+    return pos, reset
+
+
+def pv_stretch(voices, stretch, shift=0.0, F=1024, hop=256, device=0, processor=None, locked=False, transients=None, span=None):
     """A batch of recordings through the one-shot phase vocoder's time stretch (StftRoundTrip.time_stretch: one stream per recording).
     stretch: output duration / input duration in [0.25, 4], one value or one per recording; shift: the pitch shift on top, semitones.
     The recordings are padded to a common input length, each has its own position table (pos[f] = floor(f hop / stretch), held at its
     own last frame), the outputs share one length and each is trimmed to ceil(len stretch) samples.  Returns float32 [2][ceil(len
     stretch)] per recording (the signal on both channels).  `processor` (tests): an object with run(x, pos, T, semitones) to use instead
     of the GPU.  locked: the peak-locked time stretch instead (StftRoundTrip.time_stretch_locked; 1024-point frames); run then also
-    receives locked=True."""
+    receives locked=True.
+    transients=thr (with locked only; thr in [0, 1]): the transient-preserving stretch -- the batch's onset flux (processor.flux(x) ->
+    flux, mass [S][nG]), then per recording, against its own length, pick_onsets(thr) and stretch_positions_transient(span): a span of
+    2 span + 1 frames around every onset is read without stretch and its first frame restarts the phases; run then also receives
+    reset=uint8 [S][n_frames].  span: 1 .. 8, None = max(F / (2 hop), 1).  A recording without onsets takes the two-anchor line."""
     S = _batch_size(voices)
     per = _per_recording(stretch, S, "stretch", float, 0.25, 4.0, "stretch: factors within [0.25, 4] expected")
+    if transients is not None:
+        if not locked:
+            raise ValueError("transients: valid only together with locked (the phase reset is a variant of the peak-locked time stretch)")
+        if not 0.0 <= float(transients) <= 1.0:
+            raise ValueError("transients: a threshold within [0, 1] expected")
+        if span is not None and not 1 <= int(span) <= 8:
+            raise ValueError("span: 1 to 8 frames expected")
+    elif span is not None:
+        raise ValueError("span: valid only together with transients")
     if not -12.0 <= float(shift) <= 12.0:
         raise ValueError("shift: an interval within +-12 semitones expected")
     F, hop = int(F), int(hop)
@@ -420,6 +462,10 @@ def pv_stretch(voices, stretch, shift=0.0, F=1024, hop=256, device=0, processor=
     # (the formula of vp_stretch_positions, against each recording's own length: behind its end a recording repeats its last frame)
     pos = np.stack([np.minimum(np.floor(np.arange(nF, dtype=np.int64) * hop / a), max(n, F) - F) for n, a in zip(lens, per)]).astype(np.int32)
     p = processor if processor is not None else _StretchRunner(F, hop, device)
+    if transients is not None:
+        flux, mass = p.flux(x)
+        pos, reset = transient_tables(flux, mass, lens, per, nF, hop, F, float(transients), None if span is None else int(span))
+        return _both_channels(p.run(x, pos, T, float(shift), locked=True, reset=reset), outs)
     y = p.run(x, pos, T, float(shift), **_mode_kw(None, 0, locked))
     return _both_channels(y, outs)
 
@@ -708,6 +754,11 @@ def main(argv=None):
     ap.add_argument("--dry", type=float, default=1.0, help="harmonize: gain of the unshifted signal beside the voices, within [-4, 4] (default 1)")
     ap.add_argument("--hold", type=int, default=0, help="pvtune --stream: unvoiced blocks over which the last voiced ratio is kept")
     ap.add_argument("--stretch", type=float, default=None, help="stretch: output duration / input duration, 0.25 to 4 (--shift: semitones on top)")
+    ap.add_argument("--transients", type=float, nargs="?", const=0.2, default=None, metavar="THR",
+                    help="stretch, together with --locked: keep attacks -- a frame whose spectral flux is a local maximum of at least THR of its "
+                         "spectral mass (0 to 1; no value: 0.2) is an onset, the frames around it are read without stretch and the phases "
+                         "restart there.  The value is optional, so put the flag BEHIND the input files or in front of another option")
+    ap.add_argument("--span", type=int, default=None, metavar="K", help="--transients: frames kept either side of an onset, 1 to 8 (default: frame / (2 hop))")
     ap.add_argument("--frame", type=int, default=1024, help="stretch, pvtune: frame length (1024 or 2048)")
     ap.add_argument("--track-csv", action="store_true", help="pvtune: also write NAME_pvtune.csv per recording (time, period, correction in semitones per frame)")
     ap.add_argument("--lpc-voice", type=int, default=40)
@@ -749,6 +800,12 @@ def main(argv=None):
         raise SystemExit("--subbin: pvshift and pvtune take it")
     if a.subbin and not a.locked:
         raise SystemExit("--subbin: valid only together with --locked (the sub-bin region offsets are a variant of the peak-locked call)")
+    if a.transients is not None and a.flow != "stretch":
+        raise SystemExit("--transients: stretch takes it")
+    if a.transients is not None and not a.locked:
+        raise SystemExit("--transients: valid only together with --locked (the phase reset is a variant of the peak-locked time stretch)")
+    if a.span is not None and a.transients is None:
+        raise SystemExit("--span: valid only together with --transients")
     fkw = {} if a.formant is None else dict(formant=a.formant, lifter=a.lifter)
     if a.locked:
         fkw["locked"] = True
@@ -789,7 +846,7 @@ def main(argv=None):
             raise SystemExit("stretch needs --stretch FACTOR")
         try:
             outs = pv_stretch(voices, a.stretch, shift=0.0 if a.shift is None else a.shift, F=a.frame, hop=a.hop, device=a.device,
-                              **({"locked": True} if a.locked else {}))
+                              **({"locked": True} if a.locked else {}), **({} if a.transients is None else {"transients": a.transients, "span": a.span}))
         except ValueError as e:
             raise SystemExit(str(e))
         return _write_outputs(a, fs, outs)

@@ -146,6 +146,12 @@ def load_library():
         L.vp_stretch_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]
     if hasattr(L, "vp_stft_time_stretch_locked"):      # (the locked time stretch; absent from older libraries loaded through VP_AMD_LIB)
         L.vp_stft_time_stretch_locked.argtypes = [vp, fp, C.c_int, C.c_void_p, fp, C.c_void_p, C.c_void_p]
+    if hasattr(L, "vp_stft_onset_flux"):               # (the transient-preserving stretch; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_onset_num_frames.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.vp_stft_onset_flux.argtypes = [vp, fp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_onset_pick.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+        L.vp_stretch_positions_transient.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.vp_stft_time_stretch_locked_reset.argtypes = [vp, fp, C.c_int, C.c_void_p, fp, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "vp_stft_track_pitch"):              # (the pitch tracker; absent from older libraries loaded through VP_AMD_LIB)
         L.vp_track_tau_max.argtypes = [C.c_double]
         L.vp_stft_track_pitch.argtypes = [vp, fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -554,6 +560,51 @@ def stretch_positions(n_frames, hop, stretch, n_in, frame_len=1024):
     if rc:
         raise VpError(rc, L.vp_error_string(rc).decode())
     return pos
+
+
+ONSET_THRESHOLD = 0.2                   # include/vp_amd.h VP_DEFAULT_ONSET_THRESHOLD (DESIGN.md says why)
+ONSET_SPAN_MIN, ONSET_SPAN_MAX = 1, 8   # include/vp_amd.h VP_ONSET_SPAN_MIN, VP_ONSET_SPAN_MAX
+
+
+def default_onset_span(frame_len, hop):
+    """The span's half width K the tools take when none is given: max(frame_len / (2 hop), 1) -- the frames that overlap the onset's."""
+    return max(int(frame_len) // (2 * int(hop)), 1)
+
+
+def pick_onsets(flux, mass, thr=ONSET_THRESHOLD):
+    """The onsets of one row from its flux and mass tables (StftRoundTrip.onset_flux), uint8 [nG] through the library's vp_onset_pick:
+    frame g is an onset iff flux[g] > 0, flux[g] >= thr mass[g], flux[g] > flux[g-1] and flux[g] >= flux[g+1]; a missing neighbour counts
+    as -inf, a NaN in a comparison is "no".  thr in [0, 1]; VpError outside.  No device is touched."""
+    L = load_library()
+    fl, ms = np.ascontiguousarray(flux, dtype=np.float64), np.ascontiguousarray(mass, dtype=np.float64)
+    if fl.ndim != 1 or fl.shape != ms.shape:
+        raise ValueError(f"pick_onsets: flux and mass are one row each of one length, got {fl.shape} and {ms.shape}")
+    on = np.zeros(fl.shape, dtype=np.uint8)
+    rc = L.vp_onset_pick(fl.ctypes.data, ms.ctypes.data, fl.size, float(thr), on.ctypes.data)
+    if rc:
+        raise VpError(rc, L.vp_error_string(rc).decode())
+    return on
+
+
+def stretch_positions_transient(onsets, n_frames, hop, stretch, n_in, frame_len=1024, span=None):
+    """(pos int32 [n_frames], reset uint8 [n_frames]) through the library's vp_stretch_positions_transient: a constant stretch's table in
+    which a span of 2 span + 1 frames around every accepted onset is read exactly hop apart, the stretch made up between the spans, and
+    the span's first frame flagged for a phase reset (include/vp_amd.h writes the rules out).  onsets: uint8 [nG] over the input's own
+    grid, nG = (n_in - frame_len) // hop + 1.  span: 1 .. 8, None = default_onset_span(frame_len, hop).  With no accepted onset the table
+    is the two-anchor line, not stretch_positions's.  VpError as stretch_positions, or for a span out of range.  No device is touched."""
+    L = load_library()
+    K = default_onset_span(frame_len, hop) if span is None else int(span)
+    on = np.ascontiguousarray(onsets, dtype=np.uint8)
+    nG = L.vp_onset_num_frames(int(n_in), int(frame_len), int(hop))
+    if nG < 0:
+        raise VpError(nG, L.vp_error_string(nG).decode())
+    if on.shape != (nG,):
+        raise ValueError(f"stretch_positions_transient: onsets: [{nG}] expected, got {on.shape}")
+    pos, reset = np.zeros(int(n_frames), dtype=np.int32), np.zeros(int(n_frames), dtype=np.uint8)
+    rc = L.vp_stretch_positions_transient(pos.ctypes.data, reset.ctypes.data, int(n_frames), int(hop), float(stretch), int(n_in), int(frame_len), on.ctypes.data, K)
+    if rc:
+        raise VpError(rc, L.vp_error_string(rc).decode())
+    return pos, reset
 
 
 def _is(t, dtype, shape):
@@ -973,17 +1024,70 @@ class StftRoundTrip(_Handle):
         d_pos = self._position_table(positions, stretch, d_pos, n_in, d_in.device)
         self._chk(self.L.vp_stft_time_stretch(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), float(semitones), _stream_of(stream, d_in)))
 
-    def time_stretch_locked(self, d_in, d_out, positions=None, stretch=None, semitones=None, stream=None, d_pos=None, d_ratio=None):
+    def onset_flux(self, d_in, d_flux=None, d_mass=None, stream=None):
+        """The onset flux of the input's own frame grid (vp_stft_onset_flux; 1024-point frames): d_in float32 [S][n_in], any
+        n_in >= frame_len -> (flux, mass), device float64 [S][nG], nG = (n_in - frame_len) // hop + 1: mass[g] the sum of frame g's 513
+        magnitudes, flux[g] the sum of their rises over frame g - 1 (flux[0] = 0).  d_flux, d_mass: tensors to write into; None: new ones,
+        the caller's to keep.  No synchronisation.  The host picks the onsets (pick_onsets) and plans around them
+        (stretch_positions_transient)."""
+        torch = _T or _torch()
+        assert d_in.is_cuda and d_in.dtype == torch.float32 and d_in.dim() == 2 and d_in.shape[0] == self.S and d_in.is_contiguous()
+        n_in = int(d_in.shape[1])
+        assert n_in >= self.F, n_in
+        nG = (n_in - self.F) // self.hop + 1
+        if d_flux is None:
+            d_flux = torch.empty((self.S, nG), dtype=torch.float64, device=d_in.device)
+        if d_mass is None:
+            d_mass = torch.empty((self.S, nG), dtype=torch.float64, device=d_in.device)
+        assert _is(d_flux, torch.float64, (self.S, nG)) and _is(d_mass, torch.float64, (self.S, nG))
+        self._track_chk(self.L.vp_stft_onset_flux(self.h, d_in.data_ptr(), n_in, d_flux.data_ptr(), d_mass.data_ptr(), _stream_of(stream, d_in)))
+        return d_flux, d_mass
+
+    def _transient_tables(self, d_in, n_in, stretch, thr, span, stream):
+        """flux -> copy -> pick and plan per stream -> upload: the device position and reset tables of a transients= call.  ONE
+        synchronisation: the copy of the flux tables to the host."""
+        torch = _T or _torch()
+        assert stretch is not None, "transients= plans a constant stretch: give stretch="
+        a = np.broadcast_to(np.asarray(stretch, dtype=np.float64).reshape(-1), (self.S,))
+        d_flux, d_mass = self.onset_flux(d_in, stream=stream)
+        both = torch.stack((d_flux, d_mass)).cpu().numpy()                    # (the call's one synchronisation)
+        pos, reset = np.empty((self.S, self.n_frames), np.int32), np.empty((self.S, self.n_frames), np.uint8)
+        for s in range(self.S):
+            pos[s], reset[s] = stretch_positions_transient(pick_onsets(both[0, s], both[1, s], thr), self.n_frames, self.hop, a[s], n_in, self.F, span)
+        d_reset = self._stretch_tables.get("reset")
+        if d_reset is None or tuple(d_reset.shape) != reset.shape:
+            d_reset = self._stretch_tables["reset"] = torch.empty(reset.shape, dtype=torch.uint8, device=d_in.device)
+        d_reset.copy_(torch.from_numpy(reset))
+        return self._position_table(pos, None, None, n_in, d_in.device), d_reset
+
+    def time_stretch_locked(self, d_in, d_out, positions=None, stretch=None, semitones=None, stream=None, d_pos=None, d_ratio=None, d_reset=None,
+                            transients=None, span=None):
         """time_stretch with peak locking (vp_stft_time_stretch_locked; 1024-point frames): the frames are analysed at the table's positions
         as in time_stretch, and the stage between the transforms is pitch_shift_locked's with the frame's own analysis advance -- a
         sinusoid's main lobe stays one windowed sinusoid under any stretch, with or without a pitch shift on top (the definition is
         tests/pv_stretch_lock_reference.py).  positions, stretch and d_pos as in time_stretch, from the same per-handle tables.  The pitch
         is per frame and per stream: `semitones` a scalar, [n_frames] (every stream follows the curve) or [S][n_frames], each |value| <= 12,
         None = no shift; d_ratio instead: a device float64 tensor [S][n_frames] of ratios, used as it is (the kernel clamps to [0.5, 2]).
-        A 2048-point handle raises VpError (VP_ERR_GEOMETRY)."""
+        A 2048-point handle raises VpError (VP_ERR_GEOMETRY).
+        d_reset: a device uint8 tensor [S][n_frames]; a frame with a non-zero byte restarts the angles (vp_stft_time_stretch_locked_reset:
+        every peak's angle is 0 there), an all-zero table gives the call without it, bit for bit.
+        transients=thr (with stretch=; True: the default threshold 0.2): the transient-preserving stretch in one call -- onset_flux,
+        the flux tables copied to the host, pick_onsets(thr) and stretch_positions_transient(span) per stream against the input's
+        length, the tables uploaded, the reset kernel.  It SYNCHRONISES ONCE, for the copy of the flux tables; the explicit four steps
+        give the same bits.  span: the span's half width in frames, 1 .. 8, None = max(frame_len / (2 hop), 1)."""
         n_in = self._io(d_in, d_out, any_length=True)
-        d_pos = self._position_table(positions, stretch, d_pos, n_in, d_in.device)
+        if transients is not None and transients is not False:
+            assert positions is None and d_pos is None and d_reset is None, "transients= plans its own tables from stretch="
+            thr = ONSET_THRESHOLD if transients is True else float(transients)
+            d_pos, d_reset = self._transient_tables(d_in, n_in, stretch, thr, span, stream)
+        else:
+            d_pos = self._position_table(positions, stretch, d_pos, n_in, d_in.device)
         d_ratio = self._ratio_table(semitones, d_ratio, d_in.device, scalar=True, none_is_zero=True)
+        if d_reset is not None:
+            assert _is(d_reset, (_T or _torch()).uint8, (self.S, self.n_frames))
+            self._track_chk(self.L.vp_stft_time_stretch_locked_reset(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(),
+                                                                     d_reset.data_ptr(), _stream_of(stream, d_in)))
+            return
         self._track_chk(self.L.vp_stft_time_stretch_locked(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(),
                                                            _stream_of(stream, d_in)))
 
