@@ -158,7 +158,8 @@ def test_the_run_partition_changes_no_bit():
 
 
 # ---- 4. streaming -------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("c", XC.STREAM_CASES, ids=XC.stream_id)
+# (+ hop 128, which XC.STREAM_CASES compare with the one-shot at no block size)
+@pytest.mark.parametrize("c", XC.STREAM_CASES + [XC.StreamCase(256, 128, 20, 32)], ids=XC.stream_id)
 def test_streaming_is_bit_identical_to_the_one_shot_and_grouping_changes_no_bit(c):
     from vocoderproject_amd import CrossSynthStream, StftRoundTrip
     v, x = XC.stream_input(c)

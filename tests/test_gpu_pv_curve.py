@@ -176,7 +176,8 @@ def test_streaming_curve_matches_numpy():
 
 
 # ---- 4. the one-shot curve against the streaming curve --------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,hop,nb", [(1024, 256, 8), (100, 128, 60), (256, 512, 24)])
+# (64, 256): a first call in which no frame completes; (256, 256): the call of 16 blocks starts at the stream's frame 1, wavefront 1's
+@pytest.mark.parametrize("N,hop,nb", [(1024, 256, 8), (100, 128, 60), (256, 512, 24), (64, 256, 128), (256, 256, 32)])
 def test_one_shot_and_streaming_curves_agree_bit_for_bit(N, hop, nb):
     from vocoderproject_amd import PhaseVocoderStream, StftRoundTrip, semitones_to_ratios
     S, F, T = CC.N_STREAMS, 1024, N * nb

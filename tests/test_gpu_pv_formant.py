@@ -170,7 +170,12 @@ def _stream_formant(c, x, tab, phi, spans):
     return _rows(d_out), L
 
 
-@pytest.mark.parametrize("c", FC.STREAM_CASES, ids=FC.stream_id)
+# the call shapes FC.STREAM_CASES leave out: a first call in which no frame completes (N = 64), and single blocks of 256 at hop 256 (a
+# call whose first frame is not wavefront 0's)
+MORE_STREAM_CASES = [FC.StreamFormantCase(64, 256, 128, 32), FC.StreamFormantCase(256, 256, 32, 32)]
+
+
+@pytest.mark.parametrize("c", FC.STREAM_CASES + MORE_STREAM_CASES, ids=FC.stream_id)
 def test_streaming_formant_is_bit_identical_to_the_one_shot_and_grouping_changes_no_bit(c):
     from vocoderproject_amd import StftRoundTrip, semitones_to_ratios
     T = c.N * c.n_blocks

@@ -850,6 +850,11 @@ hipError_t vp_stft_launch(const VpStftArgs &a, int nStreams, int nRuns, hipStrea
 //     between a round's additions and its stores.
 // History (samples of frames not yet complete, < F), carry (< F unfinished or unemitted samples), phases, accumulator, ratio and the
 // sample counter are read into LDS at entry and written back at exit.
+// What of this is the arithmetic of one process call and not signal processing -- which frames complete in the call, history and carry
+// between the record and LDS, the slab index maps, the ring's overlap-add and emission, the flush -- is the pv_call_* helpers below, ONE
+// copy for four of the seven streaming kernels: this one, vp_k_pv_stream_lockf, vp_k_hz_stream and vp_k_xs_stream.  The kernels keep
+// their LDS carve, per-lane constants, request prefetch, stage, merge and their own record fields.  vp_k_pv_stream_curve, _lock and
+// _formant keep the same statements WRITTEN OUT: through the helpers they ran 0.6 - 1.2 % slower (docs/HISTORY.md).
 // LDS: exchange buffers / output slots, ring, history, then the one-shot's phase-vocoder arrays (124 KB: one workgroup per CU)
 __host__ __device__ constexpr size_t pv_stream_lds_bytes() { return (size_t)NWV * 8192 + (VP_PV_RING + 1024) * sizeof(float) + pv_lds_bytes(); }
 
@@ -866,13 +871,121 @@ __device__ __forceinline__ bool pv_scan_updates(const VpPvArgs &A, int s, double
     return rst;
 }
 
+// ---- one process call's bookkeeping (F = 1024, four wavefronts) ----
+// A stream that has received n samples takes M more.  Indices are RELATIVE to sample fa hop, the start of the first frame the call
+// completes: the history is [0, H), the call's samples [H, H + M), relative frame fr covers [fr hop, fr hop + F).
+struct PvCall {
+    int M;                      // samples this call
+    long long R;                // samples received after it
+    long long fa;               // frames complete before the call (fa + nf after it)
+    int nf;                     // frames of this call
+    int H;                      // history: samples [fa hop, n) (< F)
+    int er;                     // relative index of the next sample to emit (output time n)
+    int fr0;                    // relative frame of wavefront 0 in the first round (<= 0: wavefront w takes the frames 4 r + w by global index)
+};
+constexpr int PV_CALL_F = 1024, PV_CALL_RM = VP_PV_RING - 1, PV_CALL_T = 64 * NWV;
+
+__host__ __device__ constexpr PvCall pv_call_geometry(long long n, int M, int hop, int L)
+{
+    const long long R = n + M;
+    const long long fa = n >= PV_CALL_F ? (n - PV_CALL_F) / hop + 1 : 0;
+    const long long fb = R >= PV_CALL_F ? (R - PV_CALL_F) / hop + 1 : 0;
+    const int nf = (int)(fb - fa);
+    const int H = (int)(n - fa * hop);
+    return PvCall{M, R, fa, nf, H, H - L, -(int)(fa & 3)};
+}
+// the call's rounds of four frames.  A function of its own, called where the kernels' round loops begin: as a member filled by
+// pv_call_geometry (in front of the state loads) a kernel built on it took 6 more registers (docs/HISTORY.md)
+__host__ __device__ constexpr int pv_call_rounds(const PvCall &c) { return c.nf > 0 ? (c.nf - c.fr0 + NWV - 1) / NWV : 0; }
+constexpr bool pv_call_is(const PvCall &c, long long fa, long long fb, int nf, int H, int er, int fr0, int nRounds)
+{
+    return c.fa == fa && c.fa + c.nf == fb && c.nf == nf && c.H == H && c.er == er && c.fr0 == fr0 && pv_call_rounds(c) == nRounds;
+}
+//                                          n     M  hop     L    fa  fb  nf    H    er fr0 nRounds
+static_assert(pv_call_is(pv_call_geometry(0, 64, 256, 960), 0, 0, 0, 0, -960, 0, 0), "a first call in which no frame completes");
+static_assert(pv_call_is(pv_call_geometry(0, 1024, 256, 768), 0, 1, 1, 0, -768, 0, 1), "the stream's first frame");
+static_assert(pv_call_is(pv_call_geometry(1024, 256, 256, 768), 1, 2, 1, 768, 0, -1, 1), "a call whose first frame is wavefront 1's");
+static_assert(pv_call_is(pv_call_geometry(1792, 4096, 256, 768), 4, 20, 16, 768, 0, 0, 4), "four whole rounds");
+// hop 128, three blocks of 100 (L = 1024 - gcd(100, 128)): fa = 76 / 128 + 1, fb = 376 / 128 + 1, H = 1100 - 128, rounds = (2 + 1 + 3) / 4
+static_assert(pv_call_is(pv_call_geometry(1100, 300, 128, 1020), 1, 3, 2, 972, -48, -1, 1), "hop 128, N no multiple of the hop");
+
+// state -> LDS.  The history; then the ring from the carry, carry[i] = one-shot sample er + i (a reset stream starts from zeros)
+__device__ __forceinline__ void pv_call_load_hist(const PvCall &c, lds_f32 *hist, const float *recHist, int tid)
+{
+    for (int i = tid; i < c.H; i += PV_CALL_T) hist[i] = recHist[i];
+}
+__device__ __forceinline__ void pv_call_load_ring(const PvCall &c, lds_f32 *ring, const float *recCarry, bool rst, int tid)
+{
+    for (int q = tid; q < VP_PV_RING; q += PV_CALL_T) {
+        const int i = (q - c.er) & PV_CALL_RM;
+        ring[q] = (i < PV_CALL_F && !rst) ? recCarry[i] : 0.f;
+    }
+}
+
+// the index maps over [block][stream][NB] slabs; xs / ys point at stream s of block 0
+// sample at relative index rel (>= 0): the history below H, this call's blocks above
+__device__ __forceinline__ float pv_call_sample(const PvCall &c, const lds_f32 *hist, const float *xs, int NB, int S, int rel)
+{
+    if (rel < c.H) return hist[rel];
+    const unsigned k = (unsigned)(rel - c.H), b = k / (unsigned)NB;
+    return xs[(size_t)b * S * NB + (k - b * NB)];
+}
+// the finished ring samples of relative indices [from, to) leave to output time n + (j - er), j - er in [0, M); ring word q belongs to
+// thread q mod 256 throughout: no barrier between a round's additions and its stores
+__device__ __forceinline__ void pv_call_emit(const PvCall &c, lds_f32 *ring, float *ys, int NB, int S, int from, int to, int tid)
+{
+    for (int j = from + ((tid - from) & (PV_CALL_T - 1)); j < to; j += PV_CALL_T) {
+        const float v = ring[j & PV_CALL_RM];
+        const unsigned k = (unsigned)(j - c.er), b = k / (unsigned)NB;
+        ys[(size_t)b * S * NB + (k - b * NB)] = v;
+        ring[j & PV_CALL_RM] = 0.f;
+    }
+}
+
+// a round's tail (between the barrier behind the slot writes and the round's last): the overlap-add of the round's frames
+// [frW0 + wFirst, frW0 + wLast] in frame order, then the samples they finish that fall inside the call.  Returns the next relative index to
+// emit (uniform).  After the last round pv_call_emit(c, .., cb, c.er + c.M, ..) flushes the rest of the call's output: finished in earlier
+// calls or rounds (or before the stream's first sample: zeros)
+__device__ __forceinline__ int pv_call_round_tail(const PvCall &c, lds_f32 *ring, const lds_f32 *slots, float *ys, int NB, int S, int hop, int frW0, int wFirst,
+                                                  int wLast, int cb, int tid)
+{
+    const int frA = frW0 + wFirst, frB = frW0 + wLast;
+    const int lo = frA * hop, hi = frB * hop + PV_CALL_F;
+    for (int j = lo + ((tid - lo) & (PV_CALL_T - 1)); j < hi; j += PV_CALL_T) {
+        float v = ring[j & PV_CALL_RM];
+        for (int w = wFirst; w <= wLast; w++) {
+            const int o = j - (frW0 + w) * hop;
+            if (o >= 0 && o < PV_CALL_F) v += slots[w * 2048 + o];
+        }
+        ring[j & PV_CALL_RM] = v;
+    }
+    const int emitEnd = min((frB + 1) * hop, c.er + c.M);
+    pv_call_emit(c, ring, ys, NB, S, cb, emitEnd, tid);
+    return max(cb, emitEnd);
+}
+
+// LDS -> state.  History: samples [fb hop, R); carry: one-shot samples from the next one to emit (relative er + M) on
+__device__ __forceinline__ void pv_call_store_hist(const PvCall &c, float *recHist, const lds_f32 *hist, const float *xs, int NB, int S, int hop, int tid)
+{
+    const int Hn = c.H + c.M - c.nf * hop;
+    for (int i = tid; i < Hn; i += PV_CALL_T) recHist[i] = pv_call_sample(c, hist, xs, NB, S, c.nf * hop + i);
+}
+__device__ __forceinline__ void pv_call_store_carry(const PvCall &c, float *recCarry, const lds_f32 *ring, int tid)
+{
+    const int ern = c.er + c.M;
+    for (int q = tid; q < VP_PV_RING; q += PV_CALL_T) {
+        const int i = (q - ern) & PV_CALL_RM;
+        if (i < PV_CALL_F) recCarry[i] = ring[q];
+    }
+}
+
 __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream(VpPvArgs A)
 {
     extern __shared__ double smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int s = blockIdx.x;
-    constexpr int N = 512, F = 1024, nb = N + 1, RM = VP_PV_RING - 1;
-    const int hop = A.hop, O = A.O, L = A.L, NB = A.N, S = A.S;
+    constexpr int N = 512, F = 1024, nb = N + 1;
+    const int hop = A.hop, O = A.O, NB = A.N, S = A.S;
     lds_d2 *xb = (lds_d2 *)smem + wv * 512;
     lds_f32 *slots = (lds_f32 *)smem;                                          // wavefront w's output frame at w * 2048
     lds_f32 *ring = (lds_f32 *)smem + NWV * 2048;                              // [VP_PV_RING]
@@ -890,23 +1003,13 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream(VpPvArgs A)
     long long n = ((const long long *)recD)[VP_PV_COUNT];                     // samples received before this call
     const bool rst = pv_scan_updates(A, s, ratio);
     if (rst) n = 0;
-
-    const int M = A.nBlocks * NB;                                              // samples this call
-    const long long R = n + M;
-    const long long fa = n >= F ? (n - F) / hop + 1 : 0;                       // frames complete before the call
-    const long long fb = R >= F ? (R - F) / hop + 1 : 0;                       // ... and after it
-    const int nf = (int)(fb - fa);                                             // frames of this call
-    const int H = (int)(n - fa * hop);                                         // history: samples [fa hop, n) (< F), relative index 0 .. H - 1
-    const int er = H - L;                                                      // relative index of the next sample to emit (output time n)
-    const int fr0 = -(int)(fa & 3);                                            // relative frame of wavefront 0 in the first round
+    const PvCall C = pv_call_geometry(n, A.nBlocks * NB, hop, A.L);
+    const int nf = C.nf;
 
     // state -> LDS (a reset stream starts from zeros)
-    for (int i = tid; i < H; i += 64 * NWV) hist[i] = recHist[i];
+    pv_call_load_hist(C, hist, recHist, tid);
     for (int i = tid; i < nb; i += 64 * NWV) { pv.phPrev[i] = rst ? 0.0 : recD[i]; pv.sum[i] = rst ? 0.0 : recD[nb + i]; }
-    for (int q = tid; q < VP_PV_RING; q += 64 * NWV) {                         // carry[i] = one-shot sample er + i
-        const int i = (q - er) & RM;
-        ring[q] = (i < F && !rst) ? recCarry[i] : 0.f;
-    }
+    pv_call_load_ring(C, ring, recCarry, rst, tid);
 
     FftLane Lf;
     fft_lane_init(Lf, lane, A.tw1, A.tw2);
@@ -921,30 +1024,22 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream(VpPvArgs A)
 
     const float *xs = A.in + (size_t)s * NB;
     float *ys = A.out + (size_t)s * NB;
-    // sample at relative index rel (>= 0): the history below H, this call's blocks above
-    auto sample = [&](int rel) -> float {
-        if (rel < H) return hist[rel];
-        const unsigned c = (unsigned)(rel - H), b = c / (unsigned)NB;
-        return xs[(size_t)b * S * NB + (c - b * NB)];
-    };
-    // output time n + c, c in [0, M)
-    auto emit = [&](int c, float v) {
-        const unsigned b = (unsigned)c / (unsigned)NB;
-        ys[(size_t)b * S * NB + ((unsigned)c - b * NB)] = v;
-    };
-    const int nRounds = nf > 0 ? (nf - fr0 + NWV - 1) / NWV : 0;
-    int cb = er;                                                               // next relative index to emit (uniform)
+    const int nRounds = pv_call_rounds(C);
+    int cb = C.er;                                                             // next relative index to emit (uniform)
     f2 xv[8];
     auto request = [&](int k_) {
-        const int fr_ = fr0 + NWV * k_ + wv;
+        const int fr_ = C.fr0 + NWV * k_ + wv;
         if (k_ < nRounds && fr_ >= 0 && fr_ < nf) {
 #pragma unroll
-            for (int r = 0; r < 8; r++) { const int rel = fr_ * hop + 2 * (lane + 64 * r); xv[r] = f2{sample(rel), sample(rel + 1)}; }
+            for (int r = 0; r < 8; r++) {
+                const int rel = fr_ * hop + 2 * (lane + 64 * r);
+                xv[r] = f2{pv_call_sample(C, hist, xs, NB, S, rel), pv_call_sample(C, hist, xs, NB, S, rel + 1)};
+            }
         }
     };
     request(0);
     for (int k = 0; k < nRounds; k++) {
-        const int frW0 = fr0 + NWV * k;                                        // relative frame of wavefront 0 in this round
+        const int frW0 = C.fr0 + NWV * k;                                      // relative frame of wavefront 0 in this round
         const int fr = frW0 + wv;
         const bool live = fr >= 0 && fr < nf;                                  // (wavefront-uniform)
         const int wFirst = max(0, -frW0), wLast = min(NWV - 1, nf - 1 - frW0);
@@ -1044,36 +1139,17 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream(VpPvArgs A)
             for (int r = 0; r < 8; r++) slot[lane + 64 * r] = f2{(float)(z.re[r] * wa[r].x), (float)(-(z.im[r] * wa[r].y))};
         }
         __syncthreads();
-        // overlap-add of the round's frames [frA, frB] in frame order, then the samples they finish that fall inside the call
-        const int frA = frW0 + wFirst, frB = frW0 + wLast;
-        const int lo = frA * hop, hi = frB * hop + F;
-        for (int j = lo + ((tid - lo) & (64 * NWV - 1)); j < hi; j += 64 * NWV) {
-            float v = ring[j & RM];
-            for (int w = wFirst; w <= wLast; w++) {
-                const int o = j - (frW0 + w) * hop;
-                if (o >= 0 && o < F) v += slots[w * 2048 + o];
-            }
-            ring[j & RM] = v;
-        }
-        const int emitEnd = min((frB + 1) * hop, er + M);
-        for (int j = cb + ((tid - cb) & (64 * NWV - 1)); j < emitEnd; j += 64 * NWV) { emit(j - er, ring[j & RM]); ring[j & RM] = 0.f; }
-        cb = max(cb, emitEnd);
+        cb = pv_call_round_tail(C, ring, slots, ys, NB, S, hop, frW0, wFirst, wLast, cb, tid);
         __syncthreads();
     }
-    // the rest of the call's output: finished in earlier calls or rounds (or before the stream's first sample: zeros)
-    for (int j = cb + ((tid - cb) & (64 * NWV - 1)); j < er + M; j += 64 * NWV) { emit(j - er, ring[j & RM]); ring[j & RM] = 0.f; }
+    pv_call_emit(C, ring, ys, NB, S, cb, C.er + C.M, tid);                     // the flush
 
-    // LDS -> state.  History: samples [fb hop, R); carry: one-shot samples from the next one to emit (relative er + M) on
-    const int Hn = H + M - nf * hop;
-    for (int i = tid; i < Hn; i += 64 * NWV) recHist[i] = sample(nf * hop + i);
-    const int ern = er + M;
-    for (int q = tid; q < VP_PV_RING; q += 64 * NWV) {
-        const int i = (q - ern) & RM;
-        if (i < F) recCarry[i] = ring[q];
-    }
+    // LDS -> state
+    pv_call_store_hist(C, recHist, hist, xs, NB, S, hop, tid);
+    pv_call_store_carry(C, recCarry, ring, tid);
     __syncthreads();                                                           // (slot 0 / sum of the last round)
     for (int i = tid; i < nb; i += 64 * NWV) { recD[i] = pv.phPrev[i]; recD[nb + i] = pv.sum[i]; }
-    if (tid == 0) { recD[VP_PV_RATIO] = ratio; ((long long *)recD)[VP_PV_COUNT] = R; }
+    if (tid == 0) { recD[VP_PV_RATIO] = ratio; ((long long *)recD)[VP_PV_COUNT] = C.R; }
 }
 
 // the updates alone (a call with more than VP_PV_MAX_UPDATES of them pending enqueues this first, on the same stream)

@@ -159,8 +159,9 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_cross(VpStftArgs A, const 
     }
 }
 
-// ---- streaming: one workgroup per stream and call.  vp_k_pv_stream's bookkeeping (frames by their global index, ring, emit, history
-// write-back) with two input histories and no phase arrays; the stage is the one-shot's, so the outputs agree bit for bit.
+// ---- streaming: one workgroup per stream and call.  The call's bookkeeping (frames by their global index, ring, emit, history
+// write-back) is the pv_call_* helpers of vp_stft.hip, with two input histories and no phase arrays; the stage is the one-shot's, so the
+// outputs agree bit for bit.
 // LDS: four exchange buffers / output slots, ring, voice history, carrier history = 56 KB
 __host__ __device__ constexpr size_t xs_stream_lds_bytes() { return (size_t)NWV * 8192 + (VP_PV_RING + 2 * 1024) * sizeof(float); }
 
@@ -178,8 +179,8 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_xs_stream(VpXsArgs A)
     extern __shared__ double smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int s = blockIdx.x;
-    constexpr int F = 1024, RM = VP_PV_RING - 1;
-    const int hop = A.hop, L = A.L, NB = A.N, S = A.S;
+    constexpr int F = 1024;
+    const int hop = A.hop, NB = A.N, S = A.S;
     lds_d2 *xb = (lds_d2 *)smem + wv * 512;
     lds_f32 *slots = (lds_f32 *)smem;                                          // wavefront w's output frame at w * 2048
     lds_f32 *ring = (lds_f32 *)smem + NWV * 2048;                              // [VP_PV_RING]
@@ -194,22 +195,13 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_xs_stream(VpXsArgs A)
     long long n = *(const long long *)rec;                                     // samples received before this call
     const bool rst = xs_scan_updates(A, s);
     if (rst) n = 0;
-
-    const int M = A.nBlocks * NB;                                              // samples this call
-    const long long R = n + M;
-    const long long fa = n >= F ? (n - F) / hop + 1 : 0;                       // frames complete before the call
-    const long long fb = R >= F ? (R - F) / hop + 1 : 0;                       // ... and after it
-    const int nf = (int)(fb - fa);                                             // frames of this call
-    const int H = (int)(n - fa * hop);                                         // history: samples [fa hop, n) (< F), relative index 0 .. H - 1
-    const int er = H - L;                                                      // relative index of the next sample to emit (output time n)
-    const int fr0 = -(int)(fa & 3);                                            // relative frame of wavefront 0 in the first round
+    const PvCall C = pv_call_geometry(n, A.nBlocks * NB, hop, A.L);
+    const int nf = C.nf;
 
     // state -> LDS (a reset stream starts from zeros)
-    for (int i = tid; i < H; i += 64 * NWV) { histV[i] = recV[i]; histC[i] = recC[i]; }
-    for (int q = tid; q < VP_PV_RING; q += 64 * NWV) {                         // carry[i] = one-shot sample er + i
-        const int i = (q - er) & RM;
-        ring[q] = (i < F && !rst) ? recCarry[i] : 0.f;
-    }
+    pv_call_load_hist(C, histV, recV, tid);
+    pv_call_load_hist(C, histC, recC, tid);
+    pv_call_load_ring(C, ring, recCarry, rst, tid);
 
     FftAddr Lf;
     fft_addr_init(Lf, lane);
@@ -229,34 +221,23 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_xs_stream(VpXsArgs A)
 
     const float *vs = A.voice + (size_t)s * NB, *cs = A.carrier + (size_t)s * NB;
     float *ys = A.out + (size_t)s * NB;
-    // sample at relative index rel (>= 0): the history below H, this call's blocks above
-    auto sample = [&](const lds_f32 *hist, const float *xs, int rel) -> float {
-        if (rel < H) return hist[rel];
-        const unsigned c = (unsigned)(rel - H), b = c / (unsigned)NB;
-        return xs[(size_t)b * S * NB + (c - b * NB)];
-    };
-    // output time n + c, c in [0, M)
-    auto emit = [&](int c, float v) {
-        const unsigned b = (unsigned)c / (unsigned)NB;
-        ys[(size_t)b * S * NB + ((unsigned)c - b * NB)] = v;
-    };
-    const int nRounds = nf > 0 ? (nf - fr0 + NWV - 1) / NWV : 0;
-    int cb = er;                                                               // next relative index to emit (uniform)
+    const int nRounds = pv_call_rounds(C);
+    int cb = C.er;                                                             // next relative index to emit (uniform)
     f2 xv[8], xc[8];
     auto request = [&](int k_) {
-        const int fr_ = fr0 + NWV * k_ + wv;
+        const int fr_ = C.fr0 + NWV * k_ + wv;
         if (k_ < nRounds && fr_ >= 0 && fr_ < nf) {
 #pragma unroll
             for (int r = 0; r < 8; r++) {
                 const int rel = fr_ * hop + 2 * (lane + 64 * r);
-                xv[r] = f2{sample(histV, vs, rel), sample(histV, vs, rel + 1)};
-                xc[r] = f2{sample(histC, cs, rel), sample(histC, cs, rel + 1)};
+                xv[r] = f2{pv_call_sample(C, histV, vs, NB, S, rel), pv_call_sample(C, histV, vs, NB, S, rel + 1)};
+                xc[r] = f2{pv_call_sample(C, histC, cs, NB, S, rel), pv_call_sample(C, histC, cs, NB, S, rel + 1)};
             }
         }
     };
     request(0);
     for (int k = 0; k < nRounds; k++) {
-        const int frW0 = fr0 + NWV * k;                                        // relative frame of wavefront 0 in this round
+        const int frW0 = C.fr0 + NWV * k;                                      // relative frame of wavefront 0 in this round
         const int fr = frW0 + wv;
         const bool live = fr >= 0 && fr < nf;                                  // (wavefront-uniform)
         const int wFirst = max(0, -frW0), wLast = min(NWV - 1, nf - 1 - frW0);
@@ -286,34 +267,16 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_xs_stream(VpXsArgs A)
             for (int r = 0; r < 8; r++) slot[lane + 64 * r] = f2{(float)(zc.re[r] * wa[r].x), (float)(-(zc.im[r] * wa[r].y))};
         }
         __syncthreads();
-        // overlap-add of the round's frames [frA, frB] in frame order, then the samples they finish that fall inside the call
-        const int frA = frW0 + wFirst, frB = frW0 + wLast;
-        const int lo = frA * hop, hi = frB * hop + F;
-        for (int j = lo + ((tid - lo) & (64 * NWV - 1)); j < hi; j += 64 * NWV) {
-            float v = ring[j & RM];
-            for (int w = wFirst; w <= wLast; w++) {
-                const int o = j - (frW0 + w) * hop;
-                if (o >= 0 && o < F) v += slots[w * 2048 + o];
-            }
-            ring[j & RM] = v;
-        }
-        const int emitEnd = min((frB + 1) * hop, er + M);
-        for (int j = cb + ((tid - cb) & (64 * NWV - 1)); j < emitEnd; j += 64 * NWV) { emit(j - er, ring[j & RM]); ring[j & RM] = 0.f; }
-        cb = max(cb, emitEnd);
+        cb = pv_call_round_tail(C, ring, slots, ys, NB, S, hop, frW0, wFirst, wLast, cb, tid);
         __syncthreads();
     }
-    // the rest of the call's output: finished in earlier calls or rounds (or before the stream's first sample: zeros)
-    for (int j = cb + ((tid - cb) & (64 * NWV - 1)); j < er + M; j += 64 * NWV) { emit(j - er, ring[j & RM]); ring[j & RM] = 0.f; }
+    pv_call_emit(C, ring, ys, NB, S, cb, C.er + C.M, tid);                     // the flush
 
-    // LDS -> state.  Histories: samples [fb hop, R); carry: one-shot samples from the next one to emit (relative er + M) on
-    const int Hn = H + M - nf * hop;
-    for (int i = tid; i < Hn; i += 64 * NWV) { recV[i] = sample(histV, vs, nf * hop + i); recC[i] = sample(histC, cs, nf * hop + i); }
-    const int ern = er + M;
-    for (int q = tid; q < VP_PV_RING; q += 64 * NWV) {
-        const int i = (q - ern) & RM;
-        if (i < F) recCarry[i] = ring[q];
-    }
-    if (tid == 0) *(long long *)rec = R;
+    // LDS -> state
+    pv_call_store_hist(C, recV, histV, vs, NB, S, hop, tid);
+    pv_call_store_hist(C, recC, histC, cs, NB, S, hop, tid);
+    pv_call_store_carry(C, recCarry, ring, tid);
+    if (tid == 0) *(long long *)rec = C.R;
 }
 
 // the pending resets alone (a call with more than VP_PV_MAX_UPDATES of them enqueues this first, on the same stream)

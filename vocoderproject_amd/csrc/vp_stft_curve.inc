@@ -344,7 +344,9 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv2k_curve(VpStftArgs A, c
 // ---- streaming: vp_k_pv_stream with one ratio per block and stream, ratioTab [nBlocks][S].  Relative frame fr of the call ends at
 // relative sample fr hop + F - 1 >= H (it was not complete before the call), that is in block (fr hop + F - 1 - H) / N < nBlocks.  The
 // record's ratio -- the interval of the plain calls -- is carried through with the call's pending changes applied, as the plain kernel
-// does, but no frame of this call uses it.
+// does, but no frame of this call uses it.  The call's bookkeeping is WRITTEN OUT here (and in the lock and formant builds), statement for
+// statement what the pv_call_* helpers of vp_stft.hip hold for the other four streaming kernels: through the helpers this kernel ran 1.2 %
+// slower at unchanged registers (docs/HISTORY.md, "One copy of the streaming call's bookkeeping").
 __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_curve(VpPvArgs A, const double *ratioTab)
 {
     extern __shared__ double smem[];

@@ -244,7 +244,8 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_formant(VpStftArgs A, c
     }
 }
 
-// ---- streaming: vp_k_pv_stream_curve with the formant correction; ratioTab [nBlocks][S] as there, formantTab [S]
+// ---- streaming: vp_k_pv_stream_curve with the formant correction; ratioTab [nBlocks][S] as there, formantTab [S].  The call's bookkeeping
+// is written out, as there (the comment there says why).
 __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_formant(VpPvArgs A, const double *ratioTab, const double *formantTab, int nc)
 {
     extern __shared__ double smem[];

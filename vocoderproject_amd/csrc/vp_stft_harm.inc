@@ -9,8 +9,8 @@
 // definition is tests/pv_harm_reference.py: dry roundtrip(x) + sum_v gain[v] locked_roundtrip(x, ratio[v]).
 //
 // vp_k_stft_harm and vp_k_hz_stream are WRITTEN-OUT COPIES of vp_k_stft_pv_lock and vp_k_pv_stream_lock (docs/HISTORY.md, "One
-// phase-vocoder stage for both kernels", for why copies): framing, transforms, overlap-add, ring and bookkeeping are the parents',
-// statement for statement.  What differs is marked "harm:".  pv_lock_plan is split in two: hz_analyse (once per frame: peaks, owners, and
+// phase-vocoder stage for both kernels", for why copies): framing, transforms and overlap-add are the parents', statement for statement,
+// and the streaming call's bookkeeping is the parents' pv_call_* helpers.  What differs is marked "harm:".  pv_lock_plan is split in two: hz_analyse (once per frame: peaks, owners, and
 // the peaks' true frequency nu where the parent leaves the angle's advance for its one ratio) and hz_voice_plan (per voice: shifted peaks
 // and the gather's indices, in the parents' `moved` mask and `back` map, reused voice after voice).  hz_turn forms the advance
 // (nu (r - 1)) / O with the parent's operations in the parent's order, so that one voice with gain 1 and no dry part has the locked
@@ -323,14 +323,15 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_harm(VpStftArgs A, const d
 
 // ---- streaming: vp_k_pv_stream_lock with the stage above.  harm: a record of its own (VP_HZ_*, vp_stft.h): the previous phases, the
 // sample count, history, carry and one theta array per voice, handed from the call's first live frame to its last whatever their
-// wavefronts.  ratioTab [nBlocks][S][V]; gainTab [S][V] or null (1); dryTab [S] or null (0)
+// wavefronts.  The call's bookkeeping is the pv_call_* helpers of vp_stft.hip.  ratioTab [nBlocks][S][V]; gainTab [S][V] or null (1);
+// dryTab [S] or null (0)
 __global__ __launch_bounds__(64 * NWV) void vp_k_hz_stream(VpPvArgs A, const double *ratioTab, const double *gainTab, const double *dryTab, int V)
 {
     extern __shared__ double smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int s = blockIdx.x;
-    constexpr int N = 512, F = 1024, nb = N + 1, RM = VP_PV_RING - 1;
-    const int hop = A.hop, O = A.O, L = A.L, NB = A.N, S = A.S;
+    constexpr int N = 512, F = 1024, nb = N + 1;
+    const int hop = A.hop, O = A.O, NB = A.N, S = A.S;
     lds_d2 *xb = (lds_d2 *)smem + wv * 512;
     lds_f32 *slots = (lds_f32 *)smem;
     lds_f32 *ring = (lds_f32 *)smem + NWV * 2048;                              // [VP_PV_RING]
@@ -350,23 +351,13 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_hz_stream(VpPvArgs A, const dou
     long long n = ((const long long *)recD)[VP_HZ_COUNT];
     const bool rst = pv_scan_updates(A, s, noRatio);
     if (rst) n = 0;
+    const PvCall C = pv_call_geometry(n, A.nBlocks * NB, hop, A.L);
+    const int nf = C.nf;
 
-    const int M = A.nBlocks * NB;
-    const long long R = n + M;
-    const long long fa = n >= F ? (n - F) / hop + 1 : 0;
-    const long long fb = R >= F ? (R - F) / hop + 1 : 0;
-    const int nf = (int)(fb - fa);
-    const int H = (int)(n - fa * hop);
-    const int er = H - L;
-    const int fr0 = -(int)(fa & 3);
-
-    for (int i = tid; i < H; i += 64 * NWV) hist[i] = recHist[i];
+    pv_call_load_hist(C, hist, recHist, tid);
     for (int i = tid; i < nb; i += 64 * NWV) { pv.phPrev[i] = rst ? 0.0 : recD[i]; pv.sum[i] = rst ? 0.0 : recTheta[i]; }
     for (int i = tid; i < HZ_EXTRA_THETA * nb; i += 64 * NWV) thetaX[i] = rst ? 0.0 : recTheta[nb + i];   // harm:
-    for (int q = tid; q < VP_PV_RING; q += 64 * NWV) {
-        const int i = (q - er) & RM;
-        ring[q] = (i < F && !rst) ? recCarry[i] : 0.f;
-    }
+    pv_call_load_ring(C, ring, recCarry, rst, tid);
 
     FftLane Lf;
     fft_lane_init(Lf, lane, A.tw1, A.tw2);
@@ -386,34 +377,28 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_hz_stream(VpPvArgs A, const dou
 
     const float *xs = A.in + (size_t)s * NB;
     float *ys = A.out + (size_t)s * NB;
-    auto sample = [&](int rel) -> float {
-        if (rel < H) return hist[rel];
-        const unsigned c = (unsigned)(rel - H), b = c / (unsigned)NB;
-        return xs[(size_t)b * S * NB + (c - b * NB)];
-    };
-    auto emit = [&](int c, float v) {
-        const unsigned b = (unsigned)c / (unsigned)NB;
-        ys[(size_t)b * S * NB + ((unsigned)c - b * NB)] = v;
-    };
-    const int nRounds = nf > 0 ? (nf - fr0 + NWV - 1) / NWV : 0;
-    int cb = er;
+    const int nRounds = pv_call_rounds(C);
+    int cb = C.er;
     f2 xv[8];
     double rq[VP_HARM_MAX_VOICES];
 #pragma unroll
     for (int v = 0; v < VP_HARM_MAX_VOICES; v++) rq[v] = 1.0;
     auto request = [&](int k_) {
-        const int fr_ = fr0 + NWV * k_ + wv;
+        const int fr_ = C.fr0 + NWV * k_ + wv;
         if (k_ < nRounds && fr_ >= 0 && fr_ < nf) {
 #pragma unroll
-            for (int r = 0; r < 8; r++) { const int rel = fr_ * hop + 2 * (lane + 64 * r); xv[r] = f2{sample(rel), sample(rel + 1)}; }
-            const unsigned blk = (unsigned)(fr_ * hop + F - 1 - H) / (unsigned)NB;   // the block in which the frame's last sample arrives
+            for (int r = 0; r < 8; r++) {
+                const int rel = fr_ * hop + 2 * (lane + 64 * r);
+                xv[r] = f2{pv_call_sample(C, hist, xs, NB, S, rel), pv_call_sample(C, hist, xs, NB, S, rel + 1)};
+            }
+            const unsigned blk = (unsigned)(fr_ * hop + F - 1 - C.H) / (unsigned)NB; // the block in which the frame's last sample arrives
 #pragma unroll
             for (int v = 0; v < VP_HARM_MAX_VOICES; v++) if (v < V) rq[v] = ratioTab[((size_t)blk * S + s) * V + v];   // harm:
         }
     };
     request(0);
     for (int k = 0; k < nRounds; k++) {
-        const int frW0 = fr0 + NWV * k;
+        const int frW0 = C.fr0 + NWV * k;
         const int fr = frW0 + wv;
         const bool live = fr >= 0 && fr < nf;                                  // (wavefront-uniform)
         const int wFirst = max(0, -frW0), wLast = min(NWV - 1, nf - 1 - frW0);
@@ -491,34 +476,17 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_hz_stream(VpPvArgs A, const dou
             for (int r = 0; r < 8; r++) slot[lane + 64 * r] = f2{(float)(z.re[r] * wa[r].x), (float)(-(z.im[r] * wa[r].y))};
         }
         __syncthreads();
-        const int frA = frW0 + wFirst, frB = frW0 + wLast;
-        const int lo = frA * hop, hi = frB * hop + F;
-        for (int j = lo + ((tid - lo) & (64 * NWV - 1)); j < hi; j += 64 * NWV) {
-            float v = ring[j & RM];
-            for (int w = wFirst; w <= wLast; w++) {
-                const int o = j - (frW0 + w) * hop;
-                if (o >= 0 && o < F) v += slots[w * 2048 + o];
-            }
-            ring[j & RM] = v;
-        }
-        const int emitEnd = min((frB + 1) * hop, er + M);
-        for (int j = cb + ((tid - cb) & (64 * NWV - 1)); j < emitEnd; j += 64 * NWV) { emit(j - er, ring[j & RM]); ring[j & RM] = 0.f; }
-        cb = max(cb, emitEnd);
+        cb = pv_call_round_tail(C, ring, slots, ys, NB, S, hop, frW0, wFirst, wLast, cb, tid);
         __syncthreads();
     }
-    for (int j = cb + ((tid - cb) & (64 * NWV - 1)); j < er + M; j += 64 * NWV) { emit(j - er, ring[j & RM]); ring[j & RM] = 0.f; }
+    pv_call_emit(C, ring, ys, NB, S, cb, C.er + C.M, tid);                     // the flush
 
-    const int Hn = H + M - nf * hop;
-    for (int i = tid; i < Hn; i += 64 * NWV) recHist[i] = sample(nf * hop + i);
-    const int ern = er + M;
-    for (int q = tid; q < VP_PV_RING; q += 64 * NWV) {
-        const int i = (q - ern) & RM;
-        if (i < F) recCarry[i] = ring[q];
-    }
+    pv_call_store_hist(C, recHist, hist, xs, NB, S, hop, tid);
+    pv_call_store_carry(C, recCarry, ring, tid);
     __syncthreads();
     for (int i = tid; i < nb; i += 64 * NWV) { recD[i] = pv.phPrev[i]; recTheta[i] = pv.sum[i]; }
     for (int i = tid; i < HZ_EXTRA_THETA * nb; i += 64 * NWV) recTheta[nb + i] = thetaX[i];   // harm:
-    if (tid == 0) ((long long *)recD)[VP_HZ_COUNT] = R;
+    if (tid == 0) ((long long *)recD)[VP_HZ_COUNT] = C.R;
 }
 
 // the pending resets alone (a call with more than VP_PV_MAX_UPDATES of them enqueues this first, on the same stream)

@@ -311,7 +311,7 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_lock(VpStftArgs A, cons
 }
 
 // ---- streaming: vp_k_pv_stream_curve with the locked stage.  theta is the record's second array, handed from the call's first live frame
-// to its last whatever their wavefronts.
+// to its last whatever their wavefronts.  The call's bookkeeping is written out, as in vp_k_pv_stream_curve (the comment there says why).
 __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lock(VpPvArgs A, const double *ratioTab)
 {
     extern __shared__ double smem[];

@@ -280,14 +280,14 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_stft_pv_lockf(VpStftArgs A, con
 }
 
 // ---- streaming: vp_k_pv_stream_lock with the sub-bin stage.  theta is the record's second array, handed from the call's first live frame
-// to its last whatever their wavefronts.
+// to its last whatever their wavefronts.  The call's bookkeeping is the pv_call_* helpers of vp_stft.hip.
 __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lockf(VpPvArgs A, const double *ratioTab)
 {
     extern __shared__ double smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int s = blockIdx.x;
-    constexpr int N = 512, F = 1024, nb = N + 1, RM = VP_PV_RING - 1;
-    const int hop = A.hop, O = A.O, L = A.L, NB = A.N, S = A.S;
+    constexpr int N = 512, F = 1024, nb = N + 1;
+    const int hop = A.hop, O = A.O, NB = A.N, S = A.S;
     lds_d2 *xb = (lds_d2 *)smem + wv * 512;
     lds_f32 *slots = (lds_f32 *)smem;
     lds_f32 *ring = (lds_f32 *)smem + NWV * 2048;                              // [VP_PV_RING]
@@ -306,22 +306,12 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lockf(VpPvArgs A, con
     long long n = ((const long long *)recD)[VP_PV_COUNT];
     const bool rst = pv_scan_updates(A, s, recRatio);
     if (rst) n = 0;
+    const PvCall C = pv_call_geometry(n, A.nBlocks * NB, hop, A.L);
+    const int nf = C.nf;
 
-    const int M = A.nBlocks * NB;
-    const long long R = n + M;
-    const long long fa = n >= F ? (n - F) / hop + 1 : 0;
-    const long long fb = R >= F ? (R - F) / hop + 1 : 0;
-    const int nf = (int)(fb - fa);
-    const int H = (int)(n - fa * hop);
-    const int er = H - L;
-    const int fr0 = -(int)(fa & 3);
-
-    for (int i = tid; i < H; i += 64 * NWV) hist[i] = recHist[i];
+    pv_call_load_hist(C, hist, recHist, tid);
     for (int i = tid; i < nb; i += 64 * NWV) { pv.phPrev[i] = rst ? 0.0 : recD[i]; pv.sum[i] = rst ? 0.0 : recD[nb + i]; }
-    for (int q = tid; q < VP_PV_RING; q += 64 * NWV) {
-        const int i = (q - er) & RM;
-        ring[q] = (i < F && !rst) ? recCarry[i] : 0.f;
-    }
+    pv_call_load_ring(C, ring, recCarry, rst, tid);
 
     FftLane Lf;
     fft_lane_init(Lf, lane, A.tw1, A.tw2);
@@ -336,31 +326,25 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lockf(VpPvArgs A, con
 
     const float *xs = A.in + (size_t)s * NB;
     float *ys = A.out + (size_t)s * NB;
-    auto sample = [&](int rel) -> float {
-        if (rel < H) return hist[rel];
-        const unsigned c = (unsigned)(rel - H), b = c / (unsigned)NB;
-        return xs[(size_t)b * S * NB + (c - b * NB)];
-    };
-    auto emit = [&](int c, float v) {
-        const unsigned b = (unsigned)c / (unsigned)NB;
-        ys[(size_t)b * S * NB + ((unsigned)c - b * NB)] = v;
-    };
-    const int nRounds = nf > 0 ? (nf - fr0 + NWV - 1) / NWV : 0;
-    int cb = er;
+    const int nRounds = pv_call_rounds(C);
+    int cb = C.er;
     f2 xv[8];
     double rq = 1.0;
     auto request = [&](int k_) {
-        const int fr_ = fr0 + NWV * k_ + wv;
+        const int fr_ = C.fr0 + NWV * k_ + wv;
         if (k_ < nRounds && fr_ >= 0 && fr_ < nf) {
 #pragma unroll
-            for (int r = 0; r < 8; r++) { const int rel = fr_ * hop + 2 * (lane + 64 * r); xv[r] = f2{sample(rel), sample(rel + 1)}; }
-            const unsigned blk = (unsigned)(fr_ * hop + F - 1 - H) / (unsigned)NB;   // the block in which the frame's last sample arrives
+            for (int r = 0; r < 8; r++) {
+                const int rel = fr_ * hop + 2 * (lane + 64 * r);
+                xv[r] = f2{pv_call_sample(C, hist, xs, NB, S, rel), pv_call_sample(C, hist, xs, NB, S, rel + 1)};
+            }
+            const unsigned blk = (unsigned)(fr_ * hop + F - 1 - C.H) / (unsigned)NB; // the block in which the frame's last sample arrives
             rq = ratioTab[(size_t)blk * S + s];
         }
     };
     request(0);
     for (int k = 0; k < nRounds; k++) {
-        const int frW0 = fr0 + NWV * k;
+        const int frW0 = C.fr0 + NWV * k;
         const int fr = frW0 + wv;
         const bool live = fr >= 0 && fr < nf;                                  // (wavefront-uniform)
         const int wFirst = max(0, -frW0), wLast = min(NWV - 1, nf - 1 - frW0);
@@ -428,33 +412,16 @@ __global__ __launch_bounds__(64 * NWV) void vp_k_pv_stream_lockf(VpPvArgs A, con
             for (int r = 0; r < 8; r++) slot[lane + 64 * r] = f2{(float)(z.re[r] * wa[r].x), (float)(-(z.im[r] * wa[r].y))};
         }
         __syncthreads();
-        const int frA = frW0 + wFirst, frB = frW0 + wLast;
-        const int lo = frA * hop, hi = frB * hop + F;
-        for (int j = lo + ((tid - lo) & (64 * NWV - 1)); j < hi; j += 64 * NWV) {
-            float v = ring[j & RM];
-            for (int w = wFirst; w <= wLast; w++) {
-                const int o = j - (frW0 + w) * hop;
-                if (o >= 0 && o < F) v += slots[w * 2048 + o];
-            }
-            ring[j & RM] = v;
-        }
-        const int emitEnd = min((frB + 1) * hop, er + M);
-        for (int j = cb + ((tid - cb) & (64 * NWV - 1)); j < emitEnd; j += 64 * NWV) { emit(j - er, ring[j & RM]); ring[j & RM] = 0.f; }
-        cb = max(cb, emitEnd);
+        cb = pv_call_round_tail(C, ring, slots, ys, NB, S, hop, frW0, wFirst, wLast, cb, tid);
         __syncthreads();
     }
-    for (int j = cb + ((tid - cb) & (64 * NWV - 1)); j < er + M; j += 64 * NWV) { emit(j - er, ring[j & RM]); ring[j & RM] = 0.f; }
+    pv_call_emit(C, ring, ys, NB, S, cb, C.er + C.M, tid);                     // the flush
 
-    const int Hn = H + M - nf * hop;
-    for (int i = tid; i < Hn; i += 64 * NWV) recHist[i] = sample(nf * hop + i);
-    const int ern = er + M;
-    for (int q = tid; q < VP_PV_RING; q += 64 * NWV) {
-        const int i = (q - ern) & RM;
-        if (i < F) recCarry[i] = ring[q];
-    }
+    pv_call_store_hist(C, recHist, hist, xs, NB, S, hop, tid);
+    pv_call_store_carry(C, recCarry, ring, tid);
     __syncthreads();
     for (int i = tid; i < nb; i += 64 * NWV) { recD[i] = pv.phPrev[i]; recD[nb + i] = pv.sum[i]; }
-    if (tid == 0) { recD[VP_PV_RATIO] = recRatio; ((long long *)recD)[VP_PV_COUNT] = R; }
+    if (tid == 0) { recD[VP_PV_RATIO] = recRatio; ((long long *)recD)[VP_PV_COUNT] = C.R; }
 }
 
 hipError_t vp_stft_lockf_prepare_device()
