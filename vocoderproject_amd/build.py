@@ -10,6 +10,7 @@ kernel is built with the wave's denormal modes (float and double) set to "flush 
 input sample is widened to 0.0, a result in the f32-denormal range leaves as (signed) 0.0f, like on the CPU.
 """
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -20,10 +21,31 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libvp_amd.so")
 SOURCES = ["vp_kernels.hip", "vp_voc2.hip", "vp_stft.hip", "vp_channels.hip", "vp_track.hip", "vp_capi.hip"]
-PARTS = ["vp_fft.inc", "vp_filters.inc", "vp_vocoder_wg.inc", "vp_pitch.inc", "vp_pitch_ws.inc", "vp_pitch_ws_body.inc"]      # included by vp_kernels.hip
-DEPS = SOURCES + PARTS + ["vp_common.h", "vp_kernels.h", "vp_voc2.h", "vp_stft.h", "vp_fft32.inc", "vp_channels.h", "vp_stft_curve.inc", "vp_stft_stretch.inc", "vp_stft_lock.inc", "vp_stft_lockf.inc", "vp_stft_harm.inc", "vp_stft_stretch_lock.inc", "vp_stft_formant.inc", "vp_stft_cross.inc", "vp_track.h", "vp_track_body.inc", "vp_pv_transient.inc", "vp_stft_onset.inc", "vp_stft_stretch_reset.inc", "vp_onset_host.inc"]
 ARCH = "gfx950"
 NUM_TUS = 9          # groups of kernels in vp_kernels.hip (VP_TU)
+
+
+def deps_of(source):
+    """Every file `source` (a name under csrc/, or a path) reaches through quoted #include lines, itself included: sorted paths.
+    An include is looked up beside the including file, then in csrc/, then in include/ (the build's -I directories); conditionals are
+    not evaluated, so this is a superset of what any one compile reads.  The object cache and needs_build() both hash / stat this."""
+    seen, todo = set(), [os.path.join(CSRC, source)]
+    while todo:
+        path = os.path.normpath(todo.pop())
+        if path in seen:
+            continue
+        seen.add(path)
+        with open(path, encoding="utf-8", errors="replace") as f:
+            for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', f.read(), re.M):
+                for d in (os.path.dirname(path), CSRC, os.path.join(ROOT, "include")):
+                    if os.path.exists(os.path.join(d, inc)):
+                        todo.append(os.path.join(d, inc))
+                        break
+    return sorted(seen)
+
+
+DEP_PATHS = sorted({p for s in SOURCES for p in deps_of(s)})
+DEPS = [os.path.basename(p) for p in DEP_PATHS]      # (base names: tests and tools read this)
 
 
 def hipcc():
@@ -48,8 +70,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in DEPS] + [os.path.join(ROOT, "include", "vp_amd.h")]
-    return any(os.path.getmtime(p) > t for p in deps)
+    return any(os.path.getmtime(p) > t for p in DEP_PATHS)
 
 
 LIB_STAMPS = os.path.join(HERE, "libvp_amd_stamps.so")
@@ -137,15 +158,8 @@ def build(force=False, verbose=False, stamps=False, poison=False):
             src, obj, extra = job
             cmd = common + extra + ["-c", src, "-o", obj]
             hsh = hashlib.sha256((hipcc_version() + " ".join(cmd[:-1]).replace(tmp, "")).encode())
-            deps = {"vp_kernels.hip": ["vp_kernels.hip", "vp_common.h"] + PARTS,
-                    "vp_voc2.hip": ["vp_voc2.hip", "vp_voc2.h", "vp_kernels.hip", "vp_common.h"] + PARTS,
-                    "vp_stft.hip": ["vp_stft.hip", "vp_stft.h", "vp_fft.inc", "vp_fft32.inc", "vp_stft_curve.inc", "vp_stft_stretch.inc", "vp_stft_lock.inc", "vp_stft_lockf.inc", "vp_stft_harm.inc", "vp_stft_stretch_lock.inc", "vp_stft_formant.inc", "vp_stft_cross.inc", "vp_pv_transient.inc", "vp_stft_onset.inc", "vp_stft_stretch_reset.inc"],
-                    "vp_channels.hip": ["vp_channels.hip", "vp_channels.h"],
-                    "vp_track.hip": ["vp_track.hip", "vp_track.h", "vp_track_body.inc", "vp_common.h"]}.get(os.path.basename(src))
-            if deps is None:
-                deps = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.basename(src), "vp_onset_host.inc", os.path.join(ROOT, "include", "vp_amd.h")]
-            for dep in deps:
-                with open(dep if os.path.isabs(dep) else os.path.join(CSRC, dep), "rb") as f:
+            for dep in deps_of(src):
+                with open(dep, "rb") as f:
                     hsh.update(f.read())
             cache = os.path.join(HERE, ".build_cache")
             os.makedirs(cache, exist_ok=True)

@@ -1183,24 +1183,32 @@ hipError_t vp_pv_launch(const VpPvArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
-// ---- the phase-vocoder kernels along a per-frame / per-block ratio curve (vp_stft_pitch_shift_curve, vp_pv_process_blocks_curve_device) ----
+// ---- the parts: every derived kernel family is a file of its own, included here and nowhere else.  All of them use this file's helpers,
+// tables and carves; a part stands behind the parts named in its brackets, whose helpers it uses.  (tests/test_stft_parts_cpu.py holds
+// the same list, in the same order.)
+//   curve          vp_stft_pitch_shift_curve, vp_pv_process_blocks_curve_device: the kernels along a per-frame / per-block ratio curve
+//   stretch        vp_stft_time_stretch: frames analysed at caller-given positions
+//   lock           vp_stft_pitch_shift_locked, vp_pv_process_blocks_locked_device: the curve kernels with peak locking [curve: pv_curve_clamp]
+//   lockf          vp_stft_pitch_shift_locked_subbin, vp_pv_process_blocks_locked_subbin_device: the locked kernels with sub-bin region
+//                  offsets [curve: pv_curve_clamp; lock: its carve and sizes, pv_lock_mask, pv_lock_nearest, pv_lock_bin, pv_lock_turn]
+//   harm           vp_stft_harmonize, vp_hz_process_blocks_device: several locked voices and the dry signal from one analysis
+//                  [curve: pv_curve_clamp; lock: its carve and sizes, pv_lock_mask, pv_lock_nearest, pv_lock_bin]
+//   stretch_lock   vp_stft_time_stretch_locked: the locked kernel with frames at caller-given positions [curve: pv_curve_clamp; stretch:
+//                  pv_stretch_frame; lock: its carve and sizes, masks, pv_lock_turn, pv_lock_gather]
+//   cross          vp_stft_cross_synth, vp_xs_process_blocks_device: the voice's spectral envelope on the carrier [none]
+//   onset          vp_stft_onset_flux: the rectified flux and mass of the input's own frame grid, the transient-preserving stretch's first
+//                  half [none]; the host half (picking the onsets, planning the positions) is vp_onset_host.inc, included by vp_capi.hip
+//   stretch_reset  vp_stft_time_stretch_locked_reset: the locked stretch with a phase reset on flagged frames, its second half
+//                  [stretch_lock: pv_stretch_lock_plan; and what that part stands behind]
+//   formant        vp_stft_pitch_shift_formant, vp_pv_process_blocks_formant_device: the curve kernels with the cepstral formant
+//                  correction [curve: pv_curve_clamp]
 #include "vp_stft_curve.inc"
-
-// ---- the phase-vocoder kernels with frames analysed at caller-given positions: time stretch (vp_stft_time_stretch) ----
 #include "vp_stft_stretch.inc"
-
-// ---- the ratio-curve kernels with peak locking (vp_stft_pitch_shift_locked, vp_pv_process_blocks_locked_device) ----
 #include "vp_stft_lock.inc"
-
-// ---- the peak-locked kernel with frames analysed at caller-given positions: the locked time stretch (vp_stft_time_stretch_locked) ----
+#include "vp_stft_lockf.inc"
+#include "vp_stft_harm.inc"
 #include "vp_stft_stretch_lock.inc"
-
-// ---- cross-synthesis: the voice's spectral envelope on the carrier (vp_stft_cross_synth, vp_xs_process_blocks_device) ----
 #include "vp_stft_cross.inc"
-
-// ---- the transient-preserving locked time stretch: the onset flux of the input's grid (vp_stft_onset_flux) and the locked stretch with
-// a phase reset on flagged frames (vp_stft_time_stretch_locked_reset) ----
-#include "vp_pv_transient.inc"
-
-// ---- the ratio-curve kernels with the cepstral formant correction (vp_stft_pitch_shift_formant, vp_pv_process_blocks_formant_device) ----
+#include "vp_stft_onset.inc"
+#include "vp_stft_stretch_reset.inc"
 #include "vp_stft_formant.inc"

@@ -14,7 +14,7 @@
 // correction has no state across frames: the streaming record, the latency and the call bookkeeping are vp_k_pv_stream_curve's.
 //
 // They are WRITTEN-OUT COPIES of the two curve kernels, statement for statement, and kernels of their own (tests/test_kernel_resources.py
-// and tests/test_pv_curve_resources_cpu.py look the parents up by name).  What differs is marked "formant:" -- the envelope, the gain, and
+// and tests/test_stft_parts_cpu.py look the parents up by name).  What differs is marked "formant:" -- the envelope, the gain, and
 // where the twiddles live: the envelope's two transforms and the gain's reads are live on top of everything the parents keep, and with
 // the transform's and the split's twiddles resident (80 registers) the builds need 256 + 171 registers; read from the global tables where
 // they are used, as vp_k_stft_pv2k reads them, they need 256 + 111 and 256 + 104.  The values are the same, so are the bits.

@@ -1,5 +1,5 @@
-// vp_stft_harm.inc -- the phase-vocoder HARMONIZER: several peak-locked voices and the dry signal from one analysis (entered behind the
-// locked family, from the last line of vp_stft_lockf.inc: the list of parts vp_stft.hip itself includes is pinned by a test).
+// vp_stft_harm.inc -- the phase-vocoder HARMONIZER: several peak-locked voices and the dry signal from one analysis (included by
+// vp_stft.hip behind the locked family, vp_stft_lock.inc and vp_stft_lockf.inc: the locked stage's carve, masks, pv_lock_nearest and pv_lock_bin).
 //
 // A caller who wants a chord over the dry voice ran V locked calls and one round trip and mixed the results: V + 1 reads of the input,
 // forward transforms, peak searches, inverse transforms and overlap-adds.  The inverse transform and the overlap-add are linear, and the

@@ -513,7 +513,3 @@ hipError_t vp_pv_launch_lock(const VpPvArgs &a, const double *d_ratio, hipStream
     hipLaunchKernelGGL(vp_k_pv_stream_lock, dim3(a.S), dim3(64 * NWV), vp_pv_lock_lds_bytes(), st, a, d_ratio);
     return hipGetLastError();
 }
-
-// ---- the same kernels with sub-bin region offsets (vp_stft_pitch_shift_locked_subbin, vp_pv_process_blocks_locked_subbin_device): a
-// part of this family, so it enters vp_stft.hip here, behind everything above
-#include "vp_stft_lockf.inc"

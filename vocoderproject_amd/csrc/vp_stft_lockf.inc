@@ -1,5 +1,5 @@
-// vp_stft_lockf.inc -- the peak-locked phase-vocoder kernels with SUB-BIN region offsets (enters vp_stft.hip behind vp_stft_lock.inc, from
-// that file's last line: its carve, masks, pv_lock_nearest, pv_lock_bin and pv_lock_turn).
+// vp_stft_lockf.inc -- the peak-locked phase-vocoder kernels with SUB-BIN region offsets (included by vp_stft.hip behind
+// vp_stft_lock.inc: its carve, masks, pv_lock_nearest, pv_lock_bin and pv_lock_turn).
 //
 // The locked stage moves a peak's region by the integer floor(P r + 0.5) - P while its angle advances at the true frequency: the lobe
 // sits up to half a bin, plus the peak's own sub-bin position, from the frequency its phase turns at, and successive frames do not add
@@ -449,7 +449,3 @@ hipError_t vp_pv_launch_lockf(const VpPvArgs &a, const double *d_ratio, hipStrea
     hipLaunchKernelGGL(vp_k_pv_stream_lockf, dim3(a.S), dim3(64 * NWV), vp_pv_lockf_lds_bytes(), st, a, d_ratio);
     return hipGetLastError();
 }
-
-// ---- the harmonizer: several peak-locked voices and the dry signal from one analysis (vp_stft_harmonize, vp_hz_process_blocks_device): a
-// part of this family, entered here as this file is entered from vp_stft_lock.inc (the header of vp_stft_harm.inc says why)
-#include "vp_stft_harm.inc"

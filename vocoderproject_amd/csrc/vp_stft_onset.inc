@@ -1,5 +1,5 @@
 // vp_stft_onset.inc -- the ONSET FLUX of the input's own frame grid: the transient-preserving stretch's first half (included by vp_stft.hip
-// through vp_pv_transient.inc, behind the phase-vocoder kernels: the handle's window and twiddles, fft512_rx, rfft_split, stft_load_frame).
+// behind the phase-vocoder kernels and in front of vp_stft_stretch_reset.inc, the second half: the handle's window and twiddles, fft512_rx, rfft_split, stft_load_frame).
 //
 // The definition is tests/pv_transient_reference.py onset_flux: over the grid g hop of a row of nIn samples, nG = (nIn - F) / hop + 1,
 //   M_g = |rfft(x[g hop : g hop + F] w)|, bins 0 .. 512;   mass[g] = sum_k M_g[k];

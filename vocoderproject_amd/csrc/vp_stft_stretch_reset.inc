@@ -1,5 +1,5 @@
 // vp_stft_stretch_reset.inc -- the locked time stretch with a PHASE RESET on flagged frames: the transient-preserving stretch's second half
-// (included by vp_stft.hip through vp_pv_transient.inc, behind vp_stft_stretch_lock.inc: pv_stretch_lock_plan, and through it the locked stage's carve, masks, turns
+// (included by vp_stft.hip behind vp_stft_onset.inc, the first half, and vp_stft_stretch_lock.inc: pv_stretch_lock_plan, and through it the locked stage's carve, masks, turns
 // and gather).
 //
 // A frame that holds an attack is synthesised by vp_k_stft_pv_stretch_lock with angles carried over from before the attack, and its
