@@ -396,11 +396,11 @@ int vp_stft_pitch_shift_locked_subbin(vp_stft *p, const float *d_in, float *d_ou
  * voice with gain 0 still turns its angles, so it can be faded in later.  A frame without a peak contributes its dry term alone.
  * d_ratio: device double [n_streams][n_voices][vp_stft_num_frames(p)], clamped to [0.5, 2] as in the curve call;  d_gain: device double
  * [n_streams][n_voices] or NULL = every gain 1;  d_dry: device double [n_streams] or NULL = 0.  A gain or dry value that is NaN or
- * infinite counts as 0, a finite one is clamped to [-4, 4].  n_voices: 1 .. VP_HARM_MAX_VOICES.  A caller composes a tracker's ratio
- * with an interval on the table.  1024-point frames, every hop, always double, one workgroup per stream, no allocation; the runs setting
+ * infinite counts as 0, a finite one is clamped to [-4, 4].  n_voices: 1 .. VP_HARM_MAX_VOICES.  vp_stft_track_harmony below makes the
+ * table of voices at scale degrees of the tracked pitch; vp_stft_harmonize_key runs both.  1024-point frames, every hop, always double, one workgroup per stream, no allocation; the runs setting
  * and output aliasing as in the locked call.
- * Out of scope: sub-bin region offsets per voice; formant correction per voice; 2048-point frames; single precision; intervals chosen
- * from a key (diatonic harmony); gains per block or per frame.
+ * Out of scope: sub-bin region offsets per voice; formant correction per voice; 2048-point frames; single precision; gains per block
+ * or per frame.
  * VP_ERR_INVALID_ARG (null handle, input, output or ratio table; n_voices outside 1 .. 4) and VP_ERR_GEOMETRY (a 2048-point handle:
  * "harmonize: 2048-point frames are not built ...") are reported before the device is touched, in that order, and vp_stft_last_error
  * says which; VP_ERR_HIP as vp_stft_pitch_shift. */
@@ -561,7 +561,35 @@ int vp_stft_autotune(vp_stft *p, const float *d_in, float *d_out, double sample_
  * Arguments as vp_stft_autotune's plus d_formant and lifter; errors as the two calls', all before the device is touched. */
 int vp_stft_autotune_formant(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int *d_period, double *d_ratio,
                              const double *d_formant, int lifter, void *hip_stream);
-/* The message of the last tracker / autotune / formant call that failed on this handle ("" before any; the pointer is valid until the next call). */
+/* KEY-AWARE VOICES (kernel vp_k_yin_track_voices, csrc/vp_track.hip): vp_stft_track_pitch's decision for every frame, then n_voices
+ * ratios that put a voice at scale degrees of the note the tracker chose -- "a third and a fifth above, in the key" -- in the layout
+ * vp_stft_harmonize takes.  The definition is tests/pv_harmkey_reference.py, and period and ratio equal it bit for bit:
+ *   the harmony table of key k is H_k = Notes::buildFreqVect(k) through the filter 25 .. 3200 Hz instead of the tracker's 100 .. 800 Hz:
+ *   the tracker's table (its n entries and the popped slot) is the slice H_k[off_k .. off_k + n_k] of it, bit for bit, and twelve steps
+ *   above the slice exist in every key (checked where the handle builds the tables, so no index leaves a table upwards);
+ *   period > 0: pitch = fs / period; c = the index in the tracker's table of the entry getClosestFreq returns (0 .. n; n is the popped
+ *   slot); voice v has the degree d = clamp(d_degree[s][v], -12, 12), counted in steps of the key's table -- scale degrees in the twelve
+ *   scale keys, semitones in the chromatic key --; j = max(off + c + d, 0) and ratio[s][v][f] = H_k[j] / pitch, that one division.
+ *   Degree 0 has vp_stft_track_pitch's ratio, bit for bit.  The clamp at 0 binds for low notes and large negative degrees (104 Hz in
+ *   key 11 with d = -7);
+ *   period 0: ratio[s][v][f] = d_unvoiced[s][v]; NULL = 1.0 everywhere; a NaN or an infinity counts as 1.0.
+ * Frames are independent, as in vp_stft_track_pitch: no hold, no smoothing (vp_pv_tracker_process_blocks_voices_device has both).  The
+ * ratios are not clamped here; vp_stft_harmonize clamps to [0.5, 2] as for any table.
+ * d_in, d_key, sample_rate, d_period: as vp_stft_track_pitch's; d_degree: device int [n_streams][n_voices], required, read by the kernel
+ * only; d_unvoiced: device double [n_streams][n_voices] or NULL; d_ratio: device double [n_streams][n_voices][vp_stft_num_frames(p)] or
+ * NULL; d_period and d_ratio not both NULL.  n_voices: 1 .. VP_HARM_MAX_VOICES.  Both frame lengths, every hop.  No allocation, no
+ * synchronisation.  Errors: vp_stft_track_pitch's, then VP_ERR_INVALID_ARG for n_voices outside 1 .. 4 and for a null degree table
+ * ("track harmony: ..."), all before the device is touched; vp_stft_last_error says which.
+ * Out of scope: per-voice formant correction or sub-bin offsets; a table of chords per degree; smoothing in this batch form; note input. */
+int vp_stft_track_harmony(vp_stft *p, const float *d_in, double sample_rate, const int *d_key, int n_voices, const int *d_degree,
+                          const double *d_unvoiced, int *d_period, double *d_ratio, void *hip_stream);
+/* vp_stft_track_harmony followed by vp_stft_harmonize along its table, on the same stream: the output has the bits of those two calls.
+ * d_ratio is required (result and scratch), d_period optional; d_gain and d_dry as vp_stft_harmonize's.  1024-point frames:
+ * VP_ERR_GEOMETRY for a 2048-point handle, with the harmonizer's message.  Errors as the two calls' (the null output or table first), all
+ * before the device is touched. */
+int vp_stft_harmonize_key(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int n_voices, const int *d_degree,
+                          const double *d_unvoiced, const double *d_gain, const double *d_dry, int *d_period, double *d_ratio, void *hip_stream);
+/* The message of the last tracker / autotune / formant / harmony call that failed on this handle ("" before any; the pointer is valid until the next call). */
 const char *vp_stft_last_error(const vp_stft *p);
 int vp_stft_is_fused(const vp_stft *p);                      /* 1 (every handle runs the fused kernel; kept for older callers) */
 /* Diagnostic: cut every stream into this many runs of frames (one workgroup each) instead of choosing from the batch size
@@ -720,6 +748,29 @@ int vp_pv_autotune_blocks_device(vp_pv *p, vp_pv_tracker *t, const float *d_in, 
  * those two calls.  Arguments as vp_pv_autotune_blocks_device's plus d_formant and lifter. */
 int vp_pv_autotune_blocks_formant_device(vp_pv *p, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, int *d_period,
                                          double *d_ratio, const double *d_formant, int lifter, int n_blocks, void *hip_stream);
+/* The streaming tracker's KEY-AWARE VOICES (kernels vp_k_yin_track_voices_stream and vp_k_track_follow_voices): the raw decision of
+ * vp_pv_tracker_process_blocks_device, vp_stft_track_harmony's voice stage on it, then the follow stage per voice -- the table
+ * vp_hz_process_blocks_device takes.  The definition is tests/pv_harmkey_stream_reference.py; period and ratio equal it bit for bit.
+ *   per (stream, voice) tgt = 1.0, cur = 1.0 and one age = 0 per stream; per block:
+ *     period > 0: tgt[v] = raw[v], age = 0;  else: age = min(age + 1, INT_MAX), and tgt[v] = unvoiced[s][v] once age > H;
+ *     cur[v] = tgt[v] when g == 1.0, else cur[v] + g * (tgt[v] - cur[v]);  ratio[b][s][v] = cur[v].
+ * With every degree 0 and unvoiced 1.0 (or NULL) a voice's column is vp_pv_tracker_process_blocks_device's table, bit for bit.  Ring and
+ * counter are the handle's: a block goes through exactly ONE of the two process calls.  The voices' follow state is separate from the
+ * mono call's (each call advances its own and leaves the other's alone); vp_pv_tracker_reset clears both, vp_pv_tracker_set_follow
+ * governs both.  It is allocated at create with everything else.  n_voices (1 .. VP_HARM_MAX_VOICES) may differ from call to call; the
+ * voices a call does not name keep their state.  How blocks are grouped into calls does not change a bit.
+ * d_degree: device int [S][n_voices], required; d_unvoiced: device double [S][n_voices] or NULL = 1.0 (a NaN or an infinity counts as
+ * 1.0); d_period: device int [n_blocks][S] or NULL; d_ratio: device double [n_blocks][S][n_voices] or NULL; not both NULL.  Everything
+ * else, and the errors (all VP_ERR_INVALID_ARG, before the device is touched), as vp_pv_tracker_process_blocks_device's. */
+int vp_pv_tracker_process_blocks_voices_device(vp_pv_tracker *t, const float *d_in, const int *d_key, int n_voices, const int *d_degree,
+                                               const double *d_unvoiced, int *d_period, double *d_ratio, int n_blocks, void *hip_stream);
+/* vp_pv_tracker_process_blocks_voices_device with the harmonizer handle's voice count, followed by vp_hz_process_blocks_device along its
+ * table, on the same stream: the output has the bits of those two calls.  d_ratio is required (result and scratch), d_period optional.
+ * VP_ERR_GEOMETRY if S, N or the device differ between the two handles.  vp_hz_reset does not reach the tracker and vp_pv_tracker_reset
+ * does not reach the harmonizer: a caller that restarts a stream resets both. */
+int vp_hz_autoharm_blocks_device(vp_hz *h, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, const int *d_degree,
+                                 const double *d_unvoiced, const double *d_gain, const double *d_dry, int *d_period, double *d_ratio,
+                                 int n_blocks, void *hip_stream);
 
 const char *vp_error_string(int code);
 const char *vp_last_error(const vp_handle *h);

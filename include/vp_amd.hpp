@@ -373,6 +373,15 @@ public:
     {
         detail::check(vp_pv_tracker_process_blocks_device(t_, dIn, dKey, dPeriod, dRatio, nBlocks, hipStream), "processBlocksDevice");
     }
+    // the key-aware voices (vp_pv_tracker_process_blocks_voices_device): dDegree device int [S][nVoices], steps of the key's table from the
+    // note the tracker chose; dUnvoiced device double [S][nVoices] or null = 1; ratio double [nBlocks][S][nVoices], the table
+    // StreamingHarmonizer::processBlocksDevice takes.  A block goes through this call or processBlocksDevice, not both
+    void processBlocksVoices(const float *dIn, const int *dKey, int nVoices, const int *dDegree, const double *dUnvoiced, int *dPeriod,
+                             double *dRatio, int nBlocks, void *hipStream = nullptr)
+    {
+        detail::check(vp_pv_tracker_process_blocks_voices_device(t_, dIn, dKey, nVoices, dDegree, dUnvoiced, dPeriod, dRatio, nBlocks, hipStream),
+                      "processBlocksVoices");
+    }
     vp_pv_tracker *handle() const { return t_; }
 
 private:
@@ -517,6 +526,14 @@ public:
                              void *hipStream = nullptr)
     {
         detail::check(vp_hz_process_blocks_device(h_, dIn, dOut, dRatio, dGain, dDry, nBlocks, hipStream), "processBlocksDevice");
+    }
+    // tracker.processBlocksVoices with this handle's voice count, then processBlocksDevice along its table, on the same stream
+    // (vp_hz_autoharm_blocks_device): dRatio [nBlocks][S][nVoices] is result and scratch, dPeriod may be null.  Resets stay separate
+    void autoharmBlocks(StreamingPitchTracker &tracker, const float *dIn, float *dOut, const int *dKey, const int *dDegree, const double *dUnvoiced,
+                        const double *dGain, const double *dDry, int *dPeriod, double *dRatio, int nBlocks, void *hipStream = nullptr)
+    {
+        detail::check(vp_hz_autoharm_blocks_device(h_, tracker.handle(), dIn, dOut, dKey, dDegree, dUnvoiced, dGain, dDry, dPeriod, dRatio, nBlocks,
+                                                   hipStream), "autoharmBlocks");
     }
     long debugAllocCount() const { return vp_hz_debug_alloc_count(h_); }
     vp_hz *handle() const { return h_; }

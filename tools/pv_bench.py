@@ -12,6 +12,7 @@
     [VP_AMD_LIB=...] python tools/pv_bench.py --locked-subbin [--reps 7] [--out profiles/pv_lockf_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --cross [--reps 7] [--out profiles/pv_cross_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --harm [--reps 7] [--out profiles/pv_harm_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --harmkey [--reps 7] [--out profiles/pv_harmkey_bench.txt]
 
 --curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
 "steps" curve, fixed, ...): 256 streams x 65 536 samples at 1024 points / hop 256 and 2048 points / hop 512 (vp_stft_pitch_shift against
@@ -70,6 +71,14 @@ The legs: the harmonizer; three vp_stft_pitch_shift_locked calls, one double-pre
 expression on the device (a matrix-vector product over the stacked parts: one read of each, one write); one locked call alone.  Rates are input frames per second (a frame counts once however many voices it gets).
 Streaming, 16 blocks of 1024 per call: the streaming harmonizer against three locked streaming handles plus the mix (the composition's dry
 part is the undelayed input there: a caller's delay line is not timed).  The kernels' resource listings follow.
+
+--harmkey: the key-aware voices (vp_stft_track_harmony, vp_stft_harmonize_key, vp_hz_autoharm_blocks_device) beside their parts and
+beside the composition a caller had before them, alternating in one process: 256 streams x 65 536 samples at 44.1 kHz, 1024 points /
+hop 256, three voices at degrees (2, 4, -3) of keys 0 .. 12 in turn, on voiced signals and on noise.  One-shot legs: vp_stft_track_pitch;
+vp_stft_track_harmony at V = 3 (the ratio over the tracker is the voice stage's cost); vp_stft_harmonize along that table;
+vp_stft_harmonize_key (against the sum of its two calls); three autotune(locked=True) calls and the mix (the composition: parallel
+harmony from three trackers).  Streaming, 16 blocks of 1024 per call: vp_hz_autoharm_blocks_device against the tracker's voices call
+plus the harmonizer call on handles of their own.  Every table a leg takes is on the device before the clock starts.
 """
 import argparse
 import os
@@ -501,6 +510,71 @@ def harm_legs(reps, emit):
         p.close()
 
 
+def harmkey_legs(reps, emit):
+    import numpy as np
+    import torch
+    from vocoderproject_amd import HarmonizerStream, StftRoundTrip, StreamingPitchTracker
+    S, T, F, hop, fs, V = 256, 65536, 1024, 256, 44100.0, 3
+    gains, dry = (1.0, 0.7, 0.7), 1.0
+    st = StftRoundTrip(S, T, F, hop)
+    nF = st.n_frames
+    keys = torch.from_numpy((np.arange(S) % 13).astype(np.int32)).cuda()
+    deg = torch.from_numpy(np.tile(np.array([2, 4, -3], np.int32), (S, 1))).cuda()
+    unv = torch.from_numpy(np.tile(2.0 ** (np.array([4.0, 7.0, -5.0]) / 12.0), (S, 1))).cuda()
+    d_gain = torch.from_numpy(np.tile(np.array(gains), (S, 1))).cuda()
+    d_dry = torch.from_numpy(np.full(S, dry)).cuda()
+    w = torch.tensor([list(gains) + [dry]], dtype=torch.float32, device="cuda")
+    inputs = (("voiced signals", torch.from_numpy(voiced_rows(S, T, fs)).cuda()), ("noise", torch.randn(S, T, device="cuda", dtype=torch.float32) * 0.1))
+    trk, harm, table, both, old = "track_pitch", "track_harmony, V = 3", "harmonize on its table", "harmonize_key", "3 autotune(locked) + mix"
+    for what, x in inputs:
+        y = torch.empty_like(x)
+        parts = torch.empty((V + 1, S, T), dtype=torch.float32, device="cuda")
+        parts[V].copy_(x)                                      # (the composition's dry part: the input as it is)
+        period, ratio = st.track_harmony(x, fs, deg, keys=keys, unvoiced=unv)
+        torch.cuda.synchronize()
+        voiced = float((period > 0).float().mean())
+
+        def composed(x=x, y=y, parts=parts):
+            for v in range(V):
+                st.autotune(x, parts[v], fs, keys=keys, locked=True)
+            torch.mm(w, parts.view(V + 1, -1), out=y.view(1, -1))
+        legs = {trk: lambda x=x: st.track_pitch(x, fs, keys=keys),
+                harm: lambda x=x: st.track_harmony(x, fs, deg, keys=keys, unvoiced=unv),
+                table: lambda x=x, y=y, ratio=ratio: st.harmonize(x, y, d_ratio=ratio, gains=d_gain, dry=d_dry),
+                both: lambda x=x, y=y: st.harmonize(x, y, degrees=deg, sample_rate=fs, keys=keys, unvoiced=unv, gains=d_gain, dry=d_dry),
+                old: composed}
+        times = alternate(legs, reps, 20)
+        report(f"one-shot, {S} streams x {T} samples of {what} at {fs:g} Hz, F = {F}, hop = {hop}, {100.0 * voiced:.0f} % of the frames voiced",
+               times, S * nF, trk, emit)
+        m = {k: sum(v) / len(v) for k, v in times.items()}
+        emit(f"  track_harmony / track_pitch, frames per second: {m[trk] / m[harm]:.3f}")
+        emit(f"  per call: track_harmony {m[harm] * 1e3:.3f} ms + harmonize {m[table] * 1e3:.3f} ms = {(m[harm] + m[table]) * 1e3:.3f} ms; "
+             f"harmonize_key {m[both] * 1e3:.3f} ms = {m[both] / (m[harm] + m[table]):.3f} x the sum; "
+             f"3 autotune(locked) + mix {m[old] * 1e3:.3f} ms = {m[old] / m[both]:.2f} x harmonize_key")
+    st.close()
+    N, K = 1024, 16
+    for what, x in inputs:
+        blocks = x[:, :(K + 2) * N].reshape(S, K + 2, N).transpose(0, 1).contiguous()
+        hz_a, hz_b, trk_a, trk_b = HarmonizerStream(S, N, V, hop=hop), HarmonizerStream(S, N, V, hop=hop), StreamingPitchTracker(S, N, fs, F), StreamingPitchTracker(S, N, fs, F)
+        for t in (trk_a, trk_b):                               # two blocks of history first: every timed decision has a full window
+            t.process_voices_device(blocks[:2], deg, n_blocks=2, keys=keys, unvoiced=unv)
+        slab = blocks[2:].contiguous()
+        yb = torch.empty_like(slab)
+        _, tab = trk_a.process_voices_device(slab, deg, n_blocks=K, keys=keys, unvoiced=unv)
+        legs = {"tracker, voices": lambda slab=slab: trk_a.process_voices_device(slab, deg, n_blocks=K, keys=keys, unvoiced=unv),
+                "harmonizer on its table": lambda slab=slab, yb=yb, tab=tab: hz_a.process_device(slab, yb, n_blocks=K, d_ratio=tab, gains=d_gain, dry=d_dry),
+                "autoharm": lambda slab=slab, yb=yb: hz_b.autoharm_device(trk_b, slab, yb, deg, n_blocks=K, keys=keys, unvoiced=unv, gains=d_gain, dry=d_dry)}
+        times = alternate(legs, reps, 150)
+        m = {k: sum(v) / len(v) for k, v in times.items()}
+        parts_t = m["tracker, voices"] + m["harmonizer on its table"]
+        emit(f"streaming, {S} streams, {K} blocks of {N} per call of {what}, hop = {hop}")
+        emit(f"  per call: tracker {m['tracker, voices'] * 1e3:.3f} ms + harmonizer {m['harmonizer on its table'] * 1e3:.3f} ms = {parts_t * 1e3:.3f} ms; "
+             f"autoharm {m['autoharm'] * 1e3:.3f} ms = {m['autoharm'] / parts_t:.3f} x the sum "
+             f"({S * K * N // hop / m['autoharm'] / 1e6:.1f} M frames/s)")
+        for h in (hz_a, hz_b, trk_a, trk_b):
+            h.close()
+
+
 def resource_listing(emit, kernels=("vp_k_stft_fused<true, false>", "vp_k_stft_pv_stretch", "vp_k_stft_pv2k", "vp_k_stft_pv2k_stretch")):
     try:
         import kernel_resources
@@ -526,10 +600,11 @@ def main():
     ap.add_argument("--transient", action="store_true", help="the onset-flux and reset-kernel legs instead of the fixed intervals")
     ap.add_argument("--cross", action="store_true", help="the cross-synthesis legs instead of the fixed intervals")
     ap.add_argument("--harm", action="store_true", help="the harmonizer legs instead of the fixed intervals")
+    ap.add_argument("--harmkey", action="store_true", help="the key-aware voices' legs instead of the fixed intervals")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="--curve / --stretch / --track: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.locked_subbin and not a.stretch_locked and not a.transient and not a.cross and not a.harm:
+    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.locked_subbin and not a.stretch_locked and not a.transient and not a.cross and not a.harm and not a.harmkey:
         return fixed_intervals()
     lines = []
 
@@ -565,6 +640,10 @@ def main():
     if a.harm:
         harm_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_stft_pv_lock", "vp_k_stft_harm", "vp_k_pv_stream_lock", "vp_k_hz_stream"))
+    if a.harmkey:
+        harmkey_legs(max(5, a.reps), emit)
+        resource_listing(emit, ("vp_k_yin_track", "vp_k_yin_track_voices", "vp_k_yin_track_stream", "vp_k_yin_track_voices_stream", "vp_k_track_follow",
+                                "vp_k_track_follow_voices", "vp_k_stft_harm", "vp_k_hz_stream"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

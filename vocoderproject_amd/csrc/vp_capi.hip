@@ -1854,6 +1854,8 @@ struct vp_stft {
     int f32 = 0;                      // vp_stft_set_precision
     double *notes = nullptr;          // [13][VP_NOTES_STRIDE] the Notes tables of the pitch tracker (vp_stft_track_pitch), fMin 100 / fMax 800
     int *notesN = nullptr;            // [13]
+    double *harm = nullptr;           // [13][VP_NOTES_STRIDE] the harmony tables of vp_stft_track_harmony (fMin 25 / fMax 3200), then harmOff [13]
+    int *harmOff = nullptr;           // (into harm's allocation)
     std::string lastError;            // vp_stft_last_error
 };
 
@@ -1863,7 +1865,7 @@ static float stft_host_tables(int frame_len, int hop, std::vector<double> &w, st
 static void stft_free(vp_stft *p)
 {
     (void)hipFree(p->win); (void)hipFree(p->tw1); (void)hipFree(p->tw2); (void)hipFree(p->tws); (void)hipFree(p->twTop);
-    (void)hipFree(p->notes); (void)hipFree(p->notesN);
+    (void)hipFree(p->notes); (void)hipFree(p->notesN); (void)hipFree(p->harm);
 }
 
 // ---- what the three creators of this file share ----
@@ -1892,6 +1894,30 @@ static bool put_notes(double **notes, int **notesN, long *nAllocs)
     return put(notes, tab, nAllocs) && put((void **)notesN, n, sizeof n, nAllocs);
 }
 
+// the harmony tables of the key-aware voices, one per key, and behind them the index of the tracker table's entry 0 in each: one allocation.
+// The tracker's table (its entries and the popped slot) must be a slice of the harmony table, bit for bit, with VP_TRACK_MAX_DEGREE steps
+// of headroom above it: checked here, so that the kernels need no upper clamp
+static bool put_harm(double **harm, int **harmOff, long *nAllocs)
+{
+    static_assert(VP_TRACK_MAX_VOICES == VP_HARM_MAX_VOICES, "the tracker's voices are the harmonizer's");
+    const size_t tabBytes = 13 * VP_NOTES_STRIDE * sizeof(double);
+    std::vector<unsigned char> blob(tabBytes + 13 * sizeof(int), 0);
+    double *tab = (double *)blob.data();
+    int *off = (int *)(blob.data() + tabBytes);
+    for (int k = 0; k < 13; k++) {
+        double trk[VP_NOTES_STRIDE] = {0.0}, *h = tab + (size_t)k * VP_NOTES_STRIDE;
+        const int n = build_notes(k, VP_TRACK_FMIN, VP_TRACK_FMAX, trk), hN = build_notes(k, VP_TRACK_HARM_FMIN, VP_TRACK_HARM_FMAX, h);
+        if (hN + 1 > VP_NOTES_STRIDE) return false;
+        int o = 0;
+        while (o <= hN && h[o] != trk[0]) o++;
+        if (o + n + VP_TRACK_MAX_DEGREE > hN - 1 || memcmp(h + o, trk, (n + 1) * sizeof(double)) != 0) return false;
+        off[k] = o;
+    }
+    if (!put((void **)harm, blob.data(), blob.size(), nAllocs)) return false;
+    *harmOff = (int *)((unsigned char *)*harm + tabBytes);
+    return true;
+}
+
 extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int frame_len, int hop, vp_stft **out)
 {
     if (!out || n_streams <= 0 || frame_len < 8 || hop <= 0 || n_samples < frame_len) return VP_ERR_INVALID_ARG;
@@ -1914,7 +1940,8 @@ extern "C" int vp_stft_create(int device, int n_streams, int n_samples, int fram
     std::vector<double> w, t1, t2, ts, tt;
     p->scale = stft_host_tables(frame_len, hop, w, t1, t2, ts, tt);
     if (!(put(&p->win, w, nullptr) && put(&p->tw1, t1, nullptr) && put(&p->tw2, t2, nullptr) && put(&p->tws, ts, nullptr)
-          && (frame_len != 2048 || put(&p->twTop, tt, nullptr)) && put_notes(&p->notes, &p->notesN, nullptr))) {
+          && (frame_len != 2048 || put(&p->twTop, tt, nullptr)) && put_notes(&p->notes, &p->notesN, nullptr)
+          && put_harm(&p->harm, &p->harmOff, nullptr))) {
         stft_free(p); delete p; return VP_ERR_OOM;
     }
     *out = p;
@@ -2278,6 +2305,58 @@ extern "C" int vp_stft_track_pitch(vp_stft *p, const float *d_in, double sample_
     return track_launch(p, d_in, sample_rate, d_key, d_period, d_ratio, (hipStream_t)hip_stream);
 }
 
+// ---- key-aware voices (vp_k_yin_track_voices): the tracker's decision, then n_voices ratios at scale degrees of the note it chose ------
+// every argument of a harmony call beyond the tracker's, checked before the device is touched
+static int harmony_check(vp_stft *p, int n_voices, const int *d_degree)
+{
+    if (n_voices < 1 || n_voices > VP_HARM_MAX_VOICES) { p->lastError = "track harmony: the number of voices is outside 1 .. 4"; return VP_ERR_INVALID_ARG; }
+    if (!d_degree) { p->lastError = "track harmony: null degree table"; return VP_ERR_INVALID_ARG; }
+    return VP_OK;
+}
+
+static int harmony_launch(vp_stft *p, const float *d_in, double fs, const int *d_key, int n_voices, const int *d_degree, const double *d_unvoiced,
+                          int *d_period, double *d_ratio, hipStream_t st)
+{
+    VpTrackArgs a;
+    memset(&a, 0, sizeof a);
+    a.in = d_in; a.key = d_key; a.period = d_period; a.ratio = d_ratio; a.notes = p->notes; a.notesN = p->notesN;
+    a.fs = fs; a.S = p->S; a.T = p->T; a.F = p->F; a.hop = p->hop; a.nFrames = p->nFrames;
+    a.tauMax = vp_track_tau_max(fs);
+    a.tau0 = (int)std::floor(fs / VP_TRACK_FMAX);                                               // PitchProcess.cpp:429
+    const VpTrackVoices v = {p->harm, p->harmOff, d_degree, d_unvoiced, n_voices};
+    if (vp_track_voices_launch(a, v, st) != hipSuccess) { p->lastError = "track harmony: kernel launch failed"; return VP_ERR_HIP; }
+    return VP_OK;
+}
+
+extern "C" int vp_stft_track_harmony(vp_stft *p, const float *d_in, double sample_rate, const int *d_key, int n_voices, const int *d_degree,
+                                     const double *d_unvoiced, int *d_period, double *d_ratio, void *hip_stream)
+{
+    int rc = track_check(p, d_in, sample_rate, d_period, d_ratio);
+    if (!rc) rc = harmony_check(p, n_voices, d_degree);
+    if (rc) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return harmony_launch(p, d_in, sample_rate, d_key, n_voices, d_degree, d_unvoiced, d_period, d_ratio, (hipStream_t)hip_stream);
+}
+
+// vp_stft_track_harmony, then vp_stft_harmonize along its table, on the same stream.  The output and the table are looked at first, when
+// there is a handle to keep the text; then the tracker's arguments, the voices', then the harmonizer's (the frame length, the LDS ceiling)
+extern "C" int vp_stft_harmonize_key(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int n_voices, const int *d_degree,
+                                     const double *d_unvoiced, const double *d_gain, const double *d_dry, int *d_period, double *d_ratio, void *hip_stream)
+{
+    if (p && (!d_out || !d_ratio)) { p->lastError = "harmonize key: null output or ratio table (the table is result and scratch)"; return VP_ERR_INVALID_ARG; }
+    int rc = track_check(p, d_in, sample_rate, d_period, d_ratio);
+    if (!rc) rc = harmony_check(p, n_voices, d_degree);
+    const PvMode m = PvMode::lock(d_ratio);
+    if (!rc) rc = stft_check(p, "harmonize", true, nullptr, &m);
+    if (rc) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    rc = harmony_launch(p, d_in, sample_rate, d_key, n_voices, d_degree, d_unvoiced, d_period, d_ratio, (hipStream_t)hip_stream);
+    if (rc) return rc;
+    int nRuns;
+    const VpStftArgs a = stft_args(p, d_in, d_out, nullptr, &m, &nRuns);
+    return vp_stft_launch_harm(a, d_ratio, d_gain, d_dry, n_voices, p->S, (hipStream_t)hip_stream) == hipSuccess ? VP_OK : VP_ERR_HIP;
+}
+
 // the tracker, then the call of mode m (whose table is the tracker's d_ratio) along its table, on the same stream.  The output and the
 // table are looked at first, when there is a handle to keep the text; then the tracker's arguments, then the mode's
 static int stft_autotune(vp_stft *p, const float *d_in, float *d_out, double fs, const int *d_key, int *d_period, double *d_ratio, const PvMode &m,
@@ -2639,8 +2718,11 @@ extern "C" int vp_hz_process_blocks_device(vp_hz *h, const float *d_in, float *d
 struct vp_pv_tracker {
     int device = 0, S = 0, N = 0, F = 0, W = 0, tauMax = 0, tau0 = 0;
     double fs = 0;
-    unsigned char *state = nullptr;             // ring [S][W] float, then count [S] int64, tgt [S], cur [S] double, age [S] int
+    unsigned char *state = nullptr;             // ring [S][W] float, then count [S] int64, tgt [S], cur [S] double, the voices' tgtV, curV
+                                                // [S][VP_TRACK_MAX_VOICES] double, age [S], ageV [S] int
     float *ring = nullptr; long long *count = nullptr; double *tgt = nullptr, *cur = nullptr; int *age = nullptr;   // (into state)
+    double *tgtV = nullptr, *curV = nullptr; int *ageV = nullptr;                                                   // (into state)
+    double *harm = nullptr; int *harmOff = nullptr;   // the harmony tables of the voices call (put_harm)
     int *scrPeriod = nullptr; double *scrRatio = nullptr;   // [TRKS_SCRATCH_BLOCKS][S]: the raw table the caller did not ask for
     double *notes = nullptr; int *notesN = nullptr;
     long nAllocs = 0;
@@ -2652,6 +2734,7 @@ struct vp_pv_tracker {
 static void trks_free(vp_pv_tracker *t)
 {
     (void)hipFree(t->state); (void)hipFree(t->scrPeriod); (void)hipFree(t->scrRatio); (void)hipFree(t->notes); (void)hipFree(t->notesN);
+    (void)hipFree(t->harm);
 }
 
 extern "C" int vp_pv_tracker_create(int device, int n_streams, int block_size, int frame_len, double sample_rate, vp_pv_tracker **out)
@@ -2669,15 +2752,19 @@ extern "C" int vp_pv_tracker_create(int device, int n_streams, int block_size, i
     t->resetPend.assign(n_streams, 0);
     const size_t S = (size_t)n_streams;
     const size_t ringBytes = (S * t->W * sizeof(float) + 7) & ~(size_t)7;
-    std::vector<unsigned char> st(ringBytes + S * (8 + 8 + 8 + 4), 0);                          // count 0, age 0, ring zeros (never read before written)
-    for (size_t s = 0; s < 2 * S; s++) { const double one = 1.0; memcpy(&st[ringBytes + S * 8 + s * 8], &one, 8); }   // tgt = cur = 1.0
+    const size_t nFollow = 2 * S + 2 * S * VP_TRACK_MAX_VOICES;                                 // tgt, cur, tgtV, curV
+    std::vector<unsigned char> st(ringBytes + S * 8 + nFollow * 8 + 2 * S * 4, 0);              // count 0, ages 0, ring zeros (never read before written)
+    for (size_t s = 0; s < nFollow; s++) { const double one = 1.0; memcpy(&st[ringBytes + S * 8 + s * 8], &one, 8); }   // every tgt = cur = 1.0
     long *n = &t->nAllocs;
     const bool ok = put((void **)&t->state, st.data(), st.size(), n) && put((void **)&t->scrPeriod, nullptr, TRKS_SCRATCH_BLOCKS * S * sizeof(int), n)
-        && put((void **)&t->scrRatio, nullptr, TRKS_SCRATCH_BLOCKS * S * sizeof(double), n) && put_notes(&t->notes, &t->notesN, n);
+        && put((void **)&t->scrRatio, nullptr, TRKS_SCRATCH_BLOCKS * S * sizeof(double), n) && put_notes(&t->notes, &t->notesN, n)
+        && put_harm(&t->harm, &t->harmOff, n);
     if (!ok) { trks_free(t); delete t; (void)hipGetLastError(); return VP_ERR_OOM; }
     t->ring = (float *)t->state;
     t->count = (long long *)(t->state + ringBytes);
-    t->tgt = (double *)(t->count + S); t->cur = t->tgt + S; t->age = (int *)(t->cur + S);
+    t->tgt = (double *)(t->count + S); t->cur = t->tgt + S;
+    t->tgtV = t->cur + S; t->curV = t->tgtV + S * VP_TRACK_MAX_VOICES;
+    t->age = (int *)(t->curV + S * VP_TRACK_MAX_VOICES); t->ageV = t->age + S;
     *out = t;
     return VP_OK;
 }
@@ -2720,8 +2807,17 @@ static int trks_check(const vp_pv_tracker *t, const float *d_in, const int *d_pe
 
 // the pending resets travel in the arguments of update launches in front of the call: ordered on the caller's stream, no host memory
 // the device reads later, no allocation.  An output the caller left out is replaced by the handle's scratch, TRKS_SCRATCH_BLOCKS blocks
-// per launch pair (how blocks are grouped into launches does not change a bit).
-static int trks_run(vp_pv_tracker *t, const float *d_in, const int *d_key, int *d_period, double *d_ratio, int n_blocks, hipStream_t st)
+// per launch pair (how blocks are grouped into launches does not change a bit).  A reset clears the mono follow state and the voices'.
+// vc: the voices call (ratio tables [n_blocks][S][V], the voices' kernels and follow state); nullptr: the mono call
+static bool trks_reset_launch(const vp_pv_tracker *t, const VpTrackUpdArgs &u, hipStream_t st)
+{
+    VpTrackUpdArgs v = u;
+    v.count = nullptr; v.tgt = t->tgtV; v.cur = t->curV; v.age = t->ageV;
+    return vp_track_reset_launch(u, st) == hipSuccess && vp_track_reset_voices_launch(v, st) == hipSuccess;
+}
+
+static int trks_run(vp_pv_tracker *t, const float *d_in, const int *d_key, int *d_period, double *d_ratio, int n_blocks, hipStream_t st,
+                    const VpTrackVoices *vc = nullptr)
 {
     VpTrackUpdArgs u;
     memset(&u, 0, sizeof u);
@@ -2732,11 +2828,11 @@ static int trks_run(vp_pv_tracker *t, const float *d_in, const int *d_key, int *
             if (!t->resetPend[s]) continue;
             u.stream[u.n++] = s;
             if (u.n == VP_TRKS_MAX_UPDATES) {
-                if (vp_track_reset_launch(u, st) != hipSuccess) return VP_ERR_HIP;
+                if (!trks_reset_launch(t, u, st)) return VP_ERR_HIP;
                 u.n = 0;
             }
         }
-    if (u.n && vp_track_reset_launch(u, st) != hipSuccess) return VP_ERR_HIP;
+    if (u.n && !trks_reset_launch(t, u, st)) return VP_ERR_HIP;
     t->allReset = false;
     std::fill(t->resetPend.begin(), t->resetPend.end(), 0);
 
@@ -2748,16 +2844,24 @@ static int trks_run(vp_pv_tracker *t, const float *d_in, const int *d_key, int *
     memset(&f, 0, sizeof f);
     f.ring = t->ring; f.count = t->count; f.tgt = t->tgt; f.cur = t->cur; f.age = t->age;
     f.glide = t->glide; f.hold = t->hold; f.S = t->S; f.N = t->N; f.W = t->W;
-    const int chunk = (d_period && d_ratio) ? n_blocks : std::min(n_blocks, TRKS_SCRATCH_BLOCKS);
+    VpTrackFollowVoicesArgs fv;
+    memset(&fv, 0, sizeof fv);
+    const int V = vc ? vc->V : 1;
+    if (vc) {
+        fv.unvoiced = vc->unvoiced; fv.ring = t->ring; fv.count = t->count; fv.tgt = t->tgtV; fv.cur = t->curV; fv.age = t->ageV;
+        fv.glide = t->glide; fv.hold = t->hold; fv.S = t->S; fv.N = t->N; fv.W = t->W; fv.V = V;
+    }
+    const int chunk = (d_period && d_ratio) ? n_blocks : std::min(n_blocks, TRKS_SCRATCH_BLOCKS / V);   // (the scratch holds [S] doubles per block)
     for (int b = 0; b < n_blocks; b += chunk) {
         const int nb = std::min(chunk, n_blocks - b);
         const size_t row = (size_t)b * t->S;
-        a.in = f.in = d_in + row * t->N;
+        a.in = f.in = fv.in = d_in + row * t->N;
         a.period = d_period ? d_period + row : t->scrPeriod;
-        a.ratio = f.ratio = d_ratio ? d_ratio + row : t->scrRatio;
-        f.period = a.period;
-        a.nBlocks = f.nBlocks = nb;
-        if (vp_track_stream_launch(a, st) != hipSuccess || vp_track_follow_launch(f, st) != hipSuccess) return VP_ERR_HIP;
+        a.ratio = f.ratio = fv.ratio = d_ratio ? d_ratio + row * V : t->scrRatio;
+        f.period = fv.period = a.period;
+        a.nBlocks = f.nBlocks = fv.nBlocks = nb;
+        if (vc ? vp_track_voices_stream_launch(a, *vc, st) != hipSuccess || vp_track_follow_voices_launch(fv, st) != hipSuccess
+               : vp_track_stream_launch(a, st) != hipSuccess || vp_track_follow_launch(f, st) != hipSuccess) return VP_ERR_HIP;
     }
     return VP_OK;
 }
@@ -2769,6 +2873,41 @@ extern "C" int vp_pv_tracker_process_blocks_device(vp_pv_tracker *t, const float
     if (rc) return rc;
     if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     return trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
+}
+
+// the voices call: vp_pv_tracker_process_blocks_device's arguments and checks, then the voice count and the degree table
+static int trks_voices_check(const vp_pv_tracker *t, const float *d_in, int n_voices, const int *d_degree, const int *d_period, const double *d_ratio,
+                             int n_blocks)
+{
+    const int rc = trks_check(t, d_in, d_period, d_ratio, n_blocks);
+    if (rc) return rc;
+    return (n_voices < 1 || n_voices > VP_HARM_MAX_VOICES || !d_degree) ? VP_ERR_INVALID_ARG : VP_OK;
+}
+
+extern "C" int vp_pv_tracker_process_blocks_voices_device(vp_pv_tracker *t, const float *d_in, const int *d_key, int n_voices, const int *d_degree,
+                                                          const double *d_unvoiced, int *d_period, double *d_ratio, int n_blocks, void *hip_stream)
+{
+    const int rc = trks_voices_check(t, d_in, n_voices, d_degree, d_period, d_ratio, n_blocks);
+    if (rc) return rc;
+    if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    const VpTrackVoices v = {t->harm, t->harmOff, d_degree, d_unvoiced, n_voices};
+    return trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream, &v);
+}
+
+// the voices call with the harmonizer handle's voice count, then vp_hz_process_blocks_device along its table, on the same stream.  The
+// harmonizer's handle, output and table are looked at first, then the tracker's arguments, then whether the two handles match
+extern "C" int vp_hz_autoharm_blocks_device(vp_hz *h, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, const int *d_degree,
+                                            const double *d_unvoiced, const double *d_gain, const double *d_dry, int *d_period, double *d_ratio,
+                                            int n_blocks, void *hip_stream)
+{
+    if (!h || !d_out || !d_ratio) return VP_ERR_INVALID_ARG;
+    int rc = trks_voices_check(t, d_in, h->V, d_degree, d_period, d_ratio, n_blocks);
+    if (rc) return rc;
+    if (h->S != t->S || h->N != t->N || h->device != t->device) return VP_ERR_GEOMETRY;
+    if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    const VpTrackVoices v = {t->harm, t->harmOff, d_degree, d_unvoiced, h->V};
+    rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream, &v);
+    return rc ? rc : vp_hz_process_blocks_device(h, d_in, d_out, d_ratio, d_gain, d_dry, n_blocks, hip_stream);
 }
 
 // the tracker call, then the streaming call of mode m (whose table is the tracker's d_ratio) along its table, on the same stream.  The

@@ -64,6 +64,44 @@ struct VpTrackUpdArgs {
     int stream[VP_TRKS_MAX_UPDATES];    // -1: every stream
 };
 
+// ---- key-aware voices (vp_stft_track_harmony, vp_pv_tracker_process_blocks_voices_device): the same decision, then V in-key ratios -----
+#define VP_TRACK_MAX_VOICES 4           // = VP_HARM_MAX_VOICES (include/vp_amd.h; vp_capi.hip asserts it)
+#define VP_TRACK_HARM_FMIN 25.0         // the harmony tables: the tracker's recurrence through a wider filter, so that the tracker's table
+#define VP_TRACK_HARM_FMAX 3200.0       // is a slice of the key's harmony table and twelve steps either side of it exist (or clamp at 0)
+#define VP_TRACK_MAX_DEGREE 12
+
+struct VpTrackVoices {
+    const double *harm;                 // [13][VP_NOTES_STRIDE] the harmony table per key
+    const int *harmOff;                 // [13] index of the tracker table's entry 0 in the harmony table.  Where the host builds the tables
+                                        // it checks off + n + 12 <= hN - 1 (hN: the harmony table's entries): no index leaves a table upwards
+    const int *degree;                  // [S][V] steps of the key's table, clamped to -12 .. 12 by the kernel
+    const double *unvoiced;             // [S][V] the ratio of an unvoiced frame, or nullptr (1.0); a NaN or an infinity counts as 1.0
+    int V;                              // 1 .. VP_TRACK_MAX_VOICES
+};
+
+struct VpTrackFollowVoicesArgs {
+    const float *in;                    // as VpTrackFollowArgs
+    const int *period;                  // [nBlocks][S] raw
+    double *ratio;                      // [nBlocks][S][V] raw in, followed out
+    const double *unvoiced;             // [S][V] or nullptr: the target once the hold has run out
+    float *ring;
+    long long *count;
+    double *tgt, *cur;                  // [S][VP_TRACK_MAX_VOICES] the voices' follow state (the mono state is VpTrackFollowArgs')
+    int *age;                           // [S] one age per stream, shared by its voices
+    double glide;
+    int hold;
+    int S, N, W, nBlocks, V;
+};
+
+// enqueue vp_k_yin_track_voices (period [S][nFrames] or nullptr, ratio [S][V][nFrames] or nullptr) and vp_k_yin_track_voices_stream
+// (period [nBlocks][S], ratio [nBlocks][S][V], neither null), grids as their parents'; vp_k_track_follow_voices behind the latter;
+// vp_k_track_reset_voices clears the voices' follow state of the streams an update names (a.count is not read, a.tgt / a.cur are
+// [S][VP_TRACK_MAX_VOICES]).  Each returns hipGetLastError()
+hipError_t vp_track_voices_launch(const VpTrackArgs &a, const VpTrackVoices &v, hipStream_t st);
+hipError_t vp_track_voices_stream_launch(const VpTrackStreamArgs &a, const VpTrackVoices &v, hipStream_t st);
+hipError_t vp_track_follow_voices_launch(const VpTrackFollowVoicesArgs &a, hipStream_t st);
+hipError_t vp_track_reset_voices_launch(const VpTrackUpdArgs &a, hipStream_t st);
+
 // enqueue vp_k_yin_track_stream (grid = ceil(S nBlocks / VP_TRACK_WAVES)), vp_k_track_follow (behind it on the same stream: it rewrites the
 // ring the first one reads) and vp_k_track_reset; each returns hipGetLastError()
 hipError_t vp_track_stream_launch(const VpTrackStreamArgs &a, hipStream_t st);

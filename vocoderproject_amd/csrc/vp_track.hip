@@ -156,6 +156,17 @@ __global__ __launch_bounds__(64 * VP_TRACK_WAVES) void vp_k_yin_track_stream(VpT
     if (lane == 0) { A.period[g] = tau; A.ratio[g] = ratio; }
 }
 
+// the call's last cnt samples (from sample j0 of the slab on) of the workgroup's nS streams go to their rings, from slot0[stream] on
+__device__ __forceinline__ void trk_ring_update(float *ring, const float *in, const int *slot0, int tid, int s0, int nS, int cnt, int j0, int S, int N, int W)
+{
+    for (int e = tid; e < nS * cnt; e += 256) {
+        const int sl = e / cnt, k = e - sl * cnt, s = s0 + sl;
+        const int j = j0 + k, blk = j / N, off = j - blk * N;
+        const int slot = slot0[sl] + k < W ? slot0[sl] + k : slot0[sl] + k - W;
+        ring[(size_t)s * W + slot] = in[((size_t)blk * S + s) * N + off];
+    }
+}
+
 __global__ __launch_bounds__(256) void vp_k_track_follow(VpTrackFollowArgs A)
 {
     __shared__ int slot0[VP_TRKS_GROUP];
@@ -191,12 +202,7 @@ __global__ __launch_bounds__(256) void vp_k_track_follow(VpTrackFollowArgs A)
         A.tgt[s] = tgt; A.cur[s] = cur; A.age[s] = age;
         A.count[s] = n0 + total;
     }
-    for (int e = tid; e < nS * cnt; e += 256) {
-        const int sl = e / cnt, k = e - sl * cnt, s = s0 + sl;
-        const int j = j0 + k, blk = j / A.N, off = j - blk * A.N;
-        const int slot = slot0[sl] + k < A.W ? slot0[sl] + k : slot0[sl] + k - A.W;
-        A.ring[(size_t)s * A.W + slot] = A.in[((size_t)blk * A.S + s) * A.N + off];
-    }
+    trk_ring_update(A.ring, A.in, slot0, tid, s0, nS, cnt, j0, A.S, A.N, A.W);
 }
 
 // a reset stream is a fresh one: no history, follow state (1.0, 0, 1.0)
@@ -228,3 +234,6 @@ hipError_t vp_track_reset_launch(const VpTrackUpdArgs &a, hipStream_t st)
     hipLaunchKernelGGL(vp_k_track_reset, dim3((a.S + 255) / 256), dim3(256), 0, st, a);
     return hipGetLastError();
 }
+
+// ---- key-aware voices (vp_stft_track_harmony, vp_pv_tracker_process_blocks_voices_device): the kernels above with the voice stage ------
+#include "vp_track_voices_kernels.inc"

@@ -21,6 +21,7 @@ There is no CPU path here either: without a GPU the processor raises.
     python -m vocoderproject_amd.offline pvtune a.wav --stream [--block 256 --hold 8 --glide 0.5] --out-dir out/   (... block by block: the streaming tracker)
     python -m vocoderproject_amd.offline pvcross voice.wav [more.wav] --carrier synth.wav [--depth D] [--lifter N] [--stream --block N] [--hop H] --out-dir out/   (STFT cross-synthesis)
     python -m vocoderproject_amd.offline harmonize a.wav [b.wav] --voices 4,7,-5 [--gains 1,1,0.7] [--dry 1] [--stream --block N] [--hop H] --out-dir out/   (peak-locked harmonizer)
+    python -m vocoderproject_amd.offline harmonize a.wav [b.wav] --degrees 2,4,-3 --key 0 [--gains ..] [--dry 1] [--stream --block N --hold 8 --glide 0.5] [--track-csv] --out-dir out/   (voices at degrees of the key)
 """
 import argparse
 import os
@@ -709,6 +710,90 @@ def pv_harmonize(voices, intervals, gains=None, dry=1.0, F=1024, hop=256, N=1024
     return _both_channels(y, lens)
 
 
+class _HarmKeyRunner:
+    """StftRoundTrip.harmonize(degrees=...) from host arrays: x float32 [S][T], keys [S], degrees [S][V], gains [S][V], dry [S] ->
+    (float32 [S][T], period int32 [S][nF], ratio float64 [S][V][nF])."""
+
+    def __init__(self, hop, device):
+        self.hop, self.device = int(hop), device
+
+    def run(self, x, fs, keys, degrees, gains, dry):
+        def call(st, d_in, d_out):
+            return st.harmonize(d_in, d_out, degrees=degrees, sample_rate=float(fs), keys=[int(k) for k in keys], gains=gains, dry=dry)
+        y, (period, ratio) = _one_shot(x, x.shape[1], 1024, self.hop, self.device, call)
+        return y, period.cpu().numpy(), ratio.cpu().numpy()
+
+
+class _StreamHarmKeyRunner:
+    """HarmonizerStream.autoharm_device from host arrays: x float32 [S][n N] -> (y float32 [S][n N] with the harmonizer's latency still in
+    front, period int32 [n][S], ratio float64 [n][S][V])."""
+
+    def __init__(self, N, hop, hold, glide, device, blocks_per_call=16):
+        self.N, self.hop, self.hold, self.glide, self.device, self.k = int(N), int(hop), int(hold), float(glide), device, int(blocks_per_call)
+
+    def run(self, x, fs, keys, degrees, gains, dry):
+        import torch
+        from . import HarmonizerStream, StreamingPitchTracker
+        S, N = x.shape[0], self.N
+        nb = x.shape[1] // N
+        dev = torch.device("cuda", self.device)
+        hz = HarmonizerStream(S, N, degrees.shape[1], hop=self.hop, device=self.device)
+        trk = StreamingPitchTracker(S, N, float(fs), hold_blocks=self.hold, glide=self.glide, device=self.device)
+        try:
+            d_in = torch.from_numpy(np.ascontiguousarray(x.reshape(S, nb, N).transpose(1, 0, 2), np.float32)).to(dev)
+            d_out = torch.empty_like(d_in)
+            tables = [hz.autoharm_device(trk, d_in[b:b + self.k], d_out[b:b + self.k], degrees, n_blocks=min(self.k, nb - b), keys=[int(k) for k in keys],
+                                         gains=gains, dry=dry) for b in range(0, nb, self.k)]
+            torch.cuda.synchronize(dev)
+            y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(S, nb * N)
+            return np.ascontiguousarray(y), torch.cat([p for p, _ in tables]).cpu().numpy(), torch.cat([r for _, r in tables]).cpu().numpy()
+        finally:
+            trk.close()
+            hz.close()
+
+
+def pv_harmonize_key(voices, fs, degrees, key=12, gains=None, dry=1.0, hop=256, N=1024, stream=False, hold=0, glide=1.0, device=0, processor=None,
+                     with_track=False):
+    """The KEY-AWARE harmonizer on a batch (one stream per recording): beside every recording, `dry` times itself, V = 1 .. 4 peak-locked
+    voices at `degrees` (integers within +-12) steps of the key's note table from the note the pitch tracker chose -- scale degrees in a
+    scale key (2 is a third above, 4 a fifth), semitones in the chromatic key 12.  Unvoiced frames take each voice's nominal interval.
+    key: 0..12, one value or one per recording; gains, dry: as pv_harmonize's.  Batch (default): StftRoundTrip.harmonize(degrees=...) on the
+    recordings padded as pv_autotune pads them; stream: block by block through HarmonizerStream.autoharm_device with a
+    StreamingPitchTracker (hold, glide: its follow stage), the harmonizer's latency taken off.  Returns float32 [2][len] per recording;
+    with_track: also period and ratio of the padded batch ([S][nF] and [S][V][nF]; stream: [n_blocks][S] and [n_blocks][S][V]).
+    `processor` (tests): an object with run(x, fs, keys, degrees [S][V], gains [S][V], dry [S]) -> (y, period, ratio) instead of the GPU."""
+    S = _batch_size(voices)
+    many = isinstance(degrees, (list, tuple)) or (isinstance(degrees, np.ndarray) and degrees.ndim == 1)
+    dg = list(degrees) if many else []
+    if not 1 <= len(dg) <= HARM_MAX_VOICES or not all(float(v) == int(v) for v in dg):
+        raise ValueError("degrees: 1 to 4 integers expected")
+    if not all(-12 <= int(v) <= 12 for v in dg):
+        raise ValueError("degrees: steps within +-12 expected")
+    V = len(dg)
+    g = [1.0] * V if gains is None else [float(v) for v in gains]
+    if len(g) != V:
+        raise ValueError("gains: one gain per voice expected")
+    if not all(-4.0 <= v <= 4.0 for v in g):
+        raise ValueError("gains: values within [-4, 4] expected")
+    per = _per_recording(dry, S, "dry", float, -4.0, 4.0, "dry: values within [-4, 4] expected")
+    keys = _per_recording(key, S, "key", int, 0, 12, "key: 0..12 expected (12 = chromatic)")
+    if not 8000.0 <= float(fs) <= 51200.0:
+        raise ValueError("harmonize --degrees: sample rates from 8000 to 51200 Hz are served")
+    if stream and not (int(N) >= 1 and 0 <= int(hold) <= 1 << 20 and 0.0 < float(glide) <= 1.0):
+        raise ValueError("harmonize --stream: a block of at least one sample, 0 <= hold <= 2^20 blocks and 0 < glide <= 1 expected")
+    lens = _lengths(voices)
+    dtab, gtab = np.tile(np.array([int(v) for v in dg], np.int32), (S, 1)), np.tile(np.array(g, np.float64), (S, 1))
+    if stream:
+        T, lat = stream_tune_length(max(lens), N, hop)
+        p = processor if processor is not None else _StreamHarmKeyRunner(N, hop, hold, glide, device)
+    else:
+        T, lat = tune_length(max(lens), fs, 1024, hop), 0
+        p = processor if processor is not None else _HarmKeyRunner(hop, device)
+    y, period, ratio = p.run(_pack_mono(voices, lens, T), float(fs), keys, dtab, gtab, per)
+    outs = _both_channels(y, lens, lat)
+    return (outs, period, ratio) if with_track else outs
+
+
 def write_track_csv(path, fs, hop, period, ratio, n_samples=None):
     """One recording's track: a line per frame with its start time in seconds, the period in samples (0 = unvoiced) and the correction in
     semitones (12 log2 ratio); n_samples: only the frames that start inside the recording."""
@@ -750,6 +835,10 @@ def main(argv=None):
     ap.add_argument("--lifter", type=int, default=32, help="--formant, pvcross: length of the cepstral lifter in samples, 4 to 64 (short: a smoother envelope)")
     ap.add_argument("--voices", default=None, metavar="ST[,ST..]",
                     help="harmonize: 1 to 4 intervals in semitones, each within +-12, comma-separated (a list that starts below zero as --voices=-5,4)")
+    ap.add_argument("--degrees", default=None, metavar="D[,D..]",
+                    help="harmonize, instead of --voices: 1 to 4 voices at integer steps of --key's note table from the tracked note, each within "
+                         "+-12 (scale degrees in a scale key: 2 a third above, 4 a fifth; semitones in key 12); --stream, --hold, --glide and "
+                         "--track-csv as pvtune's")
     ap.add_argument("--gains", default=None, metavar="G[,G..]", help="harmonize: one gain per voice within [-4, 4] (default: 1 each)")
     ap.add_argument("--dry", type=float, default=1.0, help="harmonize: gain of the unshifted signal beside the voices, within [-4, 4] (default 1)")
     ap.add_argument("--hold", type=int, default=0, help="pvtune --stream: unvoiced blocks over which the last voiced ratio is kept")
@@ -780,14 +869,23 @@ def main(argv=None):
             if given:
                 raise SystemExit(f"{flag}: pvcross does not take it (the cross-synthesis moves neither pitch nor time)")
     if a.flow == "harmonize":
-        for flag, given in (("--formant", a.formant is not None), ("--locked", a.locked), ("--subbin", a.subbin), ("--shift", a.shift is not None), ("--glide", a.glide is not None),
-                            ("--stretch", a.stretch is not None), ("--carrier", a.carrier is not None), ("--track-csv", a.track_csv), ("--hold", a.hold != 0)):
+        # (--degrees: the track and, streamed, the tracker's follow stage are pvtune's)
+        tracked = ((("--glide", a.glide is not None and not a.stream), ("--hold", a.hold != 0 and not a.stream)) if a.degrees is not None else
+                   (("--glide", a.glide is not None), ("--track-csv", a.track_csv), ("--hold", a.hold != 0)))
+        for flag, given in (("--formant", a.formant is not None), ("--locked", a.locked), ("--subbin", a.subbin), ("--shift", a.shift is not None),
+                            ("--stretch", a.stretch is not None), ("--carrier", a.carrier is not None)) + tracked:
+            if given and a.degrees is not None:
+                raise SystemExit(f"{flag}: harmonize --degrees does not take it (its voices are peak-locked copies at degrees of the key)")
             if given:
                 raise SystemExit(f"{flag}: harmonize does not take it (its voices are peak-locked copies at the fixed intervals of --voices)")
-        if a.voices is None:
-            raise SystemExit("harmonize needs --voices ST[,ST..]")
+        if a.voices is not None and a.degrees is not None:
+            raise SystemExit("--voices and --degrees exclude each other: fixed intervals or degrees of the key")
+        if a.voices is None and a.degrees is None:
+            raise SystemExit("harmonize needs --voices ST[,ST..] or --degrees D[,D..]")
     elif a.voices is not None or a.gains is not None:
         raise SystemExit("--voices, --gains: harmonize takes them")
+    elif a.degrees is not None:
+        raise SystemExit("--degrees: harmonize takes it")
     if a.formant is not None and a.flow not in ("pvshift", "pvtune"):
         raise SystemExit("--formant: pvshift and pvtune take it")
     if a.locked and a.flow not in ("pvshift", "pvtune", "stretch"):
@@ -830,6 +928,28 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit(str(e))
         return _write_outputs(a, fs, outs)
+    if a.flow == "harmonize" and a.degrees is not None:
+        try:
+            dg = [int(v) for v in a.degrees.split(",")]
+            gains = None if a.gains is None else [float(v) for v in a.gains.split(",")]
+            glide = 1.0 if a.glide is None else float(a.glide)
+        except ValueError:
+            raise SystemExit("--degrees: comma-separated integers expected; --gains: numbers; --glide: one number in (0, 1]")
+        try:
+            outs, period, ratio = pv_harmonize_key(voices, fs, dg, key=a.key, gains=gains, dry=a.dry, hop=a.hop, N=a.block, stream=a.stream,
+                                                   hold=a.hold, glide=glide, device=a.device, with_track=True)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        rc = _write_outputs(a, fs, outs)
+        if a.track_csv:                                                            # one file per recording and voice: the voice's ratio per frame / block
+            step = a.block if a.stream else a.hop
+            for s, f in enumerate(a.inputs):
+                for v in range(len(dg)):
+                    out = os.path.join(a.out_dir, os.path.splitext(os.path.basename(f))[0] + f"_harmonize_v{v}.csv")
+                    write_track_csv(out, fs, step, period[:, s] if a.stream else period[s], ratio[:, s, v] if a.stream else ratio[s, v],
+                                    n_samples=voices[s].shape[-1])
+                    print(out)
+        return rc
     if a.flow == "harmonize":
         try:
             iv = [float(v) for v in a.voices.split(",")]

@@ -204,6 +204,12 @@ def load_library():
         L.vp_hz_process_blocks_device.argtypes = [vp, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.vp_hz_debug_alloc_count.argtypes = [vp]
         L.vp_hz_debug_alloc_count.restype = C.c_long
+    if hasattr(L, "vp_stft_track_harmony"):            # (the key-aware voices; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_stft_track_harmony.argtypes = [vp, fp, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_stft_harmonize_key.argtypes = [vp, fp, fp, C.c_double, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        L.vp_pv_tracker_process_blocks_voices_device.argtypes = [vp, fp, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                                 C.c_void_p]
+        L.vp_hz_autoharm_blocks_device.argtypes = [vp, vp, fp, fp] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
     L.vp_error_string.argtypes = [C.c_int]
     L.vp_error_string.restype = C.c_char_p
     L.vp_last_error.argtypes = [vp]
@@ -770,6 +776,72 @@ def _harm_levels(owner, V, gains, dry, dev):
     return table(gains, "gains", (S, V), [(V,), (S, V)], "gain"), table(dry, "dry", (S,), [(), (S,)], "dry")
 
 
+HARM_MAX_DEGREE = 12                    # VP_TRACK_MAX_DEGREE: the kernels clamp a degree to +-12 steps of the key's table
+
+
+def _host_keys(keys, S):
+    """`keys` as S ints with values outside 0 .. 12 counted as 12 (None: chromatic), or None when it is a device tensor."""
+    if keys is None:
+        return np.full((S,), 12, np.int64)
+    if not isinstance(keys, (int, np.integer, list, tuple, np.ndarray)):
+        return None
+    k = np.broadcast_to(np.asarray(keys), (S,)).astype(np.int64)
+    return np.where((k < 0) | (k > 12), 12, k)
+
+
+def _voice_tables(owner, degrees, keys, unvoiced, dev, V=None):
+    """The degree and unvoiced tables of a key-aware voices call as device tensors (int32 [S][V], float64 [S][V]), and V.  degrees: V ints
+    for every stream or [S][V], V = 1 .. 4 (`V` given: exactly that many), or a device int32 tensor [S][V].  unvoiced: [V], [S][V], a device
+    float64 tensor [S][V], or None = each voice's nominal interval, 2^(d / 12) in the chromatic key and 2^(round(12 d / 7) / 12) in a scale
+    key, computed here on the host (it needs host degrees and host keys: ValueError otherwise).  Host data goes into tables kept on `owner`,
+    rewritten on torch's current stream.  ValueError before anything is launched."""
+    torch = _T or _torch()
+    S = owner.S
+    host = None
+    if isinstance(degrees, torch.Tensor):
+        if not (degrees.is_cuda and degrees.dtype == torch.int32 and degrees.dim() == 2 and degrees.is_contiguous() and degrees.shape[0] == S
+                and 1 <= degrees.shape[1] <= HARM_MAX_VOICES):
+            raise ValueError(f"degrees: a contiguous int32 tensor [{S}][V] on the GPU with V = 1 .. {HARM_MAX_VOICES} expected")
+        d_degree, nV = degrees, int(degrees.shape[1])
+    else:
+        host = np.asarray(degrees)
+        if host.dtype.kind not in "iu" or host.ndim not in (1, 2) or not 1 <= host.shape[-1] <= HARM_MAX_VOICES or (host.ndim == 2 and host.shape[0] != S):
+            raise ValueError(f"degrees: V integers or [{S}][V] of them with V = 1 .. {HARM_MAX_VOICES} expected, got {np.shape(degrees)}")
+        nV = int(host.shape[-1])
+        host = np.array(np.broadcast_to(host, (S, nV)), dtype=np.int32)             # (a copy: torch wants it writable)
+        d_degree = None
+    if V is not None and nV != V:
+        raise ValueError(f"degrees: {V} voices expected, got {nV}")
+    if unvoiced is None:
+        k = _host_keys(keys, S)
+        if host is None or k is None:
+            raise ValueError("unvoiced=None (the nominal intervals) needs degrees and keys on the host: pass an unvoiced table")
+        d = np.clip(host, -HARM_MAX_DEGREE, HARM_MAX_DEGREE).astype(np.float64)
+        semis = np.where(k[:, None] == 12, d, np.floor(12.0 * d / 7.0 + 0.5))
+        u = 2.0 ** (semis / 12.0)
+    elif isinstance(unvoiced, torch.Tensor):
+        if not _is(unvoiced, torch.float64, (S, nV)):
+            raise ValueError(f"unvoiced: a contiguous float64 tensor [{S}][{nV}] on the GPU expected")
+        u = None
+    else:
+        u = np.asarray(unvoiced, dtype=np.float64)
+        if u.shape not in ((nV,), (S, nV)):
+            raise ValueError(f"unvoiced: [{nV}] or [{S}][{nV}] expected, got {u.shape}")
+        u = np.broadcast_to(u, (S, nV))
+    tabs = owner.__dict__.setdefault("_voice_tabs", {})
+    if d_degree is None:
+        if ("deg", nV) not in tabs:
+            tabs[("deg", nV)] = torch.empty((S, nV), dtype=torch.int32, device=dev)
+        d_degree = tabs[("deg", nV)]
+        d_degree.copy_(torch.from_numpy(host))
+    if u is None:
+        return d_degree, unvoiced, nV
+    if ("unv", nV) not in tabs:
+        tabs[("unv", nV)] = torch.empty((S, nV), dtype=torch.float64, device=dev)
+    tabs[("unv", nV)].copy_(torch.from_numpy(np.array(u)))
+    return d_degree, tabs[("unv", nV)], nV
+
+
 class _Handle:
     """The lifecycle of a library handle: <_prefix>_create or VpError, _chk for every later call, close() and __del__ through
     <_prefix>_destroy."""
@@ -943,19 +1015,35 @@ class StftRoundTrip(_Handle):
         self._track_chk(self.L.vp_stft_pitch_shift_formant(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), d_formant.data_ptr(), int(lifter),
                                                            _stream_of(stream, d_in)))
 
-    def harmonize(self, d_in, d_out, semitones=None, d_ratio=None, gains=None, dry=None, stream=None):
+    def harmonize(self, d_in, d_out, semitones=None, d_ratio=None, gains=None, dry=None, stream=None, degrees=None, sample_rate=None, keys=None,
+                  unvoiced=None):
         """The harmonizer (vp_stft_harmonize; 1024-point frames): V = 1 .. 4 peak-locked voices, each shifted by its own interval and mixed
         by its own gain, beside the dry signal, from one analysis of every frame -- dry roundtrip(x) + sum_v gains[v] pitch_shift_locked(x,
         semitones[v]) (the definition is tests/pv_harm_reference.py).  `semitones`: [V] fixed intervals, [V][n_frames] one curve per voice
         for every stream, or [S][V][n_frames], each |value| <= 12; they become ratios through semitones_to_ratios in a device table the
         handle keeps per shape.  d_ratio instead: a device float64 tensor [S][V][n_frames], used as it is (the kernel clamps to [0.5, 2]).
         gains: None (every gain 1), [V], [S][V] or a device float64 tensor [S][V]; dry: None (no dry part), a scalar, [S] or a device
-        float64 tensor [S].  One voice with gain 1 and no dry part has pitch_shift_locked's bits.  Wrong dtypes or shapes raise ValueError
-        before any launch; a 2048-point handle raises VpError."""
+        float64 tensor [S].  One voice with gain 1 and no dry part has pitch_shift_locked's bits.
+        degrees=..., sample_rate=... [, keys=..., unvoiced=...] instead of both: the voices sit at scale degrees of the tracked pitch
+        (vp_stft_harmonize_key: track_harmony, then this call along its table, on one stream); returns track_harmony's (period, ratio).
+        Wrong dtypes or shapes, or more than one of semitones, d_ratio and degrees, raise ValueError before any launch; a 2048-point handle
+        raises VpError."""
         torch = _T or _torch()
         _harm_io(d_in, d_out, (self.S, self.T))
-        if (semitones is None) == (d_ratio is None):
-            raise ValueError("harmonize: one of semitones and d_ratio expected")
+        if (semitones is not None) + (d_ratio is not None) + (degrees is not None) != 1:
+            raise ValueError("harmonize: exactly one of semitones, d_ratio and degrees expected")
+        if degrees is not None:
+            if sample_rate is None:
+                raise ValueError("harmonize: degrees need sample_rate")
+            d_degree, d_unv, V = _voice_tables(self, degrees, keys, unvoiced, d_in.device)
+            d_gain, d_dry = _harm_levels(self, V, gains, dry, d_in.device)
+            d_key, period, ratio = self._track_tables(keys, d_in.device, V)
+            self._track_chk(self.L.vp_stft_harmonize_key(self.h, d_in.data_ptr(), d_out.data_ptr(), float(sample_rate), _ptr(d_key), V, d_degree.data_ptr(),
+                                                         _ptr(d_unv), _ptr(d_gain), _ptr(d_dry), period.data_ptr(), ratio.data_ptr(),
+                                                         _stream_of(stream, d_in)))
+            return period, ratio
+        if sample_rate is not None or keys is not None or unvoiced is not None:
+            raise ValueError("harmonize: sample_rate, keys and unvoiced go with degrees")
         nF = self.n_frames
         if d_ratio is None:
             st = np.asarray(semitones, dtype=np.float64)
@@ -1091,13 +1179,14 @@ class StftRoundTrip(_Handle):
         self._track_chk(self.L.vp_stft_time_stretch_locked(self.h, d_in.data_ptr(), n_in, d_pos.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(),
                                                            _stream_of(stream, d_in)))
 
-    def _track_tables(self, keys, dev):
+    def _track_tables(self, keys, dev, V=None):
         """(d_key or None, period, ratio): the call's key table and outputs.  The key table is kept per handle (one device int32 [S],
-        rewritten on torch's current stream when `keys` is host data); the outputs are new tensors, the caller's to keep."""
+        rewritten on torch's current stream when `keys` is host data); the outputs are new tensors, the caller's to keep.  V: the ratio
+        table of a voices call, [S][V][n_frames]."""
         import torch
         d_key = _device_keys(self, keys, dev)
         period = torch.empty((self.S, self.n_frames), dtype=torch.int32, device=dev)
-        ratio = torch.empty((self.S, self.n_frames), dtype=torch.float64, device=dev)
+        ratio = torch.empty((self.S, self.n_frames) if V is None else (self.S, V, self.n_frames), dtype=torch.float64, device=dev)
         return d_key, period, ratio
 
     def _track_chk(self, rc):
@@ -1117,6 +1206,22 @@ class StftRoundTrip(_Handle):
         d_key, period, ratio = self._track_tables(keys, d_in.device)
         self._track_chk(self.L.vp_stft_track_pitch(self.h, d_in.data_ptr(), float(sample_rate), _ptr(d_key), period.data_ptr(), ratio.data_ptr(),
                                                    _stream_of(stream, d_in)))
+        return period, ratio
+
+    def track_harmony(self, d_in, sample_rate, degrees, keys=None, unvoiced=None, stream=None):
+        """Key-aware voices (vp_stft_track_harmony): track_pitch's decision for every frame, then one ratio per voice that puts it
+        `degrees[v]` steps of the key's table (scale degrees in a scale key, semitones in the chromatic key; clamped to +-12) from the note
+        the tracker chose.  Returns (period, ratio), device tensors int32 [S][n_frames] / float64 [S][V][n_frames] -- the table
+        harmonize(d_ratio=...) takes.  degrees: V ints for every stream or [S][V], V = 1 .. 4; keys as track_pitch's; unvoiced: the ratio of
+        unvoiced frames, [V] or [S][V], None = each voice's nominal interval (2^(d / 12) chromatic, 2^(round(12 d / 7) / 12) in a scale
+        key).  Degree 0 gives track_pitch's ratio bit for bit.  Wrong shapes raise ValueError before any launch."""
+        torch = _T or _torch()
+        if not _is(d_in, torch.float32, (self.S, self.T)):
+            raise ValueError(f"track_harmony: input: a contiguous float32 tensor [{self.S}][{self.T}] on the GPU expected")
+        d_degree, d_unv, V = _voice_tables(self, degrees, keys, unvoiced, d_in.device)
+        d_key, period, ratio = self._track_tables(keys, d_in.device, V)
+        self._track_chk(self.L.vp_stft_track_harmony(self.h, d_in.data_ptr(), float(sample_rate), _ptr(d_key), V, d_degree.data_ptr(), _ptr(d_unv),
+                                                     period.data_ptr(), ratio.data_ptr(), _stream_of(stream, d_in)))
         return period, ratio
 
     def autotune(self, d_in, d_out, sample_rate, keys=None, stream=None, formant_semitones=None, lifter=FORMANT_LIFTER, locked=False, subbin=False):
@@ -1393,17 +1498,54 @@ class HarmonizerStream(_BlockStream):
         self._chk(self.L.vp_hz_process_blocks_device(self.h, d_in.data_ptr(), d_out.data_ptr(), d_ratio.data_ptr(), _ptr(d_gain), _ptr(d_dry), n,
                                                      _stream_of(stream, d_in)))
 
-    def run(self, x, semitones, blocks_per_call=8, gains=None, dry=None):
+    def autoharm_device(self, tracker, d_in, d_out, degrees, n_blocks=1, keys=None, unvoiced=None, gains=None, dry=None, stream=None):
+        """Key-aware harmony on the device (vp_hz_autoharm_blocks_device): tracker.process_voices_device with this handle's voice count, then
+        process_device along its table, on one stream; the output has the bits of those two calls.  `tracker`: a StreamingPitchTracker
+        of the same S, N and device.  degrees, keys, unvoiced as StreamingPitchTracker.process_voices_device's; gains, dry as
+        process_device's.  Returns the tracker's (period, ratio).  Resets stay separate.  ValueError before any launch."""
+        torch = _T or _torch()
+        n = int(n_blocks)
+        if n < 1:
+            raise ValueError("harmonize: at least one block expected")
+        _harm_io(d_in, d_out, (self.S, self.N) if n == 1 and d_in.dim() == 2 else (n, self.S, self.N))
+        if (tracker.S, tracker.N) != (self.S, self.N):
+            raise ValueError(f"harmonize: the tracker has {tracker.S} streams of {tracker.N}-sample blocks, the harmonizer {self.S} of {self.N}")
+        d_degree, d_unv, _ = _voice_tables(tracker, degrees, keys, unvoiced, d_in.device, V=self.V)
+        d_gain, d_dry = _harm_levels(self, self.V, gains, dry, d_in.device)
+        d_key = _device_keys(tracker, keys, d_in.device)
+        period = torch.empty((n, self.S), dtype=torch.int32, device=d_in.device)
+        ratio = torch.empty((n, self.S, self.V), dtype=torch.float64, device=d_in.device)
+        self._chk(self.L.vp_hz_autoharm_blocks_device(self.h, tracker.h, d_in.data_ptr(), d_out.data_ptr(), _ptr(d_key), d_degree.data_ptr(), _ptr(d_unv),
+                                                      _ptr(d_gain), _ptr(d_dry), period.data_ptr(), ratio.data_ptr(), n, _stream_of(stream, d_in)))
+        return period, ratio
+
+    def run(self, x, semitones=None, blocks_per_call=8, gains=None, dry=None, degrees=None, autoharm=None, keys=None, unvoiced=None):
         """Whole signals float [S][T] -> output aligned with the input, [S][T]: the input padded with `latency` zeros (and up to whole
         blocks), streamed through process_device `blocks_per_call` blocks at a time, the first `latency` samples dropped.  `semitones`:
-        [V], [S][V] or [n_blocks_total][S][V] with n_blocks_total = ceil((T + latency) / N).  Continues from the handle's state (reset()
-        first for a fresh start)."""
+        [V], [S][V] or [n_blocks_total][S][V] with n_blocks_total = ceil((T + latency) / N).  degrees=..., autoharm=tracker [, keys=...,
+        unvoiced=...] instead of semitones: the blocks go through autoharm_device, and the result is (output, period [n_blocks_total][S],
+        ratio [n_blocks_total][S][V]).  Continues from the handle's state (reset() first for a fresh start)."""
         import torch
         x = np.asarray(x, dtype=np.float32)
         if x.ndim != 2 or x.shape[0] != self.S:
             raise ValueError(f"harmonize: input {x.shape}: an array [{self.S}][T] expected")
+        if (semitones is None) == (degrees is None):
+            raise ValueError("harmonize: one of semitones and degrees expected")
+        if (degrees is None) != (autoharm is None):
+            raise ValueError("harmonize: degrees and autoharm=tracker go together")
         T = x.shape[1]
         nb, lat = self._n_blocks(T)
+        if degrees is not None:
+            d_x = self._slab(x, nb)
+            d_out = torch.empty_like(d_x)
+            ps, rs = [], []
+            for b in range(0, nb, int(blocks_per_call)):
+                k = min(int(blocks_per_call), nb - b)
+                p, r = self.autoharm_device(autoharm, d_x[b:b + k], d_out[b:b + k], degrees, n_blocks=k, keys=keys, unvoiced=unvoiced, gains=gains, dry=dry)
+                ps.append(p)
+                rs.append(r)
+            y = self._trimmed(d_out, T, lat)
+            return y, torch.cat(ps).cpu().numpy(), torch.cat(rs).cpu().numpy()
         st = np.asarray(semitones, dtype=np.float64)
         if st.shape not in ((self.V,), (self.S, self.V), (nb, self.S, self.V)):
             raise ValueError(f"harmonize: semitones: [{self.V}], [{self.S}][{self.V}] or [{nb}][{self.S}][{self.V}] expected, got {st.shape}")
@@ -1454,4 +1596,25 @@ class StreamingPitchTracker(_StreamHandle):
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
         self._chk(self.L.vp_pv_tracker_process_blocks_device(self.h, d_in.data_ptr(), d_key.data_ptr() if d_key is not None else None,
                                                              period.data_ptr(), ratio.data_ptr(), int(n_blocks), C.c_void_p(stream)))
+        return period, ratio
+
+    def process_voices_device(self, d_in, degrees, n_blocks=1, keys=None, unvoiced=None, stream=None):
+        """Key-aware voices (vp_pv_tracker_process_blocks_voices_device): process_device's decision, then per voice the ratio `degrees[v]`
+        steps of the key's table from the note chosen, followed per voice (hold, glide: set_follow's; after the hold the target is
+        `unvoiced`).  degrees, keys, unvoiced as StftRoundTrip.track_harmony's.  Returns (period, ratio), device tensors int32 [n_blocks][S] /
+        float64 [n_blocks][S][V] -- the table HarmonizerStream.process_device(d_ratio=...) takes.  A block goes through this call or
+        process_device, not both; each keeps its own follow state.  ValueError before any launch."""
+        torch = _T or _torch()
+        n = int(n_blocks)
+        if n < 1:
+            raise ValueError("process_voices_device: at least one block expected")
+        shape = (self.S, self.N) if n == 1 and d_in.dim() == 2 else (n, self.S, self.N)
+        if not _is(d_in, torch.float32, shape):
+            raise ValueError(f"process_voices_device: input: a contiguous float32 tensor {list(shape)} on the GPU expected")
+        d_degree, d_unv, V = _voice_tables(self, degrees, keys, unvoiced, d_in.device)
+        d_key = _device_keys(self, keys, d_in.device)
+        period = torch.empty((n, self.S), dtype=torch.int32, device=d_in.device)
+        ratio = torch.empty((n, self.S, V), dtype=torch.float64, device=d_in.device)
+        self._chk(self.L.vp_pv_tracker_process_blocks_voices_device(self.h, d_in.data_ptr(), _ptr(d_key), V, d_degree.data_ptr(), _ptr(d_unv),
+                                                                    period.data_ptr(), ratio.data_ptr(), n, _stream_of(stream, d_in)))
         return period, ratio
