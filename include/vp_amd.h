@@ -247,9 +247,16 @@ int vp_get_time_parallel(const vp_handle *h);
  * up to 256 streams).  1 (default): vp_k_pitch_ws / vp_k_pitch_ws_x, the WAVE-SPECIALISED kernel (csrc/vp_pitch_ws.inc: every frame
  * start's yin() / LPC / marks on four background wavefronts beside the running frame's chunks, PitchProcess.cpp:203-271).  0: the
  * phase kernels (vp_k_pitch_fast_c / vp_k_pitch_c), which also serve every other geometry.  Same output bits either way
- * (tests/test_gpu_round5.py); the switch exists for that test and for same-box A/B timing (tools/ws_ab.py). */
+ * (tests/test_gpu_round5.py); the switch exists for that test and for same-box A/B timing (tools/ws_ab.py).
+ * Under 1, FAST single-block calls of exactly the plugin's geometry at 44.1 kHz (pitch corrector alone, certified YIN, blocks of one
+ * to four whole chunks) launch vp_k_pitch_ws_l, the lean build of vp_k_pitch_ws (csrc/vp_pitch_ws_body.inc; +6.6 % on the benched
+ * workload, profiles/ws_lean_ab.txt).  2: wave-specialised, GENERIC builds only -- never the lean one.  Same bits again
+ * (tests/test_gpu_ws_lean.py). */
 int vp_set_wave_specialised(vp_handle *h, int on);
 int vp_get_wave_specialised(const vp_handle *h);
+/* Diagnostic: symbol of the pitch kernel the handle's LAST process call launched ("" before the first; of a call with several
+ * cohorts, the last cohort's).  vp_pitch_kernel_name() names the family the geometry selects; this names the build that ran. */
+const char *vp_debug_pitch_symbol(const vp_handle *h);
 
 /* How the YIN difference function (PitchProcess.cpp:350-403) and the pitch frame's LPC autocorrelation
  * (LPC.cpp:44-97) are evaluated.

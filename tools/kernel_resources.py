@@ -6,6 +6,7 @@
 
 `.private_segment_fixed_size` is the scratch (spill) bytes per lane; tests/test_kernel_resources.py fails when a kernel that a
 BASELINE config launches has any."""
+import contextlib
 import os
 import re
 import shutil
@@ -17,17 +18,30 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def kernel_resources(lib):
-    """{demangled kernel name: {vgpr, agpr, sgpr, scratch, lds, vgpr_spill, sgpr_spill}} for the gfx950 code objects of `lib`."""
-    out = {}
+@contextlib.contextmanager
+def code_objects(lib):
+    """The gfx950 code objects of `lib`, extracted into a temporary directory: their paths, for as long as the block runs."""
     with tempfile.TemporaryDirectory(prefix="vp_co_") as tmp:
         so = os.path.join(tmp, "lib.so")
         shutil.copy(lib, so)                                   # llvm-objdump --offloading extracts next to its input
         subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", so], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        for f in sorted(os.listdir(tmp)):
-            if "amdgcn" not in f:
-                continue
-            txt = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", os.path.join(tmp, f)], check=True, capture_output=True, text=True).stdout
+        yield [os.path.join(tmp, f) for f in sorted(os.listdir(tmp)) if "amdgcn" in f]
+
+
+def by_short_name(per_symbol):
+    """{mangled symbol: value} -> {demangled name without 'void' and the argument list: value}."""
+    names = list(per_symbol)
+    filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
+    dem = subprocess.run([filt] + names, capture_output=True, text=True).stdout.split("\n") if (names and filt) else names
+    return {(re.sub(r"\(.*", "", dn.replace("void ", "")).strip() or n): per_symbol[n] for n, dn in zip(names, dem)}
+
+
+def kernel_resources(lib):
+    """{demangled kernel name: {vgpr, agpr, sgpr, scratch, lds, vgpr_spill, sgpr_spill}} for the gfx950 code objects of `lib`."""
+    out = {}
+    with code_objects(lib) as objs:
+        for obj in objs:
+            txt = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", obj], check=True, capture_output=True, text=True).stdout
             for blk in re.split(r"\n\s*- \.agpr_count:", txt)[1:]:
                 blk = ".agpr_count:" + blk
                 def num(key):
@@ -38,14 +52,18 @@ def kernel_resources(lib):
                     continue
                 out[m.group(1)] = dict(vgpr=num("vgpr_count"), agpr=num("agpr_count"), sgpr=num("sgpr_count"), scratch=num("private_segment_fixed_size"),
                                        lds=num("group_segment_fixed_size"), vgpr_spill=num("vgpr_spill_count"), sgpr_spill=num("sgpr_spill_count"))
-    names = list(out)
-    filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
-    dem = subprocess.run([filt] + names, capture_output=True, text=True).stdout.split("\n") if (names and filt) else names
-    res = {}
-    for n, dn in zip(names, dem):
-        short = re.sub(r"\(.*", "", dn.replace("void ", "")).strip() or n
-        res[short] = out[n]
-    return res
+    return by_short_name(out)
+
+
+def kernel_code_bytes(lib):
+    """{demangled kernel name: bytes of machine code} for the gfx950 code objects of `lib`: the size of each kernel's function symbol."""
+    sizes = {}
+    with code_objects(lib) as objs:
+        for obj in objs:
+            txt = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--symbols", "--wide", obj], check=True, capture_output=True, text=True).stdout
+            for m in re.finditer(r"^\s*\d+:\s+[0-9a-f]+\s+(\d+)\s+FUNC\s+\S+\s+\S+\s+\S+\s+(\S+)$", txt, re.M):
+                sizes[m.group(2)] = int(m.group(1))
+    return by_short_name(sizes)
 
 
 def fp64_op_counts(lib, kernel):

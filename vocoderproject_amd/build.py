@@ -22,7 +22,7 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libvp_amd.so")
 SOURCES = ["vp_kernels.hip", "vp_voc2.hip", "vp_stft.hip", "vp_channels.hip", "vp_track.hip", "vp_capi.hip"]
 ARCH = "gfx950"
-NUM_TUS = 9          # groups of kernels in vp_kernels.hip (VP_TU)
+NUM_TUS = 10         # groups of kernels in vp_kernels.hip (VP_TU)
 
 
 def deps_of(source):
@@ -110,6 +110,13 @@ def prune_cache(cap=CACHE_CAP_BYTES):
             pass
 
 
+def compile_command():
+    """hipcc and the flags every translation unit of the pitch-corrector / vocoder kernels is compiled with (tools/kernel_code_map.py
+    compiles its listings with the same)."""
+    return [hipcc(), "-std=c++17", "-O3", "-ffp-contract=off", "-fdenormal-fp-math=preserve-sign", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
+            "-I", os.path.join(ROOT, "include"), "-I", CSRC]
+
+
 def build(force=False, verbose=False, stamps=False, poison=False):
     """stamps=True builds the DIAGNOSTIC library (in-kernel phase timers, -DVP_STAMPS) next to the
     product one; it is only ever loaded through VP_AMD_LIB by tools/phase_stamps.py.
@@ -124,8 +131,7 @@ def build(force=False, verbose=False, stamps=False, poison=False):
     # vp_capi.hip is one more; then one link.  (One translation unit takes 90 s, the groups 40 s.)
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
-    common = [hipcc(), "-std=c++17", "-O3", "-ffp-contract=off", "-fdenormal-fp-math=preserve-sign", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
-              "-I", os.path.join(ROOT, "include"), "-I", CSRC]
+    common = compile_command()
     common += os.environ.get("VP_EXTRA_HIPCC_FLAGS", "").split()     # experiments (tools/ab.sh): e.g. scheduler options
     if stamps:
         common.append("-DVP_STAMPS")

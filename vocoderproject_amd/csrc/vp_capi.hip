@@ -71,7 +71,8 @@ struct vp_handle {
     // only the launch's first slice of N + C entries from HBM and starts every later block's slice from zeros, so it waits for both
     // counters to run out (a call after a vocoder block goes block by block until then)
     int accLive = 0;
-    int waveSpec = 1;                           // vp_set_wave_specialised: vp_k_pitch_ws* where they apply (pitch_ws_ok)
+    int waveSpec = 1;                           // vp_set_wave_specialised: vp_k_pitch_ws* where they apply (pitch_ws_ok); 2: never the lean build
+    const char *pitchSymbol = "";               // vp_debug_pitch_symbol: the pitch kernel the last process call launched
     int timeParallel = 0;                       // vp_set_time_parallel: stored and returned, without effect (the analysis front end it selected was removed in round 6)
     std::vector<void *> allocs;
     float *stageIn = nullptr, *stageOut = nullptr;
@@ -220,6 +221,27 @@ static bool pitch_ws_ok(const vp_handle *h, bool fast, int nBlocks, int nSteps)
     return vp_pitch_ws_lds_bytes(g, nSteps) + 256 <= h->ldsMax;                 // (+ the kernels' static reduction slots: 384 bytes against the 256 ldsMax leaves)
 }
 
+// The LEAN build of vp_k_pitch_ws (vp_k_pitch_ws_l, vp_pitch_ws_body.inc): what its text fixes as constants or leaves out must hold for
+// the launch -- FAST, the plugin's geometry at 44.1 kHz, the pitch corrector alone with both fusions, the certified YIN, twelve
+// wavefronts, blocks of one to four whole chunks on the chunk grid, and the prologue's four-samples-per-lane form (vp_ws_vec_ok: the
+// kernel carries no other).  Everything else -- and vp_set_wave_specialised(h, 2) -- keeps the generic builds.  Called where
+// pitch_ws_ok holds; cp / d are the launch's own arguments.
+// (a wave-specialised build and its symbol, kept together: the launch sites report what they launch, vp_debug_pitch_symbol)
+struct WsPlan { void (*fn)(VpGeom, VpCall, VpDev, VpWsSched, const float *, float *); const char *name; };
+struct WsMbPlan { void (*fn)(VpGeom, VpCall, VpDev, VpWsMb, const float *, float *); const char *name; };
+#define VP_WS_PLAN(K) WsPlan{K, #K}
+#define VP_WS_MB_PLAN(K) WsMbPlan{K, #K}
+static bool pitch_ws_lean_ok(const vp_handle *h, const VpCall &cp, const VpDev &d, int wsWaves, const float *d_in)
+{
+    const VpGeom &g = h->g;
+    if (h->waveSpec != 1 || !cp.iirFast || !pitch_common(h) || !vp_ws_lean_geom(g) || wsWaves != WS_LEAN_WAVES) return false;
+    if (!cp.fuseIngest || !cp.fuseEmit || cp.vocOn || !cp.pitchOn || cp.yinCert != 1 || d.outAcc2 || cp.nBlocks != 1) return false;
+    if (cp.pStart != 0 || g.N % g.C != 0 || cp.nSteps != g.N / g.C || cp.nSteps < 1 || cp.nSteps > 4) return false;
+    // (every stream's slab and ring: the first one's address and strides of whole 16-byte groups -- N and inSize are multiples of four
+    // where vp_ws_vec_ok holds)
+    return vp_ws_vec_ok(g, cp, 64 * wsWaves, vp_ws_p0(g, cp), (size_t)d_in, (size_t)d.voiceRing);
+}
+
 // The certified cross-correlation YIN of the full-register common-case builds (vp_k_pitch_c, vp_k_pitch_fast_c, vp_k_pitch_fast_multi_c)
 // evaluates its cross-correlations by FFT (vp_pitch.inc xcorr_fft_wave; they carry no other form): one wavefront and one exchange
 // buffer per forward transform, two per 512-sample segment of the frame.  0: the launch does not use it.
@@ -305,9 +327,10 @@ extern "C" int vp_get_time_parallel(const vp_handle *h) { return h ? h->timePara
 extern "C" int vp_set_wave_specialised(vp_handle *h, int on)
 {
     if (!h) return VP_ERR_INVALID_ARG;
-    h->waveSpec = on ? 1 : 0;
+    h->waveSpec = on == 2 ? 2 : on ? 1 : 0;
     return VP_OK;
 }
+extern "C" const char *vp_debug_pitch_symbol(const vp_handle *h) { return h ? h->pitchSymbol : ""; }
 extern "C" int vp_get_wave_specialised(const vp_handle *h) { return h ? h->waveSpec : VP_ERR_INVALID_ARG; }
 
 extern "C" const char *vp_vocoder_kernel_name(const vp_handle *h)
@@ -698,7 +721,7 @@ extern "C" int vp_prepare_explicit(vp_handle *h, double fs, int N, int S, int F,
                              (const void *)vp_k_pitch_fast_multi, (const void *)vp_k_pitch_lite, (const void *)vp_k_pitch_lite_fast,
                              (const void *)vp_k_pitch_c, (const void *)vp_k_pitch_fast_c, (const void *)vp_k_pitch_fast_multi_c,
                              (const void *)vp_k_pitch_lite_fast_c, (const void *)vp_k_pitch_lite_fast_multi, (const void *)vp_k_pitch_lite_fast_multi_c,
-                             (const void *)vp_k_pitch_ws, (const void *)vp_k_pitch_ws_x, (const void *)vp_k_pitch_ws_mb, (const void *)vp_k_pitch_ws_x_mb, (const void *)vp_k_pitch_ws_mb_o24, (const void *)vp_k_pitch_ws_x_mb_o24, (const void *)vp_k_pitch_ws_o24, (const void *)vp_k_pitch_ws_x_o24,
+                             (const void *)vp_k_pitch_ws, (const void *)vp_k_pitch_ws_x, (const void *)vp_k_pitch_ws_mb, (const void *)vp_k_pitch_ws_x_mb, (const void *)vp_k_pitch_ws_mb_o24, (const void *)vp_k_pitch_ws_x_mb_o24, (const void *)vp_k_pitch_ws_o24, (const void *)vp_k_pitch_ws_x_o24, (const void *)vp_k_pitch_ws_l,
                              (const void *)vp_k_vocoder, (const void *)vp_k_vocoder_o48, (const void *)vp_k_vocoder_lite};
         for (const void *f : fns) {
             hipFuncAttributes fa;
@@ -803,6 +826,7 @@ extern "C" int vp_prepare_explicit(vp_handle *h, double fs, int N, int S, int F,
     // VocoderProcess.cpp:39, PitchProcess.cpp:85,90: startSample = 0, nChunk = 0 for every instance
     h->cohorts.assign(1, vp_handle::Cohort{h->params.pitchBool, h->params.vocBool, 0, 0, 0, S, nullptr, {}});
     h->cohortsDirty = false; h->poisoned = false; h->poisonCode = VP_ERR_HIP;
+    h->pitchSymbol = "";                                                     // (nothing launched since this prepare)
     h->sparams.assign((size_t)S, h->params);                                 // prepare starts every stream from the handle's set
     h->spHost.assign((size_t)S, VpStreamParams{});
     h->synthNonZero = 0;                                                     // the rings start zeroed
@@ -1007,6 +1031,7 @@ static int process_device(vp_handle *h, const float *d_in, float *d_out, hipStre
                         f->cp.fftOff = (int)off; f->cp.fftWaves = fw; plan.lds = off + pitch_xfft_lds(h);
                     }
                     f->cp.ldsBytes = (int)plan.lds;
+                    h->pitchSymbol = plan.name;
                     hipLaunchKernelGGL(plan.fn, dim3(f->n), dim3(512), plan.lds, h->auxStream, f->g, f->cp, f->dp, f->in, f->out);
                 };
                 VpCall cv = c;
@@ -1076,10 +1101,16 @@ static int process_device(vp_handle *h, const float *d_in, float *d_out, hipStre
                     VpWsSched sc;
                     memset(&sc, 0, sizeof sc);
                     if (!ws_build_sched(g, cp.nChunk0, cp.nSteps, sc)) return fail_hip(h, hipErrorInvalidValue, "pitch schedule");   // (pitch_ws_ok's bounds rule this out)
-                    const auto wsk = g.orderPitch > 15 ? (cp.iirFast ? vp_k_pitch_ws_o24 : vp_k_pitch_ws_x_o24) : (cp.iirFast ? vp_k_pitch_ws : vp_k_pitch_ws_x);
-                    hipLaunchKernelGGL(wsk, dim3(co.n), dim3(64 * wsWaves), (size_t)cp.ldsBytes, st, g, cp, d, sc, d_in, d_out);
-                } else
-                hipLaunchKernelGGL(plan.fn, dim3(co.n), dim3(512), plan.lds, st, g, cp, d, d_in, d_out);
+                    const bool lean = pitch_ws_lean_ok(h, cp, d, wsWaves, d_in);
+                    const WsPlan wsk = lean ? VP_WS_PLAN(vp_k_pitch_ws_l)
+                                            : g.orderPitch > 15 ? (cp.iirFast ? VP_WS_PLAN(vp_k_pitch_ws_o24) : VP_WS_PLAN(vp_k_pitch_ws_x_o24))
+                                                                : (cp.iirFast ? VP_WS_PLAN(vp_k_pitch_ws) : VP_WS_PLAN(vp_k_pitch_ws_x));
+                    h->pitchSymbol = wsk.name;
+                    hipLaunchKernelGGL(wsk.fn, dim3(co.n), dim3(64 * wsWaves), (size_t)cp.ldsBytes, st, g, cp, d, sc, d_in, d_out);
+                } else {
+                    h->pitchSymbol = plan.name;
+                    hipLaunchKernelGGL(plan.fn, dim3(co.n), dim3(512), plan.lds, st, g, cp, d, d_in, d_out);
+                }
             }
         }
         hipError_t e = hipGetLastError();
@@ -1325,6 +1356,7 @@ static int process_both_blocks(vp_handle *h, const float *d_in, float *d_out, in
         }
         cp.ldsBytes = (int)plan.lds;
         ProfScope ps(h, st, 2);
+        h->pitchSymbol = plan.name;
         hipLaunchKernelGGL(plan.fn, dim3(co.n), dim3(512), plan.lds, st, gp, cp, dp, d_in, d_out);
     }
     {   // the vocoder: all the windows of the call, from the snapshot and the call's input; its last kernel emits
@@ -1422,8 +1454,10 @@ static int process_ws_blocks(vp_handle *h, const float *d_in, float *d_out, int 
     d.outAcc2 = nullptr;
     {
         ProfScope ps(h, st, 2);
-        const auto wsk = g.orderPitch > 15 ? (fast ? vp_k_pitch_ws_mb_o24 : vp_k_pitch_ws_x_mb_o24) : (fast ? vp_k_pitch_ws_mb : vp_k_pitch_ws_x_mb);
-        hipLaunchKernelGGL(wsk, dim3(co.n), dim3(64 * 12), (size_t)c.ldsBytes, st, g, c, d, mb, d_in, d_out);
+        const WsMbPlan wsk = g.orderPitch > 15 ? (fast ? VP_WS_MB_PLAN(vp_k_pitch_ws_mb_o24) : VP_WS_MB_PLAN(vp_k_pitch_ws_x_mb_o24))
+                                               : (fast ? VP_WS_MB_PLAN(vp_k_pitch_ws_mb) : VP_WS_MB_PLAN(vp_k_pitch_ws_x_mb));
+        h->pitchSymbol = wsk.name;
+        hipLaunchKernelGGL(wsk.fn, dim3(co.n), dim3(64 * 12), (size_t)c.ldsBytes, st, g, c, d, mb, d_in, d_out);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { h->poisoned = true; h->poisonCode = VP_ERR_HIP; return fail_hip(h, e, "kernel launch"); }

@@ -270,6 +270,32 @@ VP_HD static inline WsCarve ws_carve(const VpGeom &g, int nSteps)
 }
 VP_HD static inline size_t vp_pitch_ws_lds_bytes(const VpGeom &g, int nSteps) { return (size_t)ws_carve(g, nSteps).end * sizeof(double); }
 
+// The prologue's four-samples-per-lane form (pitch_ws_body's `vec`) is valid for a launch of nt threads: every count and counter it
+// splits into groups of four samples (two accumulator entries) is a multiple of four (two), everything fits one trip, and the stream's
+// input slab and voice ring (their addresses: xinAddr, vrAddr) are 16-byte aligned.  The generic kernels decide per launch, with their
+// own copy of this text (vp_pitch_ws_body.inc: routed through this helper their machine code moved); the host asks here before it
+// picks the lean build (vp_k_pitch_ws_l), which carries no other form.  tests/test_ws_lean_cpu.py restates it a third time.
+VP_HD static inline int vp_ws_p0(const VpGeom &g, const VpCall &c) { return (c.currCounter + c.pStart - g.toKeep + g.inSize) % g.inSize; }   // (ring_pos: MyBuffer.cpp:152)
+VP_HD static inline bool vp_ws_vec_ok(const VpGeom &g, const VpCall &c, int nt, int p0, size_t xinAddr, size_t vrAddr)
+{
+    // p0: the ring position of the voice window's first sample, vp_ws_p0(g, c) (the kernels have it at hand)
+    const int idx0 = c.pStart - g.toKeep, span = g.toKeep + g.F + (c.nSteps - 1) * g.C;
+    return ((g.N | g.inSize | c.inCounter | p0 | (idx0 - g.latency) | span) & 3) == 0 && ((c.outCounter | g.outSize | (g.N + g.C)) & 1) == 0 &&
+           g.inSize <= 4 * nt && span <= 4 * nt && g.N + g.C <= 2 * nt && ((xinAddr | vrAddr) & 15) == 0;
+}
+
+// The geometry the lean build is compiled for (its chunk, frame and order are constants in the kernel's text): the plugin's own at 44.1 kHz
+#define WS_LEAN_F 1024
+#define WS_LEAN_C 256
+#define WS_LEAN_ORDER 15
+#define WS_LEAN_TAUMAX 441
+#define WS_LEAN_WAVES 12
+VP_HD static inline bool vp_ws_lean_geom(const VpGeom &g)
+{
+    return g.F == WS_LEAN_F && g.C == WS_LEAN_C && g.cpf == 4 && g.H == WS_LEAN_F - WS_LEAN_C && g.toKeep == WS_LEAN_F && g.eLen == 2 * WS_LEAN_F + 3 * WS_LEAN_C &&
+           g.orderPitch == WS_LEAN_ORDER && g.tauMax == WS_LEAN_TAUMAX;
+}
+
 // doubles of LDS one vocoder wavefront needs for a window of length W (see vp_k_vocoder)
 VP_HD static inline size_t voc_wave_doubles(int W)
 {

@@ -22,6 +22,7 @@ __global__ void vp_k_pitch_lite_fast_multi(VpGeom g, VpCall c, VpDev d, const fl
 __global__ void vp_k_pitch_lite_fast_multi_c(VpGeom g, VpCall c, VpDev d, const float *__restrict__ in, float *__restrict__ out);
 __global__ void vp_k_pitch_ws(VpGeom g, VpCall c, VpDev d, VpWsSched sc, const float *__restrict__ in, float *__restrict__ out);
 __global__ void vp_k_pitch_ws_x(VpGeom g, VpCall c, VpDev d, VpWsSched sc, const float *__restrict__ in, float *__restrict__ out);
+__global__ void vp_k_pitch_ws_l(VpGeom g, VpCall c, VpDev d, VpWsSched sc, const float *__restrict__ in, float *__restrict__ out);
 __global__ void vp_k_pitch_ws_mb(VpGeom g, VpCall c, VpDev d, VpWsMb mb, const float *__restrict__ in, float *__restrict__ out);
 __global__ void vp_k_pitch_ws_x_mb(VpGeom g, VpCall c, VpDev d, VpWsMb mb, const float *__restrict__ in, float *__restrict__ out);
 __global__ void vp_k_pitch_ws_mb_o24(VpGeom g, VpCall c, VpDev d, VpWsMb mb, const float *__restrict__ in, float *__restrict__ out);

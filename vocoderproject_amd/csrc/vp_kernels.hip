@@ -19,12 +19,12 @@
 // The kernels are template instantiations of two large bodies; the build compiles this file several times side by side,
 // each translation unit keeping one group of them (-DVP_TU=k; 0 or undefined: all of them, e.g. for -S listings).
 //   1: ingest/gate, vocoder, emit   2: vp_k_pitch   3: vp_k_pitch_fast   4: vp_k_pitch_multi, vp_k_pitch_fast_multi
-//   5: vp_k_pitch_lite, vp_k_pitch_lite_fast   6: vp_k_pitch_ws, vp_k_pitch_ws_x (vp_pitch_ws.inc)
+//   5: vp_k_pitch_lite, vp_k_pitch_lite_fast   6: vp_k_pitch_ws, vp_k_pitch_ws_x (vp_pitch_ws.inc)   7..9: its _o24 and _mb builds
+//   10: vp_k_pitch_ws_l, the lean build of vp_k_pitch_ws
 #ifndef VP_TU
 #define VP_TU 0
 #endif
 #define VP_TU_HAS(K) (VP_TU == 0 || VP_TU == (K))
-#define VP_NUM_TUS 6
 
 #define WAVE 64
 

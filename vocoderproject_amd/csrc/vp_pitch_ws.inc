@@ -71,11 +71,23 @@
 typedef __attribute__((address_space(3))) WsCtl lds_ctl;
 // (a wait that runs out is an ERROR: vp_timeout raises the handle's fault word and the host fails the call -- what the wait was for is
 // not there, so the launch's output is void; d.spinLimit polls ~ a second)
+// LEAN (vp_k_pitch_ws_l; every program below carries the switch down to its waits): a wait that runs out only leaves a mark in LDS,
+// and the launch raises the fault word once, at its end (pitch_ws_body_l) -- the fifty wait sites of the four programs then carry one
+// LDS store each instead of an atomic, a system-scope store and their lane masks.
+// (sixteen bytes, aligned: the kernel's dynamic LDS starts behind its static LDS, and the FFT's exchange buffers and twiddles in it are
+// read and written sixteen bytes at a time -- with a static part of 8 mod 16 bytes (a 4-byte mark) every one of those accesses was
+// misaligned and the launch 9 us longer, measured: profiles/ws_lean_ab.txt)
+__shared__ __attribute__((aligned(16))) int ws_lean_tmo[4];
+template <bool LEAN = false>
 __device__ __forceinline__ void ws_wait_ge(lds_i32 *flag, int target, const VpDev &d)
 {
     int spin = 0;
     while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < target) {
-        if (++spin >= d.spinLimit) { if ((vp_tid() & 63) == 0) vp_timeout(vp_tmo(d, 61)); break; }
+        if (++spin >= d.spinLimit) {
+            if constexpr (LEAN) ws_lean_tmo[0] = 1;
+            else if ((vp_tid() & 63) == 0) vp_timeout(vp_tmo(d, 61));
+            break;
+        }
         __builtin_amdgcn_s_sleep(1);
     }
 }
@@ -85,12 +97,13 @@ __device__ __forceinline__ void ws_signal(lds_i32 *flag, int value)
     if ((vp_tid() & 63) == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 // barrier of a GROUP of n wavefronts: a monotone counter, `gen` the caller's count of barriers passed (uniform in the group)
+template <bool LEAN = false>
 __device__ __forceinline__ void ws_group_barrier(lds_i32 *ctr, int n, int &gen, const VpDev &d)
 {
     gen += 1;
     __threadfence_block();
     if ((vp_tid() & 63) == 0) __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    ws_wait_ge(ctr, n * gen, d);
+    ws_wait_ge<LEAN>(ctr, n * gen, d);
 }
 
 // exclusive prefix sums P[j] of w_j^2, j <= nb, by one wavefront (what wave 5 does in pitch_chunk_start_pre; same additions in the same
@@ -244,6 +257,7 @@ __device__ __forceinline__ void ws_psola_table_seg(const VpGeom &g, const VpDev 
 // behind the store (iir_block_park into yFrame, which nobody reads there before the instance's recursion) -- for the blocks inside the
 // segment's own chunks: what a grain spills beyond the last chunk is not final yet.  The taps are requested per trip: 96 registers of
 // them do not fit beside the gather's state.  Parked instances are released with instMode 3.
+template <bool LEAN = false>
 __device__ __forceinline__ void ws_psola_gather_seg(const VpGeom &g, const VpDev &d, const PitchLds &L, const SegTab &G, lds_ctl *ctl, int sg, int jA, int jB,
                                                     int kFirst, bool first, const lds_f64 *hpPark = nullptr, int nChunk0 = 0)
 {
@@ -266,7 +280,7 @@ __device__ __forceinline__ void ws_psola_gather_seg(const VpGeom &g, const VpDev
     };
     // the release of instance j (and of the instances without trips of their own right behind it), once everything before it is out
     auto release = [&](int j) {
-        ws_wait_ge(&ctl->psDone, j, d);
+        ws_wait_ge<LEAN>(&ctl->psDone, j, d);
         for (;;) {
             if (lane == 0) ctl->instMode[j] = hpPark ? 3 : 2;
             ws_signal(&ctl->psDone, j + 1);
@@ -419,7 +433,7 @@ __device__ __forceinline__ void ws_psola_gather_seg(const VpGeom &g, const VpDev
 // BIG (round 6, the _o24 builds): lpcPitch 16 .. WS_ORDER_MAX -- the phase kernels' forms for those orders (two groups of sixteen lags
 // on the two LPC wavefronts, levinson_fast64 / levinson_row48, 128 samples of impulse response, the block recursion with a history
 // matrix / the one-lane exact chain); the builds for lpcPitch <= 15 carry none of it.
-template <bool FAST, bool BIG>
+template <bool FAST, bool BIG, bool LEAN = false>
 __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c, const VpDev &d, const VpWsSched &sc, lds_f64 *sm, const WsCarve &cv0,
                                               lds_ctl *ctl, int bw, int gateOpen)
 {
@@ -444,6 +458,9 @@ __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c,
         // vector lanes at the head of the start's critical chain)
         VpGeom g = g0;
         WsCarve cv = cv0;
+        // (LEAN: all but tau0 are constants of the build -- nothing derived from them is computed at all)
+        if constexpr (LEAN) asm volatile("" : "+s"(g.tau0));
+        else
         asm volatile("" : "+s"(g.tauMax), "+s"(g.F), "+s"(g.C), "+s"(g.toKeep), "+s"(g.orderPitch), "+s"(g.tau0));
         asm volatile("" : "+s"(cv.xs), "+s"(cv.fr), "+s"(cv.P), "+s"(cv.dY), "+s"(cv.r), "+s"(cv.aPrev), "+s"(cv.hp), "+s"(cv.xp), "+s"(cv.aF), "+s"(cv.tw));
         L.eF = sm + cv.P;                              // the prefix sums live where the phase kernel parks them: "eFrame"
@@ -456,7 +473,7 @@ __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c,
         const int lane = vp_tid() & 63;
         if (!gateOpen) {                                                      // :208-214
             if (lead) {
-                ws_wait_ge(&ctl->bgAdopt, i, d);                            // (the producers adopt the state straight from this copy: they are done with the previous start's)
+                ws_wait_ge<LEAN>(&ctl->bgAdopt, i, d);                            // (the producers adopt the state straight from this copy: they are done with the previous start's)
                 if (lane == 0) { stBG->nAn = 0; stBG->prevPitch = 0; stBG->gateOpen = 0; ctl->pubMode = 0; }
                 ws_signal(&ctl->bgPub, gen);
             }
@@ -465,7 +482,7 @@ __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c,
         const int pn = sc.startPar[i], tS = sc.startStep[i];
         // the frame's parity buffers (and with them the exchange buffers) are free once the previous frame of that parity has
         // had its last chunk's recursion and output
-        ws_wait_ge(&ctl->fillTurn, sc.startNeed[i], d);
+        ws_wait_ge<LEAN>(&ctl->fillTurn, sc.startNeed[i], d);
         if (i == 0) WS_EV(d, wq, 0);
         L.xs = sm + cv.xs + ((g.toKeep - g.tauMax) & 1) + tS * g.C;
         L.r = sm + cv.r + pn * 64;                     // (per parity: a wavefront may be a start ahead of the one that reads these)
@@ -507,16 +524,16 @@ __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c,
             if (BIG) {
                 if (FAST) autocorr_rows_fast<true, false>(xf, g.F, order, L.r, 0, 2);
                 else for (int lag0 = 0; lag0 <= order; lag0 += 16) autocorr_rows_exact8(xf, g.F, order, lag0, L.r);
-                ws_wait_ge(&ctl->acDone, gen, d);
+                ws_wait_ge<LEAN>(&ctl->acDone, gen, d);
             } else
             if (FAST) {
                 const double t0 = autocorr_rows_fast_half<true>(xf, g.F, 0);
-                ws_wait_ge(&ctl->acDone, gen, d);
+                ws_wait_ge<LEAN>(&ctl->acDone, gen, d);
                 const double t1 = L.r[32 + (lane & 15)];
                 if (lane < 16 && lane <= order) L.r[lane] = (t0 + t1) / vp_f64_here(g.F);
             } else {
                 if (order >= 8) autocorr_rows_exact8(xf, g.F, order, 8, L.r);
-                ws_wait_ge(&ctl->acDone, gen, d);
+                ws_wait_ge<LEAN>(&ctl->acDone, gen, d);
             }
             // levinsonDurbin (LPC.cpp:107-148), then the impulse response of 1/A(z) for the block-form recursion, the frame's
             // coefficients where the recursion wavefronts read them
@@ -544,7 +561,7 @@ __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c,
             int fallback = 1;
             // yin()'s state roll (:415-425) -- here, not at the top: the producers adopt a published start straight from this copy, and
             // by now they have long done so (nothing before this point touches the state)
-            ws_wait_ge(&ctl->bgAdopt, i, d);
+            ws_wait_ge<LEAN>(&ctl->bgAdopt, i, d);
             if (lane == 0) {
                 stBG->gateOpen = 1;
                 stBG->prevPeriod = stBG->period;
@@ -557,7 +574,7 @@ __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c,
             wave_sync();
             WS_FINE(d, 1);
             if (xcCert) {
-                ws_wait_ge(&ctl->pDone, gen, d);
+                ws_wait_ge<LEAN>(&ctl->pDone, gen, d);
                 if (i == 0) WS_EV(d, wq, 2);
                 xc_scan_pick(g, L, stBG, xcCert, true);
                 wave_sync();
@@ -574,13 +591,13 @@ __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c,
             if (i == 0) WS_EV(d, wq, 3);
             VP_PRIO_DOWN();
         }
-        ws_wait_ge(&ctl->pickDone, gen, d);                                 // (no helping here: trips beside the lead's pick and marks slow the start's chain down)
+        ws_wait_ge<LEAN>(&ctl->pickDone, gen, d);                                 // (no helping here: trips beside the lead's pick and marks slow the start's chain down)
         if (ctl->pickState) {
             // a comparison of the certified form was too close to call (or VP_YIN_DIRECT): the frame's difference function in
             // the reference's arithmetic, two adjacent lags per lane on the four wavefronts, its running sum and pick on the lead
             if (lead && lane == 0) { ctl->ishareBG[0] = INT_MAX; ctl->ishareBG[1] = 0; }
             yin2_exact_waves(g, L, base, bw * WAVE + (vp_tid() & 63), 0, WS_NBG, (g.tauMax + 1) >> 1);
-            ws_group_barrier(&ctl->bgBar, WS_NBG, bgBarGen, d);
+            ws_group_barrier<LEAN>(&ctl->bgBar, WS_NBG, bgBarGen, d);
             if (lead) {
                 yin_cumsum_wave(g, L, vp_tid() & 63);
                 wave_sync();
@@ -589,11 +606,11 @@ __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c,
                 if ((vp_tid() & 63) == 0) ctl->pickT[pn] = (stBG->pitch > 1) ? stBG->period : stBG->prevVoicedPeriod;
                 ws_signal(&ctl->tDone, gen);
             }
-            ws_group_barrier(&ctl->bgBar, WS_NBG, bgBarGen, d);           // (the running sum lives where the next start's prefix sums go)
+            ws_group_barrier<LEAN>(&ctl->bgBar, WS_NBG, bgBarGen, d);           // (the running sum lives where the next start's prefix sums go)
         }
         // :216-218 for the coming frame: its outEFrame and yFrame start from zero (the exchange buffers lived there)
         if (!lead) {
-            if (xcCert) ws_wait_ge(&ctl->xcDone, gen, d);
+            if (xcCert) ws_wait_ge<LEAN>(&ctl->xcDone, gen, d);
             for (int q = bw * WAVE + lane; q < g.F; q += (WS_NBG - 1) * WAVE) { oEn[q] = 0.0; yFn[q] = 0.0; }
             __threadfence_block();
             if (lane == 0) __hip_atomic_fetch_add((lds_i32 *)&ctl->zeroDone, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -612,13 +629,13 @@ __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c,
         }
         wave_sync();
         if (i == 0) WS_EV(d, wq, 4);                                          // marks placed
-        ws_wait_ge(&ctl->lpcDone, gen, d);
+        ws_wait_ge<LEAN>(&ctl->lpcDone, gen, d);
         if (stBG->nAn != 0) {                                                 // the coefficients are adopted (:233)
             const int ncopy = ctl->lpcZ[pn] ? VP_ORDER_MAX + 1 : g.orderPitch + 1;
             for (int q = lane; q < ncopy; q += WAVE) stBG->a[q] = L.aPrev[q];
         }
         WS_FINE(d, 4);
-        ws_wait_ge(&ctl->zeroDone, (WS_NBG - 1) * gen, d);
+        ws_wait_ge<LEAN>(&ctl->zeroDone, (WS_NBG - 1) * gen, d);
         WS_FINE(d, 5);
         if (lane == 0) ctl->pubMode = stBG->nAn != 0 ? 2 : 1;
         ws_signal(&ctl->bgPub, gen);
@@ -631,7 +648,7 @@ __device__ __forceinline__ void ws_background(const VpGeom &g0, const VpCall &c,
 // PRODUCER program: the block's SEGMENTS in order (a segment = the chunks of one frame that this block's steps run), everything of
 // a chunk that does not depend on the recursion: the residual (filterFIR :280-302), the quotient / Hann tables of the frame, the
 // grain table and the gather pass of psola() (:665-741).  rank 0 owns the serial part (the table); the group meets at its own barrier.
-template <bool FAST>
+template <bool FAST, bool LEAN = false>
 __device__ __forceinline__ void ws_producer(const VpGeom &g, const VpCall &c, const VpDev &d, const VpWsSched &sc, lds_f64 *sm, const WsCarve &cv,
                                             lds_ctl *ctl, int rank, int nP, int gateOpen, bool firstBlock = true, bool lastBlock = true)
 {
@@ -682,13 +699,13 @@ __device__ __forceinline__ void ws_producer(const VpGeom &g, const VpCall &c, co
             // phase kernel's: a frame without analysis marks zeroes eFrame again.
             const int jEnd = g.toKeep + g.F + (jB - jA) * g.C;
             if (gateOpen && rank != 0) {                                      // (rank 0 keeps itself free for the tables: the serial part)
-                ws_wait_ge(&ctl->lpcDone, si + 1, d);
+                ws_wait_ge<LEAN>(&ctl->lpcDone, si + 1, d);
                 WS_TA(d, wq, 1);
                 const lds_f64 *aN = sm + cv.aF + p * WS_AF(g);
                 for (int q = 4 * (tp - WAVE); q < jEnd; q += 4 * (ntp - WAVE)) fir4((const lds_f64 *)L.xs, aN, order, q, jEnd, L.eF);
                 for (int q = jEnd + tp - WAVE; q < g.eLen; q += ntp - WAVE) L.eF[q] = 0.0;
                 WS_TA(d, wq, 2);
-                ws_wait_ge(&ctl->tDone, si + 1, d);
+                ws_wait_ge<LEAN>(&ctl->tDone, si + 1, d);
                 WS_TA(d, wq, 1);
                 const int T = ctl->pickT[p];
                 const double *hg = d.hannTab + d.hannOff[T];
@@ -696,7 +713,7 @@ __device__ __forceinline__ void ws_producer(const VpGeom &g, const VpCall &c, co
                 WS_TA(d, wq, 2);
             }
             // the background has the new frame's pitch, marks and coefficients ready (or is about to)
-            ws_wait_ge(&ctl->bgPub, si + 1, d);
+            ws_wait_ge<LEAN>(&ctl->bgPub, si + 1, d);
             WS_TA(d, wq, 1);                                                  // waited for the background
             WS_FINEP(d, 0);
             mode = ctl->pubMode;
@@ -731,7 +748,7 @@ __device__ __forceinline__ void ws_producer(const VpGeom &g, const VpCall &c, co
             }
             if (mode == 1) for (int q = tp; q < jEnd; q += ntp) L.eF[q] = 0.0;   // no analysis marks: the frame stays as :216-218 left it
             qValid = mode == 2;
-            ws_group_barrier(&ctl->prodBar, nP, barGen, d);
+            ws_group_barrier<LEAN>(&ctl->prodBar, nP, barGen, d);
             WS_TA(d, wq, 3);
             WS_FINEP(d, 3);
             if (rank == 0) ws_signal(&ctl->bgAdopt, si + 1);                  // (everybody has read the published copy)
@@ -757,21 +774,21 @@ __device__ __forceinline__ void ws_producer(const VpGeom &g, const VpCall &c, co
                     WS_TA(d, wq, 2);
                 }
                 qValid = true;
-                ws_group_barrier(&ctl->prodBar, nP, barGen, d);
+                ws_group_barrier<LEAN>(&ctl->prodBar, nP, barGen, d);
                 WS_TA(d, wq, 3);
             }
         }
         if (mode == 2) {
             // the gather pass; the segment is over -- its tables, the residual and the quotient / Hann tables free for the next one's --
             // when its last instance is out
-            ws_psola_gather_seg(g, d, L, G, ctl, sg, jA, jB, kFirst, rank == 0, hpPark, c.nChunk0);
+            ws_psola_gather_seg<LEAN>(g, d, L, G, ctl, sg, jA, jB, kFirst, rank == 0, hpPark, c.nChunk0);
             WS_FINEP(d, 4);
             WS_TA(d, wq, 5);                                                  // gather pass
-            ws_wait_ge(&ctl->psDone, jB + 1, d);
+            ws_wait_ge<LEAN>(&ctl->psDone, jB + 1, d);
             WS_FINEP(d, 6);
             WS_TA(d, wq, 3);
         } else {
-            ws_group_barrier(&ctl->prodBar, nP, barGen, d);
+            ws_group_barrier<LEAN>(&ctl->prodBar, nP, barGen, d);
             WS_TA(d, wq, 3);
             if (rank == 0) {
                 // a Start decides for its frame (no marks: output only, and the Cont chunks do nothing, :255)
@@ -796,7 +813,7 @@ __device__ __forceinline__ void ws_producer(const VpGeom &g, const VpCall &c, co
 // RECURSION program: filterIIR (PitchProcess.cpp:307-322) and fillOutputBuffer (:328-342) of the instances, by ONE wavefront
 // (EXACT: two, frames alternating -- the reference's chain is one dependent sequence per frame, 25 us per chunk, and two
 // consecutive frames share nothing).  The additions into the output keep the reference's order through fillTurn.
-template <bool FAST, bool BIG>
+template <bool FAST, bool BIG, bool LEAN = false>
 __device__ __forceinline__ void ws_recursion(const VpGeom &g, const VpCall &c, const VpDev &d, const VpWsSched &sc, lds_f64 *sm, const WsCarve &cv,
                                              lds_ctl *ctl, int me, int nIir, double gainPitch)
 {
@@ -833,7 +850,7 @@ __device__ __forceinline__ void ws_recursion(const VpGeom &g, const VpCall &c, c
         for (; fj < upto; fj++) {
             if (sc.instPar[fj] != me) continue;
             if (!block && __hip_atomic_load(&ctl->fillTurn, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < fj) break;
-            ws_wait_ge(&ctl->fillTurn, fj, d);
+            ws_wait_ge<LEAN>(&ctl->fillTurn, fj, d);
             double win[8];
             window(fj, win);
             fill(fj, win);
@@ -858,11 +875,15 @@ __device__ __forceinline__ void ws_recursion(const VpGeom &g, const VpCall &c, c
             int spin = 0;
             while (__hip_atomic_load(&ctl->psDone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < j + 1) {
                 flush(j, false);
-                if (++spin >= d.spinLimit) { if (lane == 0) vp_timeout(vp_tmo(d, 61)); break; }
+                if (++spin >= d.spinLimit) {
+                    if constexpr (LEAN) ws_lean_tmo[0] = 1;                   // (EXACT only: no LEAN build reaches this; kept in step with ws_wait_ge)
+                    else if (lane == 0) vp_timeout(vp_tmo(d, 61));
+                    break;
+                }
                 __builtin_amdgcn_s_sleep(1);
             }
         } else
-        ws_wait_ge(&ctl->psDone, j + 1, d);
+        ws_wait_ge<LEAN>(&ctl->psDone, j + 1, d);
         WS_TA(d, me, 1);                                                      // waited for the producers
         if (me == 0) WS_FINER(d, j);
         const int mode = ctl->instMode[j];
@@ -904,7 +925,7 @@ __device__ __forceinline__ void ws_recursion(const VpGeom &g, const VpCall &c, c
             const lds_f64 *aF = sm + cv.aF + p * WS_AF(g), *hpad = sm + cv.hp + p * WS_HP(g);
             if (sc.instStart[j] >= 0) haveR = false;
             else if (!haveR) { iir_block_walk_load(R, aF, order, hpad); haveR = true; }
-            ws_wait_ge(&ctl->psDone, j + 1, d);
+            ws_wait_ge<LEAN>(&ctl->psDone, j + 1, d);
             WS_TA(d, me, 1);                                                  // waited for the producers
             WS_FINER(d, j);
             if (ctl->instMode[j] == 3) {
@@ -924,6 +945,7 @@ __device__ __forceinline__ void ws_recursion(const VpGeom &g, const VpCall &c, c
 
 // FAST: fillOutputBuffer (:328-342) of the instances on a wavefront of its own, in the reference's order, right behind the recursion
 // (which then goes straight on to its next chunk)
+template <bool LEAN = false>
 __device__ __forceinline__ void ws_filler(const VpGeom &g, const VpCall &c, const VpDev &d, const VpWsSched &sc, lds_f64 *sm, const WsCarve &cv,
                                           lds_ctl *ctl, double gainPitch)
 {
@@ -937,7 +959,7 @@ __device__ __forceinline__ void ws_filler(const VpGeom &g, const VpCall &c, cons
         double win[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) win[u] = (u < nW) ? d.pitchStWin[shift + lane + WAVE * u] : 0.0;   // requested before the wait
-        ws_wait_ge(&ctl->iirDone, j + 1, d);
+        ws_wait_ge<LEAN>(&ctl->iirDone, j + 1, d);
         if (ctl->instMode[j] >= 1) {
 #pragma unroll
             for (int u = 0; u < 8; u++) if (u < nW) {
@@ -1156,11 +1178,12 @@ __device__ __forceinline__ void ws_mb_boundary(VpGeom &g, VpCall &c, VpDev &d, c
     ws_mb_launder_carve(cv);
 }
 
+#define WS_IS_LEAN false
 #include "vp_pitch_ws_body.inc"
 #define WS_MB 1
 #include "vp_pitch_ws_body.inc"
 #undef WS_MB
-
+#undef WS_IS_LEAN
 #if VP_TU_HAS(6)
 __global__ __launch_bounds__(768) void vp_k_pitch_ws(VpGeom g, VpCall c, VpDev d, VpWsSched sc, const float *__restrict__ in, float *__restrict__ out)
 {
@@ -1214,5 +1237,19 @@ __global__ __launch_bounds__(768) void vp_k_pitch_ws_x_mb_o24(VpGeom g, VpCall c
 {
     extern __shared__ double smem[];
     pitch_ws_body_mb<false, true>(g, c, d, &mb, in, out, smem);
+}
+#endif
+#if VP_TU_HAS(10)
+#define WS_IS_LEAN true
+#define WS_LEAN 1
+#include "vp_pitch_ws_body.inc"
+#undef WS_LEAN
+#undef WS_IS_LEAN
+// The lean build of vp_k_pitch_ws (FAST, one block per launch) for the launch shape of the plugin's own geometry at 44.1 kHz:
+// see pitch_ws_body_l.  Selected by the host alone (vp_capi.hip pitch_ws_lean_ok); everything else keeps the generic builds.
+__global__ __launch_bounds__(768) void vp_k_pitch_ws_l(VpGeom g, VpCall c, VpDev d, VpWsSched sc, const float *__restrict__ in, float *__restrict__ out)
+{
+    extern __shared__ double smem[];
+    pitch_ws_body_l(g, c, d, sc, in, out, smem);
 }
 #endif

@@ -11,6 +11,7 @@
 // from the input slabs (ONE round of loads), the accumulator slice is shifted, the whole-ring gate is updated incrementally, the frame
 // in flight is moved to the parity-0 buffers if it ended in the others.  Same arithmetic on the same data as block-by-block
 // launches: same bits.
+// A THIRD expansion, with WS_LEAN defined, is pitch_ws_body_l (vp_k_pitch_ws_l): see there.
 #ifdef WS_MB
 template <bool FAST, bool BIG>
 __device__ __forceinline__ void pitch_ws_body_mb(const VpGeom &g_, const VpCall &c_, const VpDev &d_, const VpWsMb *mbp, const float *__restrict__ in,
@@ -25,6 +26,23 @@ __device__ __forceinline__ void pitch_ws_body_mb(const VpGeom &g_, const VpCall 
     c.inCounter = mbp->inCtr[0]; c.outCounter = mbp->outCtr[0]; c.currCounter = mbp->currCtr[0]; c.nChunk0 = mbp->nChunk0[0];
     ws_mb_launder(g, c, d);
 #define sc (*scp)
+#elif defined(WS_LEAN)
+// The LEAN expansion (vp_k_pitch_ws_l): the single-block FAST kernel for the one launch shape the host selects it for (vp_capi.hip
+// pitch_ws_lean_ok) -- pitch corrector alone with both fusions, certified YIN, the plugin's geometry at 44.1 kHz, the `vec` prologue.
+// What that shape fixes is written into private copies of the arguments as CONSTANTS, so every path it never takes (the one-sample
+// prologue, ingest_gate_block, the unfused emit, the yinCert 0 / 2 entries, EXACT, the orders above 15) folds away and the chunk's
+// divisions, trip counts and loop bounds are immediates.  Same routines, same order of every ordered sum: same bits.
+__device__ __forceinline__ void pitch_ws_body_l(const VpGeom &g_, const VpCall &c_, const VpDev &d_, const VpWsSched &sc, const float *__restrict__ in,
+                                                float *__restrict__ out, double *smem)
+{
+    constexpr bool FAST = true, BIG = false;
+    VpGeom g = g_;
+    g.F = WS_LEAN_F; g.C = WS_LEAN_C; g.H = WS_LEAN_F - WS_LEAN_C; g.cpf = 4; g.toKeep = WS_LEAN_F; g.eLen = 2 * WS_LEAN_F + 3 * WS_LEAN_C;
+    g.orderPitch = WS_LEAN_ORDER; g.tauMax = WS_LEAN_TAUMAX;
+    VpCall c = c_;
+    c.fuseIngest = 1; c.fuseEmit = 1; c.vocOn = 0; c.pitchOn = 1; c.yinCert = 1; c.iirFast = 1; c.pStart = 0;
+    VpDev d = d_;
+    d.outAcc2 = nullptr;
 #else
 template <bool FAST, bool BIG>
 __device__ __forceinline__ void pitch_ws_body(const VpGeom &g, const VpCall &c, const VpDev &d, const VpWsSched &sc, const float *__restrict__ in,
@@ -85,8 +103,14 @@ __device__ __forceinline__ void pitch_ws_body(const VpGeom &g, const VpCall &c, 
     // pipeline takes per microsecond (41 per thread in the one-sample form, 3.4 us until the last one has left)
     typedef float f4v __attribute__((ext_vector_type(4)));
     typedef double d2v __attribute__((ext_vector_type(2)));
+#ifdef WS_LEAN
+    constexpr bool vec = true;                                                // (the host launches this build only where vp_ws_vec_ok holds)
+#else
+    // (vp_common.h vp_ws_vec_ok restates this for the host, which asks it before it picks the lean build; tests/test_ws_lean_cpu.py holds
+    // the two together.  The text stays here: routed through the helper, the generic builds' machine code moved)
     const bool vec = ((g.N | g.inSize | c.inCounter | p0 | (idx0 - g.latency) | span) & 3) == 0 && ((c.outCounter | g.outSize | (g.N + g.C)) & 1) == 0 &&
                      g.inSize <= 4 * nt && span <= 4 * nt && g.N + g.C <= 2 * nt && (((size_t)xin | (size_t)vr) & 15) == 0;
+#endif
     f4v gq = {0.f, 0.f, 0.f, 0.f}, xq = {0.f, 0.f, 0.f, 0.f}, w0q = {0.f, 0.f, 0.f, 0.f}, w1q = {0.f, 0.f, 0.f, 0.f}, w2q = {0.f, 0.f, 0.f, 0.f};
     d2v aq = {0.0, 0.0};
     if (vec) {
@@ -280,6 +304,9 @@ __device__ __forceinline__ void pitch_ws_body(const VpGeom &g, const VpCall &c, 
     }
     // the control block: counters from zero (the schedule itself is a kernel argument)
     for (int i = tid; i < (int)(sizeof(WsCtl) / sizeof(int)); i += nt) ((lds_i32 *)ctl)[i] = 0;
+#ifdef WS_LEAN
+    if (tid == 0) ws_lean_tmo[0] = 0;                                           // (a wait that runs out leaves its mark here: raised once, below)
+#endif
     if (tid >= nt / WAVE && tid < 16) gateRed[tid] = 0.0;                     // (the gate's sum takes all sixteen slots)
     WS_EV0(d, 1, 1);                                   // ... consumed ...
     __syncthreads();
@@ -347,15 +374,15 @@ __device__ __forceinline__ void pitch_ws_body(const VpGeom &g, const VpCall &c, 
         // (which of the four takes which rank: the lead on the SIMD it shares with the windowed-add wavefront -- mostly asleep -- and one
         // producer, rather than with two producers: +0.8 %, measured on one box against three other placements)
         const int x = wv - (NW - WS_NBG);
-        ws_background<FAST, BIG>(g, c, d, sc, sm, cv, ctl, FAST ? (0x1230 >> (4 * x)) & 15 : x, gateOpen);   // (EXACT: wavefront 1 is a recursion wavefront; the lead stays last)
+        ws_background<FAST, BIG, WS_IS_LEAN>(g, c, d, sc, sm, cv, ctl, FAST ? (0x1230 >> (4 * x)) & 15 : x, gateOpen);   // (EXACT: wavefront 1 is a recursion wavefront; the lead stays last)
     }
     else if (wv < nRec)
-        ws_recursion<FAST, BIG>(g, c, d, sc, sm, cv, ctl, wv, nRec, gainPitch);
+        ws_recursion<FAST, BIG, WS_IS_LEAN>(g, c, d, sc, sm, cv, ctl, wv, nRec, gainPitch);
     else if (FAST && wv == 1)
-        ws_filler(g, c, d, sc, sm, cv, ctl, gainPitch);
+        ws_filler<WS_IS_LEAN>(g, c, d, sc, sm, cv, ctl, gainPitch);
     else
 #ifdef WS_MB
-        ws_producer<FAST>(g, c, d, sc, sm, cv, ctl, wv - nFG, nP, gateOpen, blk == 0, blk == nB - 1);
+        ws_producer<FAST, WS_IS_LEAN>(g, c, d, sc, sm, cv, ctl, wv - nFG, nP, gateOpen, blk == 0, blk == nB - 1);
     if (blk != nB - 1) ws_lds_barrier(); else
     __syncthreads();
     if (blk == nB - 1) break;
@@ -363,7 +390,7 @@ __device__ __forceinline__ void pitch_ws_body(const VpGeom &g, const VpCall &c, 
     }
 #define out outb
 #else
-        ws_producer<FAST>(g, c, d, sc, sm, cv, ctl, wv - nFG, nP, gateOpen);
+        ws_producer<FAST, WS_IS_LEAN>(g, c, d, sc, sm, cv, ctl, wv - nFG, nP, gateOpen);
     __syncthreads();
 #endif
     STAMP(d, 8);
@@ -402,6 +429,11 @@ __device__ __forceinline__ void pitch_ws_body(const VpGeom &g, const VpCall &c, 
         }
         if (c.fuseEmit) ws_emit_block(g, c, d, out, st, (const lds_f64 *)oA);
     }
+#ifdef WS_LEAN
+    // a bounded wait of this launch ran out (ws_wait_ge<true>): the fault word is raised here, once, still inside the launch -- the
+    // host sees what it sees from the other builds (VP_ERR_TIMEOUT, a poisoned handle)
+    if (tid == 0 && ws_lean_tmo[0] != 0) vp_timeout(vp_tmo(d, 61));
+#endif
 #ifdef VP_STAMPS
     if (blockIdx.x == 0 && threadIdx.x == 0) { atomicAdd(&WS_SLOT(d, 0, 7), 1ULL); atomicAdd(&WS_SLOT(d, 0, 5), (unsigned long long)wall_clock64()); }   // launches of this type; kernel end
 #endif

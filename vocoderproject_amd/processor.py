@@ -117,6 +117,9 @@ def load_library():
     if hasattr(L, "vp_set_wave_specialised"):
         L.vp_set_wave_specialised.argtypes = [C.c_void_p, C.c_int]
         L.vp_get_wave_specialised.argtypes = [C.c_void_p]
+    if hasattr(L, "vp_debug_pitch_symbol"):
+        L.vp_debug_pitch_symbol.argtypes = [C.c_void_p]
+        L.vp_debug_pitch_symbol.restype = C.c_char_p
     if hasattr(L, "vp_debug_set_spin_limit"):          # (ABI version 3)
         L.vp_debug_set_spin_limit.argtypes = [C.c_void_p, C.c_int]
     L.vp_read_ub_counters.argtypes = [vp, C.POINTER(C.c_long)]
@@ -309,8 +312,9 @@ class BatchVocoderProcessor:
         self._chk(self.L.vp_set_time_parallel(self.h, int(bool(on))))
 
     def set_wave_specialised(self, on):
-        """Single-block calls of the plugin's geometry on the wave-specialised pitch kernel (default) or on the phase kernels (same bits)."""
-        self._chk(self.L.vp_set_wave_specialised(self.h, int(bool(on))))
+        """Single-block calls of the plugin's geometry on the wave-specialised pitch kernel (default) or on the phase kernels (same bits).
+        2: the wave-specialised kernel's generic builds only, never its lean build (vp_k_pitch_ws_l; same bits again)."""
+        self._chk(self.L.vp_set_wave_specialised(self.h, 2 if on == 2 else int(bool(on))))
 
     def set_yin_mode(self, mode):
         """"direct" (default: the reference's sums), "xcorr" (certified cross-correlation form, fused multiply-adds) or "fft" (the same
@@ -535,6 +539,10 @@ class BatchVocoderProcessor:
 
     def pitch_kernel_name(self):
         return self.L.vp_pitch_kernel_name(self.h).decode()
+
+    def debug_pitch_symbol(self):
+        """Diagnostic: symbol of the pitch kernel the last process call launched ("" before the first)."""
+        return self.L.vp_debug_pitch_symbol(self.h).decode()
 
     def debug_set_spin_limit(self, polls):
         """Diagnostic: polls a kernel's bounded inter-wavefront wait makes before it raises VP_ERR_TIMEOUT (default 2^22)."""
