@@ -596,6 +596,28 @@ int vp_stft_track_harmony(vp_stft *p, const float *d_in, double sample_rate, con
  * before the device is touched. */
 int vp_stft_harmonize_key(vp_stft *p, const float *d_in, float *d_out, double sample_rate, const int *d_key, int n_voices, const int *d_degree,
                           const double *d_unvoiced, const double *d_gain, const double *d_dry, int *d_period, double *d_ratio, void *hip_stream);
+/* THE FINE TRACKER (kernels vp_k_yin_track_fine and vp_k_yin_track_voices_fine, csrc/vp_track_fine_kernels.inc): the same decision, with
+ * the period refined below one sample by a parabola through the normalised function d' around its minimum (step 5 of the YIN paper).  The
+ * integer period quantises the pitch to +-1/2 sample (+-6 cents at 300 Hz, +-15 at 780 Hz at 44.1 kHz); refined, the error of a steady
+ * voice stays below a third of a cent (profiles/pv_track_fine_quality.txt).  The definition is tests/pv_track_fine_reference.py, bit for bit:
+ *   tau > 0 the integer period, a = d'[tau - 1], b = d'[tau], c = d'[tau + 1];
+ *   refine iff tau - 1 >= 1 and tau + 1 <= tauMax - 1 (neither lag 0 nor the guard slot is a neighbour), a >= b, c >= b, and
+ *   den = (a - b) + (c - b) is > 0 and finite; then tau_fine = tau + (0.5 (a - c)) / den, |tau_fine - tau| <= 1/2; else tau_fine = tau;
+ *   pitch = fs / tau_fine, ratio = closest(pitch, key) / pitch: the note is looked up again, on the refined pitch, and may differ from
+ *   the integer tracker's near the midpoint between two notes.  Unvoiced: period 0, tau_fine 0.0, ratio 1.0.  A NaN fails a comparison.
+ * vp_stft_set_track_mode selects, per handle, the tracker of vp_stft_track_pitch, vp_stft_autotune, vp_stft_autotune_formant,
+ * vp_stft_track_harmony (the voices' note index and division use the refined pitch) and vp_stft_harmonize_key: VP_TRACK_INTEGER (the
+ * default: what those calls always did, bit for bit) or VP_TRACK_FINE; any other value is VP_ERR_INVALID_ARG.  Signatures, checks,
+ * messages, no allocation and no synchronisation are the same in both modes.
+ * vp_stft_track_pitch_fine always refines, whatever the mode, and also returns the refined period: d_period_fine, device double
+ * [n_streams][vp_stft_num_frames(p)].  Any of the three outputs may be NULL, not all three (VP_ERR_INVALID_ARG, "pitch tracker: period,
+ * refined period and ratio outputs are all null"); every other argument, check and message as vp_stft_track_pitch's. */
+#define VP_TRACK_INTEGER 0
+#define VP_TRACK_FINE 1
+int vp_stft_set_track_mode(vp_stft *p, int mode);
+int vp_stft_get_track_mode(const vp_stft *p);                /* the mode, or VP_ERR_INVALID_ARG on NULL */
+int vp_stft_track_pitch_fine(vp_stft *p, const float *d_in, double sample_rate, const int *d_key, int *d_period, double *d_period_fine,
+                             double *d_ratio, void *hip_stream);
 /* The message of the last tracker / autotune / formant / harmony call that failed on this handle ("" before any; the pointer is valid until the next call). */
 const char *vp_stft_last_error(const vp_stft *p);
 int vp_stft_is_fused(const vp_stft *p);                      /* 1 (every handle runs the fused kernel; kept for older callers) */
@@ -778,6 +800,20 @@ int vp_pv_tracker_process_blocks_voices_device(vp_pv_tracker *t, const float *d_
 int vp_hz_autoharm_blocks_device(vp_hz *h, vp_pv_tracker *t, const float *d_in, float *d_out, const int *d_key, const int *d_degree,
                                  const double *d_unvoiced, const double *d_gain, const double *d_dry, int *d_period, double *d_ratio,
                                  int n_blocks, void *hip_stream);
+/* The streaming FINE tracker (kernels vp_k_yin_track_stream_fine and vp_k_yin_track_voices_stream_fine): the raw decision per block is
+ * vp_stft_track_pitch_fine's for the same window, the follow stage is unchanged (it reads the int period only as the voiced flag).  The
+ * definition is tests/pv_track_fine_stream_reference.py.  vp_pv_tracker_set_mode(VP_TRACK_INTEGER, the default, or VP_TRACK_FINE;
+ * anything else VP_ERR_INVALID_ARG) selects the tracker of the five process calls above from the next call on; it touches no stream
+ * state (ring, counters, follow state), so a stream may change mode between two calls.
+ * vp_pv_tracker_process_blocks_fine_device is vp_pv_tracker_process_blocks_device with the fine tracker whatever the mode, and
+ * d_period_fine: device double [n_blocks][S] or NULL, the refined period of the raw decision before the follow stage -- 0.0 on unvoiced
+ * blocks and while the ring fills.  The checks are vp_pv_tracker_process_blocks_device's, unchanged: d_period and d_ratio may not both be
+ * NULL (VP_ERR_INVALID_ARG), also when d_period_fine is given -- the refined period is an addition to the call's tables, not a third
+ * alternative. */
+int vp_pv_tracker_set_mode(vp_pv_tracker *t, int mode);
+int vp_pv_tracker_get_mode(const vp_pv_tracker *t);                     /* the mode, or VP_ERR_INVALID_ARG on NULL */
+int vp_pv_tracker_process_blocks_fine_device(vp_pv_tracker *t, const float *d_in, const int *d_key, int *d_period, double *d_period_fine,
+                                             double *d_ratio, int n_blocks, void *hip_stream);
 
 const char *vp_error_string(int code);
 const char *vp_last_error(const vp_handle *h);

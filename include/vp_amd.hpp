@@ -382,6 +382,16 @@ public:
         detail::check(vp_pv_tracker_process_blocks_voices_device(t_, dIn, dKey, nVoices, dDegree, dUnvoiced, dPeriod, dRatio, nBlocks, hipStream),
                       "processBlocksVoices");
     }
+    // the fine tracker (VP_TRACK_FINE): the period refined below one sample, the note looked up on the refined pitch; from the next process
+    // call on, for the mono call, the voices and the composed calls; touches no stream state
+    void setFine(bool fine) { detail::check(vp_pv_tracker_set_mode(t_, fine ? VP_TRACK_FINE : VP_TRACK_INTEGER), "setFine"); }
+    bool fine() const { return vp_pv_tracker_get_mode(t_) == VP_TRACK_FINE; }
+    // processBlocksDevice with the fine tracker whatever the mode; dPeriodFine: device double [nBlocks][S] or null, the refined period of
+    // the raw decision (0.0 on unvoiced blocks and while the ring fills)
+    void processBlocksFine(const float *dIn, const int *dKey, int *dPeriod, double *dPeriodFine, double *dRatio, int nBlocks, void *hipStream = nullptr)
+    {
+        detail::check(vp_pv_tracker_process_blocks_fine_device(t_, dIn, dKey, dPeriod, dPeriodFine, dRatio, nBlocks, hipStream), "processBlocksFine");
+    }
     vp_pv_tracker *handle() const { return t_; }
 
 private:

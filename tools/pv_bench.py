@@ -13,6 +13,7 @@
     [VP_AMD_LIB=...] python tools/pv_bench.py --cross [--reps 7] [--out profiles/pv_cross_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --harm [--reps 7] [--out profiles/pv_harm_bench.txt]
     [VP_AMD_LIB=...] python tools/pv_bench.py --harmkey [--reps 7] [--out profiles/pv_harmkey_bench.txt]
+    [VP_AMD_LIB=...] python tools/pv_bench.py --track-fine [--reps 7] [--out profiles/pv_track_fine_bench.txt]
 
 --curve: the ratio-curve builds against their fixed-interval parents, in ONE process with the legs alternating (fixed, constant curve,
 "steps" curve, fixed, ...): 256 streams x 65 536 samples at 1024 points / hop 256 and 2048 points / hop 512 (vp_stft_pitch_shift against
@@ -79,6 +80,10 @@ vp_stft_track_harmony at V = 3 (the ratio over the tracker is the voice stage's 
 vp_stft_harmonize_key (against the sum of its two calls); three autotune(locked=True) calls and the mix (the composition: parallel
 harmony from three trackers).  Streaming, 16 blocks of 1024 per call: vp_hz_autoharm_blocks_device against the tracker's voices call
 plus the harmonizer call on handles of their own.  Every table a leg takes is on the device before the clock starts.
+
+--track-fine: the fine trackers (VP_TRACK_FINE) beside the integer ones, alternating in one process on one handle whose mode is switched
+between the legs: vp_stft_track_pitch at 256 streams x 65 536 samples, 1024 points / hop 256 (kernels vp_k_yin_track and
+vp_k_yin_track_fine), and vp_pv_tracker_process_blocks_device at 16 blocks of 1024 per call with full windows.
 """
 import argparse
 import os
@@ -411,6 +416,48 @@ def track_stream_legs(reps, emit):
         h.close()
 
 
+def track_fine_legs(reps, emit):
+    """The fine trackers beside the integer ones, the mode switched on one handle between the legs (the switch is a host-side store)."""
+    import numpy as np
+    import torch
+    from vocoderproject_amd import StftRoundTrip, StreamingPitchTracker
+    S, T, fs, F, hop, N, K = 256, 65536, 44100.0, 1024, 256, 1024, 16
+    rows = voiced_rows(S, T, fs)
+    x = torch.from_numpy(rows).cuda()
+    keys = torch.from_numpy((np.arange(S) % 13).astype(np.int32)).cuda()
+    st = StftRoundTrip(S, T, F, hop)
+    period, _ = st.track_pitch(x, fs, keys=keys)
+    torch.cuda.synchronize()
+    voiced = float((period > 0).float().mean())
+
+    def batch(fine):
+        st.set_track_mode(fine)
+        st.track_pitch(x, fs, keys=keys)
+    times = alternate({"vp_k_yin_track": lambda: batch(False), "vp_k_yin_track_fine": lambda: batch(True)}, reps, 20)
+    report(f"fine pitch tracker, {S} streams x {T} samples at {fs:g} Hz, F = {F}, hop = {hop}, {100.0 * voiced:.0f} % of the frames voiced",
+           times, S * st.n_frames, "vp_k_yin_track", emit)
+    m = {k: sum(v) / len(v) for k, v in times.items()}
+    emit(f"  per call: integer {m['vp_k_yin_track'] * 1e3:.3f} ms, fine {m['vp_k_yin_track_fine'] * 1e3:.3f} ms; fine / integer, frames per second: "
+         f"{m['vp_k_yin_track'] / m['vp_k_yin_track_fine']:.3f}")
+    st.close()
+    blocks = torch.from_numpy(np.ascontiguousarray(rows[:, :(K + 2) * N].reshape(S, K + 2, N).transpose(1, 0, 2))).cuda()
+    trk = StreamingPitchTracker(S, N, fs, F)
+    trk.process_device(blocks[:2], n_blocks=2, keys=keys)                    # two blocks of history: every decision has a full window
+    slab = blocks[2:].contiguous()
+
+    def stream(fine):
+        trk.set_fine(fine)
+        trk.process_device(slab, n_blocks=K, keys=keys)
+    times = alternate({"integer": lambda: stream(False), "fine": lambda: stream(True)}, reps, 500)
+    m = {k: sum(v) / len(v) for k, v in times.items()}
+    emit(f"streaming fine tracker, {S} streams, {K} blocks of {N} per call (tracker and follow kernel)")
+    for k, v in times.items():
+        r = [S * K / t / 1e6 for t in v]
+        emit(f"  {k:<28s} {sum(r) / len(r):8.2f} M decisions/s  (min {min(r):.2f}, max {max(r):.2f}, {len(r)} repetitions)  {m[k] * 1e6:8.1f} us per call")
+    emit(f"  fine / integer, decisions per second: {m['integer'] / m['fine']:.3f}")
+    trk.close()
+
+
 def saw_rows(S, T, fs, seed=12):
     """--cross's carriers: one sawtooth per stream, 55 .. 220 Hz; float32 [S][T]."""
     import numpy as np
@@ -594,6 +641,7 @@ def main():
     ap.add_argument("--stretch", action="store_true", help="the time-stretch legs instead of the fixed intervals")
     ap.add_argument("--track", action="store_true", help="the pitch-tracker legs instead of the fixed intervals")
     ap.add_argument("--track-stream", action="store_true", help="the streaming-tracker legs instead of the fixed intervals")
+    ap.add_argument("--track-fine", action="store_true", help="the fine trackers beside the integer ones instead of the fixed intervals")
     ap.add_argument("--locked", action="store_true", help="the peak-locked legs instead of the fixed intervals")
     ap.add_argument("--locked-subbin", action="store_true", help="the sub-bin peak-locked legs instead of the fixed intervals")
     ap.add_argument("--stretch-locked", action="store_true", help="the locked time-stretch legs instead of the fixed intervals")
@@ -604,7 +652,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="--curve / --stretch / --track: also write the report to this file")
     a = ap.parse_args()
-    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.locked_subbin and not a.stretch_locked and not a.transient and not a.cross and not a.harm and not a.harmkey:
+    if not a.curve and not a.stretch and not a.track and not a.track_stream and not a.locked and not a.locked_subbin and not a.stretch_locked and not a.transient and not a.cross and not a.harm and not a.harmkey and not a.track_fine:
         return fixed_intervals()
     lines = []
 
@@ -622,6 +670,9 @@ def main():
     if a.track_stream:
         track_stream_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_yin_track", "vp_k_yin_track_stream", "vp_k_track_follow", "vp_k_track_reset", "vp_k_pv_stream_curve"))
+    if a.track_fine:
+        track_fine_legs(max(5, a.reps), emit)
+        resource_listing(emit, ("vp_k_yin_track", "vp_k_yin_track_fine", "vp_k_yin_track_stream", "vp_k_yin_track_stream_fine"))
     if a.locked:
         locked_legs(max(5, a.reps), emit)
         resource_listing(emit, ("vp_k_stft_pv_curve", "vp_k_stft_pv_lock", "vp_k_pv_stream_curve", "vp_k_pv_stream_lock"))

@@ -1890,6 +1890,7 @@ struct vp_stft {
     int *notesN = nullptr;            // [13]
     double *harm = nullptr;           // [13][VP_NOTES_STRIDE] the harmony tables of vp_stft_track_harmony (fMin 25 / fMax 3200), then harmOff [13]
     int *harmOff = nullptr;           // (into harm's allocation)
+    int trackMode = VP_TRACK_INTEGER; // vp_stft_set_track_mode: which tracker the calls that track launch
     std::string lastError;            // vp_stft_last_error
 };
 
@@ -2305,11 +2306,16 @@ extern "C" int vp_track_tau_max(double sample_rate)
 extern "C" const char *vp_stft_last_error(const vp_stft *p) { return p ? p->lastError.c_str() : ""; }
 
 // every argument of a tracker call, checked before the device is touched
-static int track_check(vp_stft *p, const float *d_in, double fs, const int *d_period, const double *d_ratio)
+// (fine_entry: vp_stft_track_pitch_fine, whose third output d_period_fine counts as an output)
+static int track_check(vp_stft *p, const float *d_in, double fs, const int *d_period, const double *d_ratio, bool fine_entry = false,
+                       const double *d_period_fine = nullptr)
 {
     if (!p) return VP_ERR_INVALID_ARG;
     if (!d_in) { p->lastError = "pitch tracker: null input"; return VP_ERR_INVALID_ARG; }
-    if (!d_period && !d_ratio) { p->lastError = "pitch tracker: period and ratio outputs are both null"; return VP_ERR_INVALID_ARG; }
+    if (!d_period && !d_ratio && !d_period_fine) {
+        p->lastError = fine_entry ? "pitch tracker: period, refined period and ratio outputs are all null" : "pitch tracker: period and ratio outputs are both null";
+        return VP_ERR_INVALID_ARG;
+    }
     const int tauMax = vp_track_tau_max(fs);
     if (tauMax < 0) { p->lastError = "pitch tracker: sample rate outside 8000 .. 51200 Hz"; return VP_ERR_INVALID_ARG; }
     if (p->T < p->F + tauMax) {
@@ -2319,7 +2325,9 @@ static int track_check(vp_stft *p, const float *d_in, double fs, const int *d_pe
     return VP_OK;
 }
 
-static int track_launch(vp_stft *p, const float *d_in, double fs, const int *d_key, int *d_period, double *d_ratio, hipStream_t st)
+// fine: the fine tracker (the handle's mode, or vp_stft_track_pitch_fine, which also passes the table of refined periods)
+static int track_launch(vp_stft *p, const float *d_in, double fs, const int *d_key, int *d_period, double *d_ratio, hipStream_t st, bool fine,
+                        double *d_period_fine = nullptr)
 {
     VpTrackArgs a;
     memset(&a, 0, sizeof a);
@@ -2327,7 +2335,7 @@ static int track_launch(vp_stft *p, const float *d_in, double fs, const int *d_k
     a.fs = fs; a.S = p->S; a.T = p->T; a.F = p->F; a.hop = p->hop; a.nFrames = p->nFrames;
     a.tauMax = vp_track_tau_max(fs);
     a.tau0 = (int)std::floor(fs / VP_TRACK_FMAX);                                               // PitchProcess.cpp:429
-    if (vp_track_launch(a, st) != hipSuccess) { p->lastError = "pitch tracker: kernel launch failed"; return VP_ERR_HIP; }
+    if ((fine ? vp_track_fine_launch(a, d_period_fine, st) : vp_track_launch(a, st)) != hipSuccess) { p->lastError = "pitch tracker: kernel launch failed"; return VP_ERR_HIP; }
     return VP_OK;
 }
 
@@ -2336,7 +2344,26 @@ extern "C" int vp_stft_track_pitch(vp_stft *p, const float *d_in, double sample_
     const int rc = track_check(p, d_in, sample_rate, d_period, d_ratio);
     if (rc) return rc;
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return track_launch(p, d_in, sample_rate, d_key, d_period, d_ratio, (hipStream_t)hip_stream);
+    return track_launch(p, d_in, sample_rate, d_key, d_period, d_ratio, (hipStream_t)hip_stream, p->trackMode == VP_TRACK_FINE);
+}
+
+extern "C" int vp_stft_set_track_mode(vp_stft *p, int mode)
+{
+    if (!p || (mode != VP_TRACK_INTEGER && mode != VP_TRACK_FINE)) return VP_ERR_INVALID_ARG;
+    p->trackMode = mode;
+    return VP_OK;
+}
+
+extern "C" int vp_stft_get_track_mode(const vp_stft *p) { return p ? p->trackMode : VP_ERR_INVALID_ARG; }
+
+// vp_stft_track_pitch with the fine tracker whatever the mode, and the table of refined periods
+extern "C" int vp_stft_track_pitch_fine(vp_stft *p, const float *d_in, double sample_rate, const int *d_key, int *d_period, double *d_period_fine,
+                                        double *d_ratio, void *hip_stream)
+{
+    const int rc = track_check(p, d_in, sample_rate, d_period, d_ratio, true, d_period_fine);
+    if (rc) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return track_launch(p, d_in, sample_rate, d_key, d_period, d_ratio, (hipStream_t)hip_stream, true, d_period_fine);
 }
 
 // ---- key-aware voices (vp_k_yin_track_voices): the tracker's decision, then n_voices ratios at scale degrees of the note it chose ------
@@ -2358,7 +2385,7 @@ static int harmony_launch(vp_stft *p, const float *d_in, double fs, const int *d
     a.tauMax = vp_track_tau_max(fs);
     a.tau0 = (int)std::floor(fs / VP_TRACK_FMAX);                                               // PitchProcess.cpp:429
     const VpTrackVoices v = {p->harm, p->harmOff, d_degree, d_unvoiced, n_voices};
-    if (vp_track_voices_launch(a, v, st) != hipSuccess) { p->lastError = "track harmony: kernel launch failed"; return VP_ERR_HIP; }
+    if ((p->trackMode == VP_TRACK_FINE ? vp_track_voices_fine_launch(a, v, st) : vp_track_voices_launch(a, v, st)) != hipSuccess) { p->lastError = "track harmony: kernel launch failed"; return VP_ERR_HIP; }
     return VP_OK;
 }
 
@@ -2401,7 +2428,7 @@ static int stft_autotune(vp_stft *p, const float *d_in, float *d_out, double fs,
     if (!rc) rc = stft_check(p, "autotune", true, nullptr, &m);
     if (rc) return rc;
     if (hipSetDevice(p->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    rc = track_launch(p, d_in, fs, d_key, d_period, d_ratio, (hipStream_t)hip_stream);
+    rc = track_launch(p, d_in, fs, d_key, d_period, d_ratio, (hipStream_t)hip_stream, p->trackMode == VP_TRACK_FINE);
     return rc ? rc : stft_fused(p, d_in, d_out, nullptr, &m, (hipStream_t)hip_stream);
 }
 
@@ -2761,6 +2788,7 @@ struct vp_pv_tracker {
     double *notes = nullptr; int *notesN = nullptr;
     long nAllocs = 0;
     int hold = 0; double glide = 1.0;           // what the next call uses
+    int mode = VP_TRACK_INTEGER;                // vp_pv_tracker_set_mode: which tracker the next call launches
     bool allReset = false;
     std::vector<char> resetPend;                // [S]
 };
@@ -2832,6 +2860,15 @@ extern "C" int vp_pv_tracker_set_follow(vp_pv_tracker *t, int hold_blocks, doubl
     return VP_OK;
 }
 
+extern "C" int vp_pv_tracker_set_mode(vp_pv_tracker *t, int mode)
+{
+    if (!t || (mode != VP_TRACK_INTEGER && mode != VP_TRACK_FINE)) return VP_ERR_INVALID_ARG;
+    t->mode = mode;
+    return VP_OK;
+}
+
+extern "C" int vp_pv_tracker_get_mode(const vp_pv_tracker *t) { return t ? t->mode : VP_ERR_INVALID_ARG; }
+
 // every argument of a streaming tracker call, checked before the device is touched
 static int trks_check(const vp_pv_tracker *t, const float *d_in, const int *d_period, const double *d_ratio, int n_blocks)
 {
@@ -2842,7 +2879,8 @@ static int trks_check(const vp_pv_tracker *t, const float *d_in, const int *d_pe
 // the pending resets travel in the arguments of update launches in front of the call: ordered on the caller's stream, no host memory
 // the device reads later, no allocation.  An output the caller left out is replaced by the handle's scratch, TRKS_SCRATCH_BLOCKS blocks
 // per launch pair (how blocks are grouped into launches does not change a bit).  A reset clears the mono follow state and the voices'.
-// vc: the voices call (ratio tables [n_blocks][S][V], the voices' kernels and follow state); nullptr: the mono call
+// vc: the voices call (ratio tables [n_blocks][S][V], the voices' kernels and follow state); nullptr: the mono call.  fine: the fine
+// trackers in front of the same follow kernels; d_period_fine: the mono fine call's table of refined periods [n_blocks][S], or nullptr
 static bool trks_reset_launch(const vp_pv_tracker *t, const VpTrackUpdArgs &u, hipStream_t st)
 {
     VpTrackUpdArgs v = u;
@@ -2851,7 +2889,7 @@ static bool trks_reset_launch(const vp_pv_tracker *t, const VpTrackUpdArgs &u, h
 }
 
 static int trks_run(vp_pv_tracker *t, const float *d_in, const int *d_key, int *d_period, double *d_ratio, int n_blocks, hipStream_t st,
-                    const VpTrackVoices *vc = nullptr)
+                    const VpTrackVoices *vc = nullptr, bool fine = false, double *d_period_fine = nullptr)
 {
     VpTrackUpdArgs u;
     memset(&u, 0, sizeof u);
@@ -2894,8 +2932,9 @@ static int trks_run(vp_pv_tracker *t, const float *d_in, const int *d_key, int *
         a.ratio = f.ratio = fv.ratio = d_ratio ? d_ratio + row * V : t->scrRatio;
         f.period = fv.period = a.period;
         a.nBlocks = f.nBlocks = fv.nBlocks = nb;
-        if (vc ? vp_track_voices_stream_launch(a, *vc, st) != hipSuccess || vp_track_follow_voices_launch(fv, st) != hipSuccess
-               : vp_track_stream_launch(a, st) != hipSuccess || vp_track_follow_launch(f, st) != hipSuccess) return VP_ERR_HIP;
+        const hipError_t raw = vc ? (fine ? vp_track_voices_stream_fine_launch(a, *vc, st) : vp_track_voices_stream_launch(a, *vc, st))
+                                  : (fine ? vp_track_stream_fine_launch(a, d_period_fine ? d_period_fine + row : nullptr, st) : vp_track_stream_launch(a, st));
+        if (raw != hipSuccess || (vc ? vp_track_follow_voices_launch(fv, st) : vp_track_follow_launch(f, st)) != hipSuccess) return VP_ERR_HIP;
     }
     return VP_OK;
 }
@@ -2906,7 +2945,17 @@ extern "C" int vp_pv_tracker_process_blocks_device(vp_pv_tracker *t, const float
     const int rc = trks_check(t, d_in, d_period, d_ratio, n_blocks);
     if (rc) return rc;
     if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    return trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
+    return trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream, nullptr, t->mode == VP_TRACK_FINE);
+}
+
+// vp_pv_tracker_process_blocks_device with the fine tracker whatever the mode, and the table of refined periods
+extern "C" int vp_pv_tracker_process_blocks_fine_device(vp_pv_tracker *t, const float *d_in, const int *d_key, int *d_period, double *d_period_fine,
+                                                        double *d_ratio, int n_blocks, void *hip_stream)
+{
+    const int rc = trks_check(t, d_in, d_period, d_ratio, n_blocks);
+    if (rc) return rc;
+    if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
+    return trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream, nullptr, true, d_period_fine);
 }
 
 // the voices call: vp_pv_tracker_process_blocks_device's arguments and checks, then the voice count and the degree table
@@ -2925,7 +2974,7 @@ extern "C" int vp_pv_tracker_process_blocks_voices_device(vp_pv_tracker *t, cons
     if (rc) return rc;
     if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     const VpTrackVoices v = {t->harm, t->harmOff, d_degree, d_unvoiced, n_voices};
-    return trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream, &v);
+    return trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream, &v, t->mode == VP_TRACK_FINE);
 }
 
 // the voices call with the harmonizer handle's voice count, then vp_hz_process_blocks_device along its table, on the same stream.  The
@@ -2940,7 +2989,7 @@ extern "C" int vp_hz_autoharm_blocks_device(vp_hz *h, vp_pv_tracker *t, const fl
     if (h->S != t->S || h->N != t->N || h->device != t->device) return VP_ERR_GEOMETRY;
     if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
     const VpTrackVoices v = {t->harm, t->harmOff, d_degree, d_unvoiced, h->V};
-    rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream, &v);
+    rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream, &v, t->mode == VP_TRACK_FINE);
     return rc ? rc : vp_hz_process_blocks_device(h, d_in, d_out, d_ratio, d_gain, d_dry, n_blocks, hip_stream);
 }
 
@@ -2954,7 +3003,7 @@ static int pv_autotune(vp_pv *p, vp_pv_tracker *t, const float *d_in, float *d_o
     if (rc) return rc;
     if (p->S != t->S || p->N != t->N || p->device != t->device) return VP_ERR_GEOMETRY;
     if (hipSetDevice(t->device) != hipSuccess) return VP_ERR_NO_DEVICE;
-    rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream);
+    rc = trks_run(t, d_in, d_key, d_period, d_ratio, n_blocks, (hipStream_t)hip_stream, nullptr, t->mode == VP_TRACK_FINE);
     return rc ? rc : pv_run(p, d_in, d_out, n_blocks, (hipStream_t)hip_stream, m);
 }
 

@@ -107,3 +107,12 @@ hipError_t vp_track_reset_voices_launch(const VpTrackUpdArgs &a, hipStream_t st)
 hipError_t vp_track_stream_launch(const VpTrackStreamArgs &a, hipStream_t st);
 hipError_t vp_track_follow_launch(const VpTrackFollowArgs &a, hipStream_t st);
 hipError_t vp_track_reset_launch(const VpTrackUpdArgs &a, hipStream_t st);
+
+// ---- fine (sub-sample) trackers (csrc/vp_track_fine_kernels.inc): the same decisions, the period refined by a parabola through the
+// normalised function's minimum and the note looked up on the refined pitch.  Arguments, grids and LDS as the integer launchers';
+// periodFine ([S][nFrames] for the batch kernel, [nBlocks][S] for the streaming one) receives the refined period, or is nullptr.  The
+// streaming launches are followed by vp_track_follow_launch / vp_track_follow_voices_launch as the integer ones are
+hipError_t vp_track_fine_launch(const VpTrackArgs &a, double *periodFine, hipStream_t st);
+hipError_t vp_track_voices_fine_launch(const VpTrackArgs &a, const VpTrackVoices &v, hipStream_t st);
+hipError_t vp_track_stream_fine_launch(const VpTrackStreamArgs &a, double *periodFine, hipStream_t st);
+hipError_t vp_track_voices_stream_fine_launch(const VpTrackStreamArgs &a, const VpTrackVoices &v, hipStream_t st);

@@ -237,3 +237,6 @@ hipError_t vp_track_reset_launch(const VpTrackUpdArgs &a, hipStream_t st)
 
 // ---- key-aware voices (vp_stft_track_harmony, vp_pv_tracker_process_blocks_voices_device): the kernels above with the voice stage ------
 #include "vp_track_voices_kernels.inc"
+
+// ---- fine (sub-sample) trackers (VP_TRACK_FINE, vp_stft_track_pitch_fine): the kernels above with the parabolic stage -------------------
+#include "vp_track_fine_kernels.inc"

@@ -2,6 +2,8 @@
 // (csrc/vp_track_voices_kernels.inc): one pitch decision becomes V in-key ratios.  The definition is tests/pv_harmkey_reference.py.  In scope: lane, s,
 // tau (uniform), nf0, nf1, notesN, A.fs, the harmony table of the stream's key hf0 / hf1 (entry lane, entry 64 + lane), hOff, and VC
 // (VpTrackVoices).  Leaves: vr, in lane v < V the ratio of voice v.
+// Also included by the fine trackers (csrc/vp_track_fine_kernels.inc) in a block where `tau` names the REFINED period, a double: this text
+// may use tau only in the voiced test `tau > 0` and as the divisor of A.fs -- an integer use of it would change meaning there.
     double vr = 1.0;
     int deg = 0;
     if (lane < VC.V) {

@@ -17,7 +17,7 @@ There is no CPU path here either: without a GPU the processor raises.
     python -m vocoderproject_amd.offline stretch a.wav b.wav --stretch 1.5 [--shift 3] [--locked] --out-dir out/   (time stretch, one-shot phase vocoder)
     python -m vocoderproject_amd.offline stretch a.wav --stretch 2 --locked --transients [THR] [--span K] --out-dir out/   (attacks kept: no stretch across an onset, phases restart at it)
     python -m vocoderproject_amd.offline pvshift a.wav --shift -12 --locked --subbin --out-dir out/   (peak locking with sub-bin region offsets)
-    python -m vocoderproject_amd.offline pvtune a.wav b.wav --key 0 --out-dir out/ [--track-csv]        (pitch tracker + phase-vocoder correction)
+    python -m vocoderproject_amd.offline pvtune a.wav b.wav --key 0 --out-dir out/ [--track-csv] [--fine]   (pitch tracker + phase-vocoder correction; --fine: sub-sample periods)
     python -m vocoderproject_amd.offline pvtune a.wav --stream [--block 256 --hold 8 --glide 0.5] --out-dir out/   (... block by block: the streaming tracker)
     python -m vocoderproject_amd.offline pvcross voice.wav [more.wav] --carrier synth.wav [--depth D] [--lifter N] [--stream --block N] [--hop H] --out-dir out/   (STFT cross-synthesis)
     python -m vocoderproject_amd.offline harmonize a.wav [b.wav] --voices 4,7,-5 [--gains 1,1,0.7] [--dry 1] [--stream --block N] [--hop H] --out-dir out/   (peak-locked harmonizer)
@@ -475,14 +475,21 @@ class _AutotuneRunner:
     """StftRoundTrip.autotune from host arrays: x float32 [S][T], keys [S] -> (y float32 [S][T], period int32 [S][nF], ratio float64 [S][nF])."""
 
     def __init__(self, F, hop, device):
-        self.F, self.hop, self.device = int(F), int(hop), device
+        self.F, self.hop, self.device, self.fine = int(F), int(hop), device, False
+
+    def set_fine(self, fine):
+        """The fine tracker (StftRoundTrip.set_track_mode); run then also returns the refined periods float64 [S][nF]."""
+        self.fine = bool(fine)
 
     def run(self, x, fs, keys, formant=None, lifter=32, locked=False, subbin=False):
         def call(st, d_in, d_out):
-            return st.autotune(d_in, d_out, float(fs), keys=[int(k) for k in keys], formant_semitones=formant, lifter=int(lifter),
-                               **_mode_kw(None, 0, locked, subbin=subbin))
-        y, (period, ratio) = _one_shot(x, x.shape[1], self.F, self.hop, self.device, call)
-        return y, period.cpu().numpy(), ratio.cpu().numpy()
+            if self.fine:
+                st.set_track_mode(True)
+            res = st.autotune(d_in, d_out, float(fs), keys=[int(k) for k in keys], formant_semitones=formant, lifter=int(lifter),
+                              **_mode_kw(None, 0, locked, subbin=subbin))
+            return res + (st.track_pitch(d_in, float(fs), keys=[int(k) for k in keys], with_fine_period=True)[2],) if self.fine else res
+        y, tables = _one_shot(x, x.shape[1], self.F, self.hop, self.device, call)
+        return (y,) + tuple(t.cpu().numpy() for t in tables)
 
 
 def tune_length(max_len, fs, F, hop):
@@ -501,15 +508,20 @@ def _check_tune(voices, fs, key, formant, lifter):
     return keys
 
 
-def _tune(p, voices, lens, T, fs, keys, kw, offset, with_track):
-    """Both pvtune flows from the packed call on: p.run(x, fs, keys, **kw) -> the recordings from sample `offset` on, with the track or not."""
-    y, period, ratio = p.run(_pack_mono(voices, lens, T), float(fs), keys, **kw)
+def _tune(p, voices, lens, T, fs, keys, kw, offset, with_track, fine=False):
+    """Both pvtune flows from the packed call on: p.run(x, fs, keys, **kw) -> the recordings from sample `offset` on, with the track or not.
+    fine: p.set_fine(True) first; run then returns the refined periods as a fourth item, and so does the track."""
+    if fine:
+        p.set_fine(True)
+    y, *track = p.run(_pack_mono(voices, lens, T), float(fs), keys, **kw)
+    if len(track) != (3 if fine else 2):
+        raise ValueError("pvtune: the processor's run returned %d tables where %d were expected" % (len(track), 3 if fine else 2))
     outs = _both_channels(y, lens, offset)
-    return (outs, period, ratio) if with_track else outs
+    return (outs,) + tuple(track) if with_track else outs
 
 
 def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, with_track=False, formant=None, lifter=32, locked=False,
-                subbin=False):
+                subbin=False, fine=False):
     """A batch of recordings through the pitch tracker and the one-shot phase vocoder (StftRoundTrip.autotune: one stream per recording):
     every frame is moved onto the nearest note of its recording's key.  key: Notes::key 0..12 (12 = chromatic), one value or one per
     recording.  The recordings are zero-padded to a common length (tune_length).  Returns float32 [2][len] per recording (the corrected
@@ -519,7 +531,8 @@ def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, w
     singer's formants where they were; lifter: the cepstral lifter, 4 .. 64 samples; run then also receives formant and lifter.
     locked: the correction runs through the peak-locked call (StftRoundTrip.autotune(locked=True); 1024-point frames, not together with
     formant); run then also receives locked=True.  subbin (with locked only): the locked call with sub-bin region offsets; run then also
-    receives subbin=True."""
+    receives subbin=True.  fine: the fine tracker (StftRoundTrip.set_track_mode: the period refined below one sample, the note looked up
+    on the refined pitch); the processor's set_fine(True) is called first, and with_track also returns the refined periods float64 [S][nF]."""
     keys = _check_tune(voices, fs, key, formant, lifter)
     if formant is not None and int(F) != 1024:
         raise ValueError("pvtune --formant: 1024-point frames expected (the formant kernels are not built for 2048)")
@@ -527,7 +540,7 @@ def pv_autotune(voices, fs, key=12, F=1024, hop=256, device=0, processor=None, w
     _check_subbin(subbin, locked)
     lens = _lengths(voices)
     p = processor if processor is not None else _AutotuneRunner(F, hop, device)
-    return _tune(p, voices, lens, tune_length(max(lens), fs, F, hop), fs, keys, _mode_kw(formant, lifter, locked, subbin=subbin), 0, with_track)
+    return _tune(p, voices, lens, tune_length(max(lens), fs, F, hop), fs, keys, _mode_kw(formant, lifter, locked, subbin=subbin), 0, with_track, fine)
 
 
 class _StreamTuneRunner:
@@ -536,6 +549,17 @@ class _StreamTuneRunner:
 
     def __init__(self, N, hop, F, hold, glide, device, blocks_per_call=16):
         self.N, self.hop, self.F, self.hold, self.glide, self.device, self.k = int(N), int(hop), int(F), int(hold), float(glide), device, int(blocks_per_call)
+        self.fine = False
+
+    def set_fine(self, fine):
+        """The fine tracker (StreamingPitchTracker.set_fine); run then goes through the composed call's two parts, whose bits it has, and
+        also returns the raw decisions' refined periods float64 [n][S]."""
+        self.fine = bool(fine)
+
+    def _fine_call(self, pv, trk, d_in, d_out, n, keys, formant, lifter, lk):
+        period, ratio, fine = trk.process_device(d_in, n_blocks=n, keys=keys, with_fine_period=True)
+        pv.process_device(d_in, d_out, n_blocks=n, d_ratio=ratio, **({} if formant is None else {"formant_semitones": formant, "lifter": lifter}), **lk)
+        return period, ratio, fine
 
     def run(self, x, fs, keys, formant=None, lifter=32, locked=False, subbin=False):
         import torch
@@ -549,12 +573,17 @@ class _StreamTuneRunner:
         try:
             d_in = torch.from_numpy(np.ascontiguousarray(x.reshape(S, nb, N).transpose(1, 0, 2), np.float32)).to(dev)
             d_out = torch.empty_like(d_in)
-            tables = [pv.autotune_device(trk, d_in[b:b + self.k], d_out[b:b + self.k], n_blocks=min(self.k, nb - b), keys=[int(k) for k in keys],
-                                         formant_semitones=formant, lifter=int(lifter), **lk)
-                      for b in range(0, nb, self.k)]
+            if self.fine:
+                trk.set_fine(True)
+                tables = [self._fine_call(pv, trk, d_in[b:b + self.k], d_out[b:b + self.k], min(self.k, nb - b), [int(k) for k in keys], formant, int(lifter), lk)
+                          for b in range(0, nb, self.k)]
+            else:
+                tables = [pv.autotune_device(trk, d_in[b:b + self.k], d_out[b:b + self.k], n_blocks=min(self.k, nb - b), keys=[int(k) for k in keys],
+                                             formant_semitones=formant, lifter=int(lifter), **lk)
+                          for b in range(0, nb, self.k)]
             torch.cuda.synchronize(dev)
             y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(S, nb * N)
-            return np.ascontiguousarray(y), torch.cat([p for p, _ in tables]).cpu().numpy(), torch.cat([r for _, r in tables]).cpu().numpy()
+            return (np.ascontiguousarray(y),) + tuple(torch.cat([t[i] for t in tables]).cpu().numpy() for i in range(len(tables[0])))
         finally:
             trk.close()
             pv.close()
@@ -569,7 +598,7 @@ def stream_tune_length(max_len, N, hop):
 
 
 def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glide=1.0, device=0, processor=None, with_track=False, formant=None,
-                       lifter=32, locked=False, subbin=False):
+                       lifter=32, locked=False, subbin=False, fine=False):
     """pv_autotune block by block, as a live caller would run it: the streaming tracker (StreamingPitchTracker, analysis length F) decides
     one ratio per block of N samples from the audio received so far, holds the last voiced ratio for `hold` unvoiced blocks and moves the
     fraction `glide` of the way to its target per block; the streaming phase vocoder (1024-point frames) shifts along that table.  The
@@ -577,7 +606,8 @@ def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glid
     [2][len] per recording; with_track: also period int32 [n_blocks][S] and ratio float64 [n_blocks][S] of the padded batch.  A decision
     costs the same at every N: N = 64 costs 16 times as much per second of audio as N = 1024.  `processor` (tests): an object with
     run(x, fs, keys) to use instead of the GPU.  formant, lifter, locked, subbin: as pv_autotune's (the shifter's frames are 1024 points
-    whatever F)."""
+    whatever F).  fine: as pv_autotune's (StreamingPitchTracker.set_fine); with_track then also returns the raw decisions' refined
+    periods float64 [n_blocks][S], which the follow stage neither holds nor glides."""
     keys = _check_tune(voices, fs, key, formant, lifter)
     _check_locked(locked, formant)
     _check_subbin(subbin, locked)
@@ -588,7 +618,7 @@ def pv_autotune_stream(voices, fs, key=12, N=1024, hop=256, F=1024, hold=0, glid
     lens = _lengths(voices)
     T, lat = stream_tune_length(max(lens), N, hop)
     p = processor if processor is not None else _StreamTuneRunner(N, hop, F, hold, glide, device)
-    return _tune(p, voices, lens, T, fs, keys, _mode_kw(formant, lifter, locked, subbin=subbin), lat, with_track)
+    return _tune(p, voices, lens, T, fs, keys, _mode_kw(formant, lifter, locked, subbin=subbin), lat, with_track, fine)
 
 
 class _CrossRunner:
@@ -715,13 +745,20 @@ class _HarmKeyRunner:
     (float32 [S][T], period int32 [S][nF], ratio float64 [S][V][nF])."""
 
     def __init__(self, hop, device):
-        self.hop, self.device = int(hop), device
+        self.hop, self.device, self.fine = int(hop), device, False
+
+    def set_fine(self, fine):
+        """The fine tracker (StftRoundTrip.set_track_mode); run then also returns the refined periods float64 [S][nF]."""
+        self.fine = bool(fine)
 
     def run(self, x, fs, keys, degrees, gains, dry):
         def call(st, d_in, d_out):
-            return st.harmonize(d_in, d_out, degrees=degrees, sample_rate=float(fs), keys=[int(k) for k in keys], gains=gains, dry=dry)
-        y, (period, ratio) = _one_shot(x, x.shape[1], 1024, self.hop, self.device, call)
-        return y, period.cpu().numpy(), ratio.cpu().numpy()
+            if self.fine:
+                st.set_track_mode(True)
+            res = st.harmonize(d_in, d_out, degrees=degrees, sample_rate=float(fs), keys=[int(k) for k in keys], gains=gains, dry=dry)
+            return res + (st.track_pitch(d_in, float(fs), keys=[int(k) for k in keys], with_fine_period=True)[2],) if self.fine else res
+        y, tables = _one_shot(x, x.shape[1], 1024, self.hop, self.device, call)
+        return (y,) + tuple(t.cpu().numpy() for t in tables)
 
 
 class _StreamHarmKeyRunner:
@@ -730,6 +767,12 @@ class _StreamHarmKeyRunner:
 
     def __init__(self, N, hop, hold, glide, device, blocks_per_call=16):
         self.N, self.hop, self.hold, self.glide, self.device, self.k = int(N), int(hop), int(hold), float(glide), device, int(blocks_per_call)
+        self.fine = False
+
+    def set_fine(self, fine):
+        """The fine tracker (StreamingPitchTracker.set_fine); run then also returns the raw decisions' refined periods float64 [n][S], from
+        a twin tracker fed the same blocks through process_device(with_fine_period=True)."""
+        self.fine = bool(fine)
 
     def run(self, x, fs, keys, degrees, gains, dry):
         import torch
@@ -739,21 +782,30 @@ class _StreamHarmKeyRunner:
         dev = torch.device("cuda", self.device)
         hz = HarmonizerStream(S, N, degrees.shape[1], hop=self.hop, device=self.device)
         trk = StreamingPitchTracker(S, N, float(fs), hold_blocks=self.hold, glide=self.glide, device=self.device)
+        twin = None
         try:
             d_in = torch.from_numpy(np.ascontiguousarray(x.reshape(S, nb, N).transpose(1, 0, 2), np.float32)).to(dev)
             d_out = torch.empty_like(d_in)
+            if self.fine:
+                twin = StreamingPitchTracker(S, N, float(fs), device=self.device)
+                trk.set_fine(True)
             tables = [hz.autoharm_device(trk, d_in[b:b + self.k], d_out[b:b + self.k], degrees, n_blocks=min(self.k, nb - b), keys=[int(k) for k in keys],
                                          gains=gains, dry=dry) for b in range(0, nb, self.k)]
+            fine = [twin.process_device(d_in[b:b + self.k], n_blocks=min(self.k, nb - b), keys=[int(k) for k in keys], with_fine_period=True)[2]
+                    for b in range(0, nb, self.k)] if self.fine else None
             torch.cuda.synchronize(dev)
             y = d_out.cpu().numpy().transpose(1, 0, 2).reshape(S, nb * N)
-            return np.ascontiguousarray(y), torch.cat([p for p, _ in tables]).cpu().numpy(), torch.cat([r for _, r in tables]).cpu().numpy()
+            out = (np.ascontiguousarray(y), torch.cat([p for p, _ in tables]).cpu().numpy(), torch.cat([r for _, r in tables]).cpu().numpy())
+            return out + (torch.cat(fine).cpu().numpy(),) if self.fine else out
         finally:
+            if twin is not None:
+                twin.close()
             trk.close()
             hz.close()
 
 
 def pv_harmonize_key(voices, fs, degrees, key=12, gains=None, dry=1.0, hop=256, N=1024, stream=False, hold=0, glide=1.0, device=0, processor=None,
-                     with_track=False):
+                     with_track=False, fine=False):
     """The KEY-AWARE harmonizer on a batch (one stream per recording): beside every recording, `dry` times itself, V = 1 .. 4 peak-locked
     voices at `degrees` (integers within +-12) steps of the key's note table from the note the pitch tracker chose -- scale degrees in a
     scale key (2 is a third above, 4 a fifth), semitones in the chromatic key 12.  Unvoiced frames take each voice's nominal interval.
@@ -761,7 +813,10 @@ def pv_harmonize_key(voices, fs, degrees, key=12, gains=None, dry=1.0, hop=256, 
     recordings padded as pv_autotune pads them; stream: block by block through HarmonizerStream.autoharm_device with a
     StreamingPitchTracker (hold, glide: its follow stage), the harmonizer's latency taken off.  Returns float32 [2][len] per recording;
     with_track: also period and ratio of the padded batch ([S][nF] and [S][V][nF]; stream: [n_blocks][S] and [n_blocks][S][V]).
-    `processor` (tests): an object with run(x, fs, keys, degrees [S][V], gains [S][V], dry [S]) -> (y, period, ratio) instead of the GPU."""
+    `processor` (tests): an object with run(x, fs, keys, degrees [S][V], gains [S][V], dry [S]) -> (y, period, ratio) instead of the GPU.
+    fine: the fine tracker (the period refined below one sample; every voice's note index and ratio come from the refined pitch); the
+    processor's set_fine(True) is called first, its run returns the refined periods ([S][nF]; stream: [n_blocks][S]) as a fourth item,
+    and so does with_track."""
     S = _batch_size(voices)
     many = isinstance(degrees, (list, tuple)) or (isinstance(degrees, np.ndarray) and degrees.ndim == 1)
     dg = list(degrees) if many else []
@@ -789,20 +844,26 @@ def pv_harmonize_key(voices, fs, degrees, key=12, gains=None, dry=1.0, hop=256, 
     else:
         T, lat = tune_length(max(lens), fs, 1024, hop), 0
         p = processor if processor is not None else _HarmKeyRunner(hop, device)
-    y, period, ratio = p.run(_pack_mono(voices, lens, T), float(fs), keys, dtab, gtab, per)
+    if fine:
+        p.set_fine(True)
+    y, *track = p.run(_pack_mono(voices, lens, T), float(fs), keys, dtab, gtab, per)
+    if len(track) != (3 if fine else 2):
+        raise ValueError("harmonize --degrees: the processor's run returned %d tables where %d were expected" % (len(track), 3 if fine else 2))
     outs = _both_channels(y, lens, lat)
-    return (outs, period, ratio) if with_track else outs
+    return (outs,) + tuple(track) if with_track else outs
 
 
-def write_track_csv(path, fs, hop, period, ratio, n_samples=None):
+def write_track_csv(path, fs, hop, period, ratio, n_samples=None, period_fine=None):
     """One recording's track: a line per frame with its start time in seconds, the period in samples (0 = unvoiced) and the correction in
-    semitones (12 log2 ratio); n_samples: only the frames that start inside the recording."""
+    semitones (12 log2 ratio); n_samples: only the frames that start inside the recording.  period_fine (the fine tracker): a fourth
+    column, the refined period in samples."""
     with open(path, "w") as f:
-        f.write("time_s,period,semitones\n")
+        f.write("time_s,period,semitones\n" if period_fine is None else "time_s,period,semitones,period_fine\n")
         for i, (p, r) in enumerate(zip(period, ratio)):
             if n_samples is not None and i * int(hop) >= int(n_samples) and i > 0:
                 break
-            f.write("%.6f,%d,%.6f\n" % (i * int(hop) / float(fs), int(p), 12.0 * np.log2(float(r))))
+            f.write("%.6f,%d,%.6f" % (i * int(hop) / float(fs), int(p), 12.0 * np.log2(float(r))))
+            f.write("\n" if period_fine is None else ",%.6f\n" % float(period_fine[i]))
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------
@@ -850,6 +911,10 @@ def main(argv=None):
     ap.add_argument("--span", type=int, default=None, metavar="K", help="--transients: frames kept either side of an onset, 1 to 8 (default: frame / (2 hop))")
     ap.add_argument("--frame", type=int, default=1024, help="stretch, pvtune: frame length (1024 or 2048)")
     ap.add_argument("--track-csv", action="store_true", help="pvtune: also write NAME_pvtune.csv per recording (time, period, correction in semitones per frame)")
+    ap.add_argument("--fine", action="store_true",
+                    help="pvtune [--stream], harmonize --degrees [--stream]: the fine pitch tracker -- the period refined below one sample by a "
+                         "parabola through the difference function's minimum, the note looked up on the refined pitch; --track-csv gains a "
+                         "fourth column, the refined period")
     ap.add_argument("--lpc-voice", type=int, default=40)
     ap.add_argument("--lpc-synth", type=int, default=5)
     ap.add_argument("--block", type=int, default=1024)
@@ -904,11 +969,15 @@ def main(argv=None):
         raise SystemExit("--transients: valid only together with --locked (the phase reset is a variant of the peak-locked time stretch)")
     if a.span is not None and a.transients is None:
         raise SystemExit("--span: valid only together with --transients")
+    if a.fine and not (a.flow == "pvtune" or (a.flow == "harmonize" and a.degrees is not None)):
+        raise SystemExit("--fine: pvtune and harmonize --degrees take it (the flows that track the pitch)")
     fkw = {} if a.formant is None else dict(formant=a.formant, lifter=a.lifter)
     if a.locked:
         fkw["locked"] = True
     if a.subbin:
         fkw["subbin"] = True
+    if a.fine and a.flow == "pvtune":
+        fkw["fine"] = True
 
     recs = [read_wav(f) for f in a.inputs]
     fs = recs[0][0]
@@ -936,8 +1005,8 @@ def main(argv=None):
         except ValueError:
             raise SystemExit("--degrees: comma-separated integers expected; --gains: numbers; --glide: one number in (0, 1]")
         try:
-            outs, period, ratio = pv_harmonize_key(voices, fs, dg, key=a.key, gains=gains, dry=a.dry, hop=a.hop, N=a.block, stream=a.stream,
-                                                   hold=a.hold, glide=glide, device=a.device, with_track=True)
+            outs, period, ratio, *fine = pv_harmonize_key(voices, fs, dg, key=a.key, gains=gains, dry=a.dry, hop=a.hop, N=a.block, stream=a.stream,
+                                                          hold=a.hold, glide=glide, device=a.device, with_track=True, **({"fine": True} if a.fine else {}))
         except ValueError as e:
             raise SystemExit(str(e))
         rc = _write_outputs(a, fs, outs)
@@ -947,7 +1016,7 @@ def main(argv=None):
                 for v in range(len(dg)):
                     out = os.path.join(a.out_dir, os.path.splitext(os.path.basename(f))[0] + f"_harmonize_v{v}.csv")
                     write_track_csv(out, fs, step, period[:, s] if a.stream else period[s], ratio[:, s, v] if a.stream else ratio[s, v],
-                                    n_samples=voices[s].shape[-1])
+                                    n_samples=voices[s].shape[-1], **({"period_fine": fine[0][:, s] if a.stream else fine[0][s]} if fine else {}))
                     print(out)
         return rc
     if a.flow == "harmonize":
@@ -977,11 +1046,11 @@ def main(argv=None):
                     glide = 1.0 if a.glide is None else float(a.glide)
                 except ValueError:
                     raise SystemExit("pvtune --stream --glide: one number in (0, 1] expected")
-                outs, period, ratio = pv_autotune_stream(voices, fs, key=a.key, N=a.block, hop=a.hop, F=a.frame, hold=a.hold, glide=glide,
-                                                         device=a.device, with_track=True, **fkw)
-                period, ratio, step = period.T, ratio.T, a.block                    # a row per block, at the block's start
+                outs, period, ratio, *fine = pv_autotune_stream(voices, fs, key=a.key, N=a.block, hop=a.hop, F=a.frame, hold=a.hold, glide=glide,
+                                                                device=a.device, with_track=True, **fkw)
+                period, ratio, step, fine = period.T, ratio.T, a.block, [t.T for t in fine]   # a row per block, at the block's start
             else:
-                outs, period, ratio = pv_autotune(voices, fs, key=a.key, F=a.frame, hop=a.hop, device=a.device, with_track=True, **fkw)
+                outs, period, ratio, *fine = pv_autotune(voices, fs, key=a.key, F=a.frame, hop=a.hop, device=a.device, with_track=True, **fkw)
                 step = a.hop
         except ValueError as e:
             raise SystemExit(str(e))
@@ -989,7 +1058,7 @@ def main(argv=None):
         if a.track_csv:
             for s, f in enumerate(a.inputs):
                 out = os.path.join(a.out_dir, os.path.splitext(os.path.basename(f))[0] + "_pvtune.csv")
-                write_track_csv(out, fs, step, period[s], ratio[s], n_samples=voices[s].shape[-1])
+                write_track_csv(out, fs, step, period[s], ratio[s], n_samples=voices[s].shape[-1], **({"period_fine": fine[0][s]} if fine else {}))
                 print(out)
         return rc
     if a.flow == "pvshift":

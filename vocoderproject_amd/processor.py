@@ -161,6 +161,13 @@ def load_library():
         L.vp_stft_autotune.argtypes = [vp, fp, fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vp_stft_last_error.argtypes = [vp]
         L.vp_stft_last_error.restype = C.c_char_p
+    if hasattr(L, "vp_stft_track_pitch_fine"):         # (the fine tracker; absent from older libraries loaded through VP_AMD_LIB)
+        L.vp_stft_set_track_mode.argtypes = [vp, C.c_int]
+        L.vp_stft_get_track_mode.argtypes = [vp]
+        L.vp_stft_track_pitch_fine.argtypes = [vp, fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_pv_tracker_set_mode.argtypes = [vp, C.c_int]
+        L.vp_pv_tracker_get_mode.argtypes = [vp]
+        L.vp_pv_tracker_process_blocks_fine_device.argtypes = [vp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.vp_stft_set_runs.argtypes = [vp, C.c_int]
     L.vp_stft_set_precision.argtypes = [vp, C.c_int]
     L.vp_stft_get_precision.argtypes = [vp]
@@ -784,6 +791,7 @@ def _harm_levels(owner, V, gains, dry, dev):
     return table(gains, "gains", (S, V), [(V,), (S, V)], "gain"), table(dry, "dry", (S,), [(), (S,)], "dry")
 
 
+TRACK_INTEGER, TRACK_FINE = 0, 1        # VP_TRACK_INTEGER, VP_TRACK_FINE: the tracker mode of a handle
 HARM_MAX_DEGREE = 12                    # VP_TRACK_MAX_DEGREE: the kernels clamp a degree to +-12 steps of the key's table
 
 
@@ -1202,16 +1210,35 @@ class StftRoundTrip(_Handle):
             msg = self.L.vp_stft_last_error(self.h).decode()
             raise VpError(rc, msg or self.L.vp_error_string(rc).decode())
 
-    def track_pitch(self, d_in, sample_rate, keys=None, stream=None):
+    def set_track_mode(self, fine):
+        """fine=True: the calls that track (track_pitch, autotune, track_harmony, harmonize with degrees) use the fine tracker
+        (vp_stft_set_track_mode, VP_TRACK_FINE): the period refined below one sample by a parabola through the normalised difference
+        function's minimum, the note looked up on the refined pitch.  False (the default): the integer period, today's bits."""
+        rc = self.L.vp_stft_set_track_mode(self.h, TRACK_FINE if fine else TRACK_INTEGER)
+        if rc:
+            raise VpError(rc, self.L.vp_error_string(rc).decode())
+
+    @property
+    def track_fine(self):
+        return self.L.vp_stft_get_track_mode(self.h) == TRACK_FINE
+
+    def track_pitch(self, d_in, sample_rate, keys=None, stream=None, with_fine_period=False):
         """The pitch tracker (vp_stft_track_pitch): PitchProcess's YIN and nearest note for every frame of the batch at once.  Returns
         (period, ratio), device tensors int32 / float64 [S][n_frames]: the period in samples (0 = unvoiced) and the ratio
         closestFreq / pitch that moves the frame onto its key's nearest note (1.0 where unvoiced) -- the table pitch_shift_curve(d_ratio=...)
         takes.  keys: Notes::key per stream, 0..12 (12 = chromatic, also for any value outside the range): an int, a sequence of S ints or
         a device int32 tensor [S]; None = chromatic.  8000 <= sample_rate <= 51200 and n_samples >= frame_len + ceil(sample_rate / 100)
-        (VpError otherwise).  Frames are independent: no smoothing, no hold across unvoiced frames."""
+        (VpError otherwise).  Frames are independent: no smoothing, no hold across unvoiced frames.
+        with_fine_period=True: the fine tracker whatever the mode (vp_stft_track_pitch_fine); returns (period, ratio, period_fine), the
+        third a float64 [S][n_frames] table of refined periods (0.0 where unvoiced)."""
         import torch
         assert _is(d_in, torch.float32, (self.S, self.T))
         d_key, period, ratio = self._track_tables(keys, d_in.device)
+        if with_fine_period:
+            fine = torch.empty((self.S, self.n_frames), dtype=torch.float64, device=d_in.device)
+            self._track_chk(self.L.vp_stft_track_pitch_fine(self.h, d_in.data_ptr(), float(sample_rate), _ptr(d_key), period.data_ptr(), fine.data_ptr(),
+                                                            ratio.data_ptr(), _stream_of(stream, d_in)))
+            return period, ratio, fine
         self._track_chk(self.L.vp_stft_track_pitch(self.h, d_in.data_ptr(), float(sample_rate), _ptr(d_key), period.data_ptr(), ratio.data_ptr(),
                                                    _stream_of(stream, d_in)))
         return period, ratio
@@ -1585,6 +1612,15 @@ class StreamingPitchTracker(_StreamHandle):
         """0 <= hold_blocks <= 2^20 unvoiced blocks the last voiced ratio outlives, 0 < glide <= 1; every stream, from the next call on."""
         self._chk(self.L.vp_pv_tracker_set_follow(self.h, int(hold_blocks), float(glide)))
 
+    def set_fine(self, fine):
+        """fine=True: every process call of this tracker (mono, voices, and the composed autotune / autoharm calls) uses the fine raw
+        decision (vp_pv_tracker_set_mode, VP_TRACK_FINE) from the next call on; no stream state is touched.  False: the integer one."""
+        self._chk(self.L.vp_pv_tracker_set_mode(self.h, TRACK_FINE if fine else TRACK_INTEGER))
+
+    @property
+    def fine(self):
+        return self.L.vp_pv_tracker_get_mode(self.h) == TRACK_FINE
+
     def _tables(self, keys, n_blocks, dev):
         """(d_key or None, period, ratio) of a call of n_blocks blocks: the key table is kept per handle (one device int32 [S], rewritten
         on torch's current stream when `keys` is host data); the outputs are new tensors, the caller's to keep."""
@@ -1592,16 +1628,23 @@ class StreamingPitchTracker(_StreamHandle):
         d_key = _device_keys(self, keys, dev)
         return d_key, torch.empty((n_blocks, self.S), dtype=torch.int32, device=dev), torch.empty((n_blocks, self.S), dtype=torch.float64, device=dev)
 
-    def process_device(self, d_in, n_blocks=1, keys=None, stream=None):
+    def process_device(self, d_in, n_blocks=1, keys=None, stream=None, with_fine_period=False):
         """n_blocks blocks on the device: torch float32 [n_blocks][S][N] (or [S][N] for one block), the slab PhaseVocoderStream takes,
         enqueued on `stream` (default: the current torch stream) without synchronising.  keys as StftRoundTrip.track_pitch's.  Returns
-        (period, ratio), device tensors int32 / float64 [n_blocks][S]: the period in samples (0 = unvoiced) and the followed ratio."""
+        (period, ratio), device tensors int32 / float64 [n_blocks][S]: the period in samples (0 = unvoiced) and the followed ratio.
+        with_fine_period=True: the fine tracker whatever the mode (vp_pv_tracker_process_blocks_fine_device); returns (period, ratio,
+        period_fine), the third the raw decision's refined period, float64 [n_blocks][S] (0.0 unvoiced or while the ring fills)."""
         import torch
         shape = (self.S, self.N) if n_blocks == 1 and d_in.dim() == 2 else (int(n_blocks), self.S, self.N)
         assert d_in.is_cuda and d_in.dtype == torch.float32 and tuple(d_in.shape) == shape and d_in.is_contiguous()
         d_key, period, ratio = self._tables(keys, int(n_blocks), d_in.device)
         if stream is None:
             stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        if with_fine_period:
+            fine = torch.empty((int(n_blocks), self.S), dtype=torch.float64, device=d_in.device)
+            self._chk(self.L.vp_pv_tracker_process_blocks_fine_device(self.h, d_in.data_ptr(), _ptr(d_key), period.data_ptr(), fine.data_ptr(),
+                                                                      ratio.data_ptr(), int(n_blocks), C.c_void_p(stream)))
+            return period, ratio, fine
         self._chk(self.L.vp_pv_tracker_process_blocks_device(self.h, d_in.data_ptr(), d_key.data_ptr() if d_key is not None else None,
                                                              period.data_ptr(), ratio.data_ptr(), int(n_blocks), C.c_void_p(stream)))
         return period, ratio
